@@ -7,7 +7,8 @@
 One "step" = one skpangu_step() = one 6-h forward of the Pangu network on a synthetic state that is
 already resident in HBM (autoregressive, in place).  N > 1: one process per GPU, one ensemble member
 per rank (weak scaling, members are independent); the timed region ends with the RCCL reduction that
-forms the ensemble mean/spread of the final step.  Prints ONE JSON line on rank 0.
+forms the ensemble mean/spread of the final step.  Prints ONE JSON line on rank 0.  ``--dump-outputs DIR`` also writes what the last
+timed step computed as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs, so two builds compare output for output).
 
 At N = 1 the same line also carries, under "models", a short driver-timed run of the other two rows of the hot path (FourCastNet
 v2-small and GraphCast at 721x1440: ms per step, the roofline of the dominant stage, the committed profile it is read against);
@@ -393,6 +394,7 @@ def run_sfno(args, rank, local_rank, world, dist):
     finite = bool(torch.isfinite(x).all().item())
     if rank != 0:
         return
+    dumped = dump_outputs(args.dump_outputs, {"sfno_state": x}) if args.dump_outputs else None
     f_step = flops_per_step(cfg)
     dom = max(stats, key=lambda s: s["total_ms"])
     dom_ms = dom["total_ms"] / dom["launches"]
@@ -428,6 +430,8 @@ def run_sfno(args, rank, local_rank, world, dist):
                                             "dense_tflops": round(s["flops"] / (s["total_ms"] * 1e-3) / 1e12, 1),
                                             "alg_GBps": round(s["bytes"] / (s["total_ms"] * 1e-3) / 1e9, 1)} for s in stats}},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
         from oracle import sfno_oracle as O
         tr = O.Transforms(cfg)                           # quadrature / Legendre tables: setup, not timed (the engine prepares its own once, too)
@@ -511,6 +515,7 @@ def run_graphcast(args, rank, local_rank, world, dist):
     finite = bool(torch.isfinite(b).all().item())
     if rank != 0:
         return
+    dumped = dump_outputs(args.dump_outputs, {"graphcast_state": b}) if args.dump_outputs else None
     f_step = flops_per_step(cfg, cfg.n_lat * cfg.n_lon, g.n_mesh, len(g.mesh_edges), len(g.g2m_edges) * (world if sharded else 1), 3 * cfg.n_lat * cfg.n_lon)
     f_exec = flops_per_step_executed(cfg, cfg.n_lat * cfg.n_lon, g.n_mesh, len(g.mesh_edges), len(g.g2m_edges) * (world if sharded else 1), 3 * cfg.n_lat * cfg.n_lon)
     counts = (cfg, cfg.n_lat * cfg.n_lon, g.n_mesh, len(g.mesh_edges), len(g.g2m_edges) * (world if sharded else 1), 3 * cfg.n_lat * cfg.n_lon)
@@ -571,6 +576,8 @@ def run_graphcast(args, rank, local_rank, world, dist):
                                             "dense_tflops": round(s["flops"] / (s["total_ms"] * 1e-3) / 1e12, 1),
                                             "alg_GBps": round(alg.get(s["name"], 0.0) / (s["total_ms"] / args.steps * 1e-3) / 1e9, 1)} for s in stats}}),
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if world == 1 and not args.no_cpu_baseline:
         # bounded sample with one piece per cost class, each timed on the host cores and scaled by its own count (not by FLOPs alone:
         # the edge updates are gather / scatter-bound on a CPU): (1) the grid-node embedder on 1/8 of the grid (dense, per grid node);
@@ -654,7 +661,11 @@ def main():
                     "replicated, one all-reduce of the mesh aggregate per step) instead of running one member each; strong scaling")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo only to "
                     "exercise the multi-rank control flow on a box with fewer GPUs than ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's "
+                    "states; with --gpus > 1 also the ensemble mean / spread) as DIR/<name>.npy, under 64 MB in all (a fixed sample of larger arrays)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -754,6 +765,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     finite = bool(torch.isfinite(x).all().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {f"pangu_member{m}": xm for m, xm in zip(mine, xs)} if world > 1 else {"pangu_state": x}
+        if world > 1:
+            arrays.update(zip(("ensemble_mean", "ensemble_spread", "ensemble_members"), saved))
+        dumped = dump_outputs(args.dump_outputs, arrays)
 
     if rank == 0:
         timed = [s for s in stats if s["launches"] > 0]
@@ -808,6 +825,8 @@ def main():
                            for s in timed},
             },
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         kept = {}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, geom, x_host, kept)
@@ -848,7 +867,7 @@ def main():
             eng = x = xs = graphs = None             # release the Pangu engine's arenas and states before GraphCast's 47 GB
             torch.cuda.empty_cache()
             sub = copy.copy(args)
-            sub.steps, sub.warmup, sub.no_cpu_baseline, sub.no_parity, sub.shard = 5, 2, True, True, False
+            sub.steps, sub.warmup, sub.no_cpu_baseline, sub.no_parity, sub.shard, sub.dump_outputs = 5, 2, True, True, False, None
             out["models"] = {}
             for name, fn in (("sfno", run_sfno), ("graphcast", run_graphcast)):
                 try:
@@ -870,7 +889,8 @@ def main():
 def compact_line(out: dict) -> dict:
     """The line the driver records: everything BENCH_rNN.json must hold, under 3 KB.  The whole detail goes to bench_detail.json."""
     keep = lambda d, keys: {k: d[k] for k in keys if d is not None and k in d}  # noqa: E731
-    line = keep(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data"))
+    line = keep(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                      "dump_outputs"))
     cfg = out.get("config", {})
     line["config"] = {"workload": cfg.get("workload", "")[:160], "precision": cfg.get("precision", "")[:120], **keep(cfg, ("parallelism", "members", "finite", "calibration", "rounding", "term_plan", "guard"))}
     line["config"]["parallelism"] = str(line["config"].get("parallelism", ""))[:120]
@@ -901,6 +921,32 @@ def compact_line(out: dict) -> dict:
             line[k] = {kk: (keep(vv, ("ms_per_step",)) if isinstance(vv, dict) else vv) for kk, vv in line[k].items()}
     line["detail"] = "bench_detail.json"
     return line
+
+
+DUMP_BYTES = 60_000_000      # --dump-outputs: all arrays together, headers included, stay under 64 MB
+
+
+def dump_outputs(dest: str, arrays: dict) -> dict:
+    """``--dump-outputs DIR``: the arrays the timed path returned in its last step, one ``DIR/<name>.npy`` each (float32, or float64 when
+    computed so).  An array larger than its share of DUMP_BYTES keeps every channel (leading axis) at a fixed sample of the other positions:
+    a seeded permutation's first entries, in index order -- the same positions for the same shape in every run.  Returns name -> shapes."""
+    import numpy as np
+    os.makedirs(dest, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays)) - 4096
+    info = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        full = list(t.shape)
+        if t.numel() * t.element_size() > share:
+            flat = t.reshape(t.shape[0] if t.dim() > 1 else 1, -1)
+            keep = share // (flat.shape[0] * t.element_size())
+            idx = torch.randperm(flat.shape[1], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = flat[:, idx.to(flat.device)]
+        np.save(os.path.join(dest, name + ".npy"), t.cpu().numpy())
+        info[name] = {"shape": full, "saved": list(t.shape)}
+    return info
 
 
 def emit(out: dict):
