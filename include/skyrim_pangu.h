@@ -59,7 +59,7 @@ typedef struct skpangu_config {
 
 typedef struct skpangu_sizes {
     long long master_floats;   /* elements of the fp32 master parameter blob (skpangu_param_info layout) */
-    size_t prepared_bytes;     /* kernel-ready parameter arena (16-bit weight planes, expanded bias, tables) */
+    size_t prepared_bytes;     /* kernel-ready parameter arena (16-bit weight planes, compact bias tables, index tables) */
     size_t workspace_bytes;    /* activations of one step (residual streams, Q/K/V, MLP hidden) */
     long long state_floats;    /* 69 * n_lat * n_lon */
     int n_params;              /* entries of the master parameter table */
@@ -104,7 +104,7 @@ typedef struct skpangu_stage_stat {
 } skpangu_stage_stat;
 int skpangu_profile(skpangu_ctx* ctx, int enable);
 int skpangu_profile_read(skpangu_ctx* ctx, skpangu_stage_stat* out, int cap, int* n);
-/* Debug view of an internal buffer ("q","k","vt","ao","hid","u","x1","x2","x4","widx<res><roll>","bias_exp<blk>"); owned by the context's arenas. */
+/* Debug view of an internal buffer ("q","k","vt","ao","hid","u","x1","x2","x4","widx<res><roll>","bias_exp<blk>" = the compact bias table of block blk); owned by the context's arenas. */
 int skpangu_debug_buffer(skpangu_ctx* ctx, const char* name, void** ptr_dev, size_t* bytes);
 
 #ifdef __cplusplus

@@ -126,19 +126,17 @@ struct Engine : IEngine {
     Work<P> wk;
     std::vector<Param> params;
     size_t prep_bytes = 0, ws_bytes = 0;
-    size_t bias_exp_elems[16];
+    size_t bias_elems[16];
     size_t q_elems = 0, ao_elems = 0, hid_elems = 0;
-    bool fused_mlp = false;   // one-kernel MLP (fused_mlp.hip): 3-term modes with the hidden as hi/lo pair
-    bool rt_proj = false, rt_qkv = false;   // row-tile proj / QKV kernels (rowtile.hip)
-    bool fused_block = false;               // proj + LayerNorm + residual + MLP as one kernel (fused_block.hip)
-    bool attn2 = true;                      // attention with the bias gathered from the compact table in LDS (SKP_ATTN_V1=1: the expanded table)
+    bool rt_qkv = false;                    // row-tile QKV kernel (rowtile.hip)
+    bool fused_block = false;               // proj + LayerNorm + residual + MLP as one kernel (fused_block.hip); mlp_mode 1: the split GEMMs
     bool fused_qa = true;                   // QKV + attention as ONE kernel, q / k / v in registers (attention.hip; SKP_SPLIT_ATTN=1: the two launches)
     int plan2 = 0;                          // bit l: layer l + 1 runs proj / fc1 / fc2 with TWO terms (weights as one fp16 plane, fused_block2.hip)
     bool two_term(int layer) const { return (plan2 >> layer) & 1; }
     bool qkv_one(int layer) const { return rt_qkv && ((plan2 >> (4 + layer)) & 1); }   // QKV with ONE term (stream hi plane x weight hi plane)
     bool block_one(int layer) const { return (plan2 >> (8 + layer)) & 1; }             // proj / fc1 / fc2 with ONE term (activation hi plane x weight hi plane)
     // the fused QKV + attention kernel takes the row-tile QKV weights of a block: one plane at either width, hi / lo planes at C = 192 only (LDS)
-    bool qa_fused(const BlockW<T>& bw, int res) const { return fused_qa && rt_qkv && attn2 && bw.bias_cmp && (bw.qkvh || (bw.qkvf && res == 0)); }
+    bool qa_fused(int layer) const { return fused_qa && rt_qkv && (qkv_one(layer) || layer_res(layer) == 0); }
     T* zrow = nullptr;
     float *qkv_w_tmp = nullptr, *qkv_b_tmp = nullptr;
     float* cal_sum = nullptr;               // column sums of one GEMM operand (calibrate)
@@ -166,11 +164,9 @@ struct Engine : IEngine {
     hipError_t profile_read(skpangu_stage_stat* out, int cap, int* n) override {
         static const char* names_split[C_COUNT] = {"embed", "qkv_r0", "attn_r0", "proj_r0", "fc1_r0", "fc2_r0", "qkv_r1", "attn_r1",
                                                    "proj_r1", "fc1_r1", "fc2_r1", "downsample", "upsample", "recover"};
-        static const char* names_fused[C_COUNT] = {"embed", "qkv_r0", "attn_r0", "proj_r0", "mlp_r0", "fc2_r0", "qkv_r1", "attn_r1",
-                                                   "proj_r1", "mlp_r1", "fc2_r1", "downsample", "upsample", "recover"};
         static const char* names_block[C_COUNT] = {"embed", "qkv_r0", "attn_r0", "proj_r0", "proj_mlp_r0", "fc2_r0", "qkv_r1", "attn_r1",
                                                    "proj_r1", "proj_mlp_r1", "fc2_r1", "downsample", "upsample", "recover"};
-        const char* const* names = fused_block ? names_block : (fused_mlp ? names_fused : names_split);
+        const char* const* names = fused_block ? names_block : names_split;
         double ms[C_COUNT] = {0}; int cnt[C_COUNT] = {0};
         if (prof_used > 0) {
             hipError_t e = hipEventSynchronize(prof_ev[prof_used - 1]);
@@ -190,18 +186,23 @@ struct Engine : IEngine {
             const int o = r == 0 ? 0 : 5;
             fl[C_QKV0 + o] = 2 * mw * C * 3 * C;      by[C_QKV0 + o] = nt * C * 2 * NA_ + 3 * mw * C * 2 + 3 * C * C * wb;
             fl[C_ATTN0 + o] = g.nwin[r] * heads * 4.0 * 144 * 144 * 32;
-            by[C_ATTN0 + o] = 3 * mw * C * 2 + mw * C * sa + (double)g.types[r] * heads * (attn2 ? 3456 : 81 * 256) * 2;
+            by[C_ATTN0 + o] = 3 * mw * C * 2 + mw * C * sa + (double)g.types[r] * heads * 3456 * 2;
             fl[C_PROJ0 + o] = 2 * mw * C * C;          by[C_PROJ0 + o] = mw * C * sa + 2 * nt * C * 4 + C * C * wb;   // stream: 4 B/elem read + 4 B/elem written
             fl[C_FC1_0 + o] = 2 * nt * C * 4 * C;      by[C_FC1_0 + o] = nt * C * 2 * NA_ + nt * 4 * C * sa + 4 * C * C * wb;
             fl[C_FC2_0 + o] = 2 * nt * C * 4 * C;      by[C_FC2_0 + o] = nt * 4 * C * sa + 2 * nt * C * 4 + 4 * C * C * wb;
-            if (fused_qa && rt_qkv && attn2 && (r == 0 || (plan2 >> (4 + 1)) & 1)) {   // QKV inside the attention launch: its FLOPs, the stream's hi plane in, the output out
-                fl[C_ATTN0 + o] += fl[C_QKV0 + o];
-                by[C_ATTN0 + o] = nt * C * 2 + mw * C * sa + 3 * C * C * wb + (double)g.types[r] * heads * 3456 * 2;
+            // QKV inside the attention launch (qa_fused, decided per layer): its FLOPs, the stream's hi plane in, the output out.  A stage
+            // whose two layers differ reports the mean over its launches.
+            const int nblk = kDepths[r == 0 ? 0 : 1] + kDepths[r == 0 ? 3 : 2];
+            const int nqa = r == 0 ? (qa_fused(0) ? kDepths[0] : 0) + (qa_fused(3) ? kDepths[3] : 0)
+                                   : (qa_fused(1) ? kDepths[1] : 0) + (qa_fused(2) ? kDepths[2] : 0);
+            if (nqa > 0) {
+                const double qa_fl = fl[C_ATTN0 + o] + fl[C_QKV0 + o];
+                const double qa_by = nt * C * 2 + mw * C * sa + 3 * C * C * wb + (double)g.types[r] * heads * 3456 * 2;
+                fl[C_ATTN0 + o] = nqa == nblk ? qa_fl : (nqa * qa_fl + (nblk - nqa) * fl[C_ATTN0 + o]) / nblk;
+                by[C_ATTN0 + o] = nqa == nblk ? qa_by : (nqa * qa_by + (nblk - nqa) * by[C_ATTN0 + o]) / nblk;
             }
-            if (fused_mlp) {   // one kernel: both GEMMs, stream read once + written once, both weight matrices
+            if (fused_block) { // one kernel: projection + both MLP GEMMs, stream read once + written once, the attention rows read, all weights
                 fl[C_FC1_0 + o] = 4 * nt * C * 4 * C;  by[C_FC1_0 + o] = 2 * nt * C * 4 + 8 * C * C * wb;
-            }
-            if (fused_block) { // ... and the projection in front of them: + its FLOPs, + the attention rows read, + its weights
                 fl[C_FC1_0 + o] += 2 * mw * C * C;     by[C_FC1_0 + o] += nt * C * sa + C * C * wb;
             }
         }
@@ -243,9 +244,9 @@ struct Engine : IEngine {
                 bw.qkv = take_lin(a, 3 * c, c); bw.proj = take_lin(a, c, c);
                 bw.fc1 = take_lin(a, 4 * c, c); bw.fc2 = take_lin(a, c, 4 * c);
                 const bool t2 = two_term(layer);
-                bw.w1f = fused_mlp && !t2 ? a.take<T>((size_t)8 * c * c) : nullptr;      // 4c x c elements, hi + lo
-                bw.w2f = fused_mlp && !t2 ? a.take<T>((size_t)8 * c * c) : nullptr;
-                bw.projf = (rt_proj || fused_block) && !t2 ? a.take<T>((size_t)2 * c * c) : nullptr;
+                bw.w1f = fused_block && !t2 ? a.take<T>((size_t)8 * c * c) : nullptr;      // 4c x c elements, hi + lo
+                bw.w2f = fused_block && !t2 ? a.take<T>((size_t)8 * c * c) : nullptr;
+                bw.projf = fused_block && !t2 ? a.take<T>((size_t)2 * c * c) : nullptr;
                 bw.projh = t2 ? a.take<T>((size_t)c * c) : nullptr;                       // hi plane only
                 bw.w1h = t2 ? a.take<T>((size_t)4 * c * c) : nullptr;
                 bw.w2h = t2 ? a.take<T>((size_t)4 * c * c) : nullptr;
@@ -255,9 +256,8 @@ struct Engine : IEngine {
                 bw.fc1_b = a.take<float>(4 * c); bw.fc2_b = a.take<float>(c);
                 bw.n1_g = a.take<float>(c); bw.n1_b = a.take<float>(c);
                 bw.n2_g = a.take<float>(c); bw.n2_b = a.take<float>(c);
-                bias_exp_elems[b] = attn2 ? (size_t)g.types[res] * heads * 3456 : (size_t)g.types[res] * heads * 81 * 256;
-                bw.bias_exp = attn2 ? nullptr : a.take<f16>(bias_exp_elems[b]);
-                bw.bias_cmp = attn2 ? a.take<f16>(bias_exp_elems[b]) : nullptr;
+                bias_elems[b] = (size_t)g.types[res] * heads * 3456;
+                bw.bias_cmp = a.take<f16>(bias_elems[b]);
             }
         }
         w.down_g = a.take<float>(768); w.down_b = a.take<float>(768);
@@ -297,13 +297,8 @@ struct Engine : IEngine {
     }
 
     explicit Engine(const Geom& geom, int qkv_a1 = 0, int mlp_mode = 0, int term_plan = 0) : g(geom) {
-        attn2 = getenv("SKP_ATTN_V1") == nullptr;
         fused_qa = getenv("SKP_SPLIT_ATTN") == nullptr;
-        fused_mlp = (P::NA == 2 && P::NW == 2 && mlp_mode == 0);
-        // proj in row-tile form measures the same as the tiled GEMM (0.199 vs 0.197 ms at C = 384, 0.264 vs 0.264 at C = 192: with 16 rows
-        // per wave its LDS reads run at 2/3 of the LDS rate): kept behind SKP_RT_PROJ=1, the tiled LayerNorm GEMM stays the default
-        rt_proj = (P::NA == 2 && P::NW == 2 && mlp_mode == 0 && getenv("SKP_RT_PROJ") != nullptr);
-        fused_block = fused_mlp && getenv("SKP_SPLIT_BLOCK") == nullptr;
+        fused_block = mlp_mode == 0;
         rt_qkv = (std::is_same<P, PrecF16x3>::value && qkv_a1 && mlp_mode == 0);
         plan2 = (std::is_same<P, PrecF16x3>::value && fused_block) ? term_plan : 0;     // the two-term kernel exists for fp16 planes, fused form
         wk.qkv_a1 = qkv_a1;
@@ -357,15 +352,13 @@ struct Engine : IEngine {
                 CK(lin(bw.proj, P_(m, p + "attn.proj.weight"), c, c, c, 1, s));
                 CK(lin(bw.fc1, P_(m, p + "mlp.fc1.weight"), 4 * c, c, c, 1, s));
                 CK(lin(bw.fc2, P_(m, p + "mlp.fc2.weight"), c, 4 * c, 4 * c, 1, s));
-                if constexpr (P::NA == 2 && P::NW == 2) {
-                    if (bw.projf) CK(prep_rowtile_weights<T>(P_(m, p + "attn.proj.weight"), const_cast<T*>(bw.projf), c, c, s));
-                    if (bw.qkvf) CK(prep_rowtile_weights<T>(qkv_w, const_cast<T*>(bw.qkvf), 3 * c, c, s));
-                    if (bw.qkvh) CK(prep_rowtile_weights<T>(qkv_w, const_cast<T*>(bw.qkvh), 3 * c, c, s, 1));
-                    if (bw.w1f) CK(prep_mlp_weights<T>(P_(m, p + "mlp.fc1.weight"), P_(m, p + "mlp.fc2.weight"), const_cast<T*>(bw.w1f), const_cast<T*>(bw.w2f), c, s));
-                    if (bw.projh) {
-                        CK(prep_rowtile_weights<T>(P_(m, p + "attn.proj.weight"), const_cast<T*>(bw.projh), c, c, s, 1));
-                        CK(prep_mlp_weights<T>(P_(m, p + "mlp.fc1.weight"), P_(m, p + "mlp.fc2.weight"), const_cast<T*>(bw.w1h), const_cast<T*>(bw.w2h), c, s, 1));
-                    }
+                if (bw.projf) CK(prep_rowtile_weights<T>(P_(m, p + "attn.proj.weight"), const_cast<T*>(bw.projf), c, c, s));
+                if (bw.qkvf) CK(prep_rowtile_weights<T>(qkv_w, const_cast<T*>(bw.qkvf), 3 * c, c, s));
+                if (bw.qkvh) CK(prep_rowtile_weights<T>(qkv_w, const_cast<T*>(bw.qkvh), 3 * c, c, s, 1));
+                if (bw.w1f) CK(prep_mlp_weights<T>(P_(m, p + "mlp.fc1.weight"), P_(m, p + "mlp.fc2.weight"), const_cast<T*>(bw.w1f), const_cast<T*>(bw.w2f), c, s));
+                if (bw.projh) {
+                    CK(prep_rowtile_weights<T>(P_(m, p + "attn.proj.weight"), const_cast<T*>(bw.projh), c, c, s, 1));
+                    CK(prep_mlp_weights<T>(P_(m, p + "mlp.fc1.weight"), P_(m, p + "mlp.fc2.weight"), const_cast<T*>(bw.w1h), const_cast<T*>(bw.w2h), c, s, 1));
                 }
                 CK(copyf(bw.qkv_b, qkv_bias, 3 * c, s));
                 CK(copyf(bw.proj_b, P_(m, p + "attn.proj.bias"), c, s));
@@ -375,8 +368,7 @@ struct Engine : IEngine {
                 CK(copyf(bw.n1_b, P_(m, p + "norm1.bias"), c, s));
                 CK(copyf(bw.n2_g, P_(m, p + "norm2.weight"), c, s));
                 CK(copyf(bw.n2_b, P_(m, p + "norm2.bias"), c, s));
-                if (attn2) CK(prep_bias_compact(P_(m, p + "attn.bias_table"), const_cast<f16*>(bw.bias_cmp), g.types[res], heads, g.nH[res], (i & 1) ? g.roll_sign : 0, g.mask_value, s, g.bias_transposed));
-                else CK(prep_bias_expand(P_(m, p + "attn.bias_table"), const_cast<f16*>(bw.bias_exp), g.types[res], heads, g.nH[res], (i & 1) ? g.roll_sign : 0, g.mask_value, s, g.bias_transposed));
+                CK(prep_bias_compact(P_(m, p + "attn.bias_table"), const_cast<f16*>(bw.bias_cmp), g.types[res], heads, g.nH[res], (i & 1) ? g.roll_sign : 0, g.mask_value, s, g.bias_transposed));
             }
         }
         CK(copyf(w.down_g, P_(m, "down.norm.weight"), 768, s));
@@ -416,7 +408,7 @@ struct Engine : IEngine {
         bool fused = false;
         if constexpr (std::is_same<P, PrecF16x3>::value) {
             // QKV + attention in one launch: the row-tile QKV forms (stream hi plane; one weight plane, or hi / lo at C = 192) with the compact bias
-            if (qa_fused(bw, res)) {
+            if (qa_fused(layer0)) {
                 mark(C_ATTN0 + o, s);
                 CK(op_qkv_attention(g, bw, widx, res, xs, wk, s, block_one(layer0) ? 1 : 2));
                 fused = true;
@@ -431,7 +423,7 @@ struct Engine : IEngine {
                 CK((op_qkv<P>(g, bw, widx, res, xs, wk, s)));
             }
             mark(C_ATTN0 + o, s);
-            AttnArgs<P> a{wk.q, wk.k, wk.vt, wk.qkv_plane, bw.bias_exp, bw.bias_cmp, wk.ao, wk.ao_plane, C, g.nwin[res], g.nW[res], heads};
+            AttnArgs<P> a{wk.q, wk.k, wk.vt, bw.bias_cmp, wk.ao, wk.ao_plane, C, g.nwin[res], g.nW[res], heads};
             a.out_planes = block_one(layer0) ? 1 : 0;           // a one-term block kernel reads the hi plane only
             CK(launch_attention<P>(a, s));
         }
@@ -443,29 +435,16 @@ struct Engine : IEngine {
                 return hipSuccess;
             }
         }
-        if constexpr (P::NA == 2 && P::NW == 2) {
-            if (fused_block) {                    // everything after the attention in one kernel; timed under "mlp"
-                mark(C_FC1_0 + o, s);
-                CK((op_proj_mlp_fused<P>(g, bw, w.winv[res][i & 1], res, xs, wk, s)));
-                mark(-1, s);
-                return hipSuccess;
-            }
+        if (fused_block) {                        // everything after the attention in one kernel; timed under the fc1 category ("proj_mlp")
+            mark(C_FC1_0 + o, s);
+            CK((op_proj_mlp_fused<P>(g, bw, w.winv[res][i & 1], res, xs, wk, s)));
+            mark(-1, s);
+            return hipSuccess;
         }
+        // the split form: proj as the tiled LayerNorm GEMM (a row-tile proj measured the same: 0.199 vs 0.197 ms at C = 384, 0.264 vs
+        // 0.264 at C = 192 -- with 16 rows per wave its LDS reads run at 2/3 of the LDS rate), then fc1 and fc2
         mark(C_PROJ0 + o, s);
-        if constexpr (P::NA == 2 && P::NW == 2) {
-            if (rt_proj) CK((op_proj_rowtile<P>(g, bw, widx, res, xs, wk, s)));
-            else CK((op_proj<P>(g, bw, widx, res, xs, wk, s)));
-        } else {
-            CK((op_proj<P>(g, bw, widx, res, xs, wk, s)));
-        }
-        if constexpr (P::NA == 2 && P::NW == 2) {
-            if (fused_mlp) {                      // timed under the fc1 category ("mlp" when fused); fc2 has no launch of its own
-                mark(C_FC1_0 + o, s);
-                CK((op_mlp_fused<P>(g, bw, res, xs, wk, s)));
-                mark(-1, s);
-                return hipSuccess;
-            }
-        }
+        CK((op_proj<P>(g, bw, widx, res, xs, wk, s)));
         mark(C_FC1_0 + o, s);
         CK((op_fc1<P>(g, bw, res, xs, wk, s)));
         mark(C_FC2_0 + o, s);
@@ -533,7 +512,7 @@ struct Engine : IEngine {
         if (q1) CK(colsum_planes<T>(xs, 0, 1, nullptr, ntok, C, scratch, cal_sum, s));                       // one-term QKV reads the stream's hi plane
         CK((op_qkv<P>(g, bw, widx, res, xs, wk, s)));
         if (q1) CK(bias_fold(qkv_w, cal_sum, inv, const_cast<float*>(bw.qkv_b), 3 * C, C, s));
-        AttnArgs<P> a{wk.q, wk.k, wk.vt, wk.qkv_plane, bw.bias_exp, bw.bias_cmp, wk.ao, wk.ao_plane, C, g.nwin[res], g.nW[res], heads};
+        AttnArgs<P> a{wk.q, wk.k, wk.vt, bw.bias_cmp, wk.ao, wk.ao_plane, C, g.nwin[res], g.nW[res], heads};
         CK(launch_attention<P>(a, s));
         if (t2) CK(colsum_planes<T>(wk.ao, wk.ao_plane, npl, w.winv[res][i & 1], ntok, C, scratch, cal_sum, s));   // window rows of the real tokens
         CK((op_proj<P>(g, bw, widx, res, xs, wk, s)));
@@ -618,7 +597,7 @@ struct Engine : IEngine {
         if (n.rfind("bias_exp", 0) == 0) {
             const int b = atoi(n.c_str() + 8);
             if (b < 0 || b > 15) return false;
-            return set(attn2 ? w.blk[b].bias_cmp : w.blk[b].bias_exp, bias_exp_elems[b] * sizeof(f16));
+            return set(w.blk[b].bias_cmp, bias_elems[b] * sizeof(f16));
         }
         return false;
     }

@@ -1,11 +1,10 @@
 // Earth-specific 3D window attention (EarthAttention3D core) for gfx950.
 //
-// One wavefront = one (window, head): 144 tokens x head_dim 32.  Everything a wave needs is read
-// straight into MFMA fragment registers -- Q/K rows are 64-byte contiguous, V arrives transposed
-// ([d][token], written that way by the QKV epilogue) so each lane's 4 keys are 8 contiguous bytes,
-// and the earth-specific bias (+ shifted-window mask) is pre-expanded per (window type, head) in
-// exactly the accumulator layout.  No LDS, no barriers; the only cross-lane traffic is the 2-step
-// butterfly of the softmax row reduction.
+// One wavefront = one (window, head): 144 tokens x head_dim 32.  Q / K / V are read straight into MFMA
+// fragment registers -- Q/K rows are 64-byte contiguous, V arrives transposed ([d][token], written that
+// way by the QKV epilogue) so each lane's 4 keys are 8 contiguous bytes -- and the earth-specific bias
+// (+ shifted-window mask) is gathered from its compact table, staged in LDS once per (window type, head).
+// The only cross-lane traffic besides that is the 2-step butterfly of the softmax row reduction.
 //
 //   S^T[key][q] = K Q^T   (A = K frag, B = Q frag)   -> lane (q = l&15) holds 4 keys per fragment
 //   O^T[d][q]   = V^T P^T (A = V^T frag, B = P frag) -> lane (q = l&15) holds 4 head-dim rows per fragment
@@ -75,105 +74,10 @@ __device__ __forceinline__ void attn_softmax_pv(f32x4 (&s)[9], const uint4 (&vf)
 // rounding-sensitive part of the network (measured on the oracle: fp16 q/k/v -> 7e-5, fp16 P -> 4e-5 per-channel
 // error, vs 3.3e-4 / 3.6e-4 for the attention output / MLP hidden, which therefore stay hi/lo split), so
 // QK^T and PV are one MFMA term each and the Q/K/V round trip through HBM is 2 bytes per element.
-// 165 VGPRs -> three waves per SIMD (the default schedule takes 189 = two; four would spill ~40 registers)
-template <class TO, int NPL_O>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) earth_attention_kernel(const f16* __restrict__ q, const f16* __restrict__ k,
-                                                              const f16* __restrict__ vt, long long plane,
-                                                              const f16* __restrict__ bias_exp, TO* __restrict__ out, long long out_plane,
-                                                              int ld_out, int n_win, int nW, int heads) {
-    typedef f16 T;
-    constexpr int NPL = 1;
-    const int lane = threadIdx.x & 63;
-    const long long wg = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (wg >= (long long)n_win * heads) return;
-    // consecutive waves share (type, head) -> the expanded bias tile stays hot in L2
-    const int wi = (int)(wg % nW);
-    const int th = (int)(wg / nW);
-    const int head = th % heads, type = th / heads;
-    const int win = type * nW + wi;
-    const long long base = (long long)win * heads + head;
-    const int l15 = lane & 15, g = lane >> 4;
-
-    const T* qp = q + base * (WIN_TOKENS * HEAD_DIM) + l15 * HEAD_DIM + g * 8;
-    const T* kp = k + base * (WIN_TOKENS * HEAD_DIM) + g * 8;
-    const T* vp = vt + base * (WIN_TOKENS * HEAD_DIM) + (8 * (l15 >> 2) + (l15 & 3)) * WIN_TOKENS;      // + 4 df rows
-    const f16* bp = bias_exp + ((long long)type * heads + head) * (81 * 256);
-
-    uint4 kf[NPL][9];
-#pragma unroll
-    for (int p = 0; p < NPL; ++p)
-#pragma unroll
-        for (int f = 0; f < 9; ++f) kf[p][f] = *reinterpret_cast<const uint4*>(kp + p * plane + attn_key(f, l15) * HEAD_DIM);
-
-    uint4 vf[NPL][2][5];
-#pragma unroll
-    for (int p = 0; p < NPL; ++p)
-#pragma unroll
-        for (int df = 0; df < 2; ++df)
-#pragma unroll
-            for (int kb = 0; kb < 5; ++kb) {
-                const T* s = vp + p * plane + df * 4 * WIN_TOKENS;
-                if (kb < 4) vf[p][df][kb] = *reinterpret_cast<const uint4*>(s + kb * 32 + g * 8);
-                else { const uint2 lo = *reinterpret_cast<const uint2*>(s + 128 + g * 4); vf[p][df][kb] = make_uint4(lo.x, lo.y, 0, 0); }
-            }
-
-    // software prefetch: Q fragment and the 9 bias/mask fragments of query block qf+1 are in flight while block qf
-    // computes (one exposed L2/HBM round trip per window instead of nine)
-    uint4 qn[NPL];
-    uint4 bn[4];
-    uint2 bn8;
-#pragma unroll
-    for (int p = 0; p < NPL; ++p) qn[p] = *reinterpret_cast<const uint4*>(qp + p * plane);
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) bn[kb] = *reinterpret_cast<const uint4*>(bp + kb * 512 + lane * 8);
-    bn8 = *reinterpret_cast<const uint2*>(bp + 2048 + lane * 4);
-#pragma unroll 1
-    for (int qf = 0; qf < 9; ++qf) {
-        uint4 qv[NPL];
-        uint4 bcur[4];
-#pragma unroll
-        for (int p = 0; p < NPL; ++p) qv[p] = qn[p];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) bcur[kb] = bn[kb];
-        const uint2 bcur8 = bn8;
-        if (qf < 8) {
-#pragma unroll
-            for (int p = 0; p < NPL; ++p) qn[p] = *reinterpret_cast<const uint4*>(qp + p * plane + (qf + 1) * 16 * HEAD_DIM);
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb) bn[kb] = *reinterpret_cast<const uint4*>(bp + (qf + 1) * 2304 + kb * 512 + lane * 8);
-            bn8 = *reinterpret_cast<const uint2*>(bp + (qf + 1) * 2304 + 2048 + lane * 4);
-        }
-
-        // the bias / mask tile is the accumulator the score MFMA starts from (one conversion per value, no add)
-        f32x4 s[9];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-            const typename OpT<f16>::v8 b = as_v8<f16>(bcur[kb]);
-            s[2 * kb] = f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
-            s[2 * kb + 1] = f32x4{(float)b[4], (float)b[5], (float)b[6], (float)b[7]};
-        }
-        {
-            typedef f16 h4 __attribute__((ext_vector_type(4)));
-            const h4 b = __builtin_bit_cast(h4, bcur8);
-            s[8] = f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
-        }
-#pragma unroll
-        for (int f = 0; f < 9; ++f) s[f] = OpT<T>::mfma(as_v8<T>(kf[0][f]), as_v8<T>(qv[0]), s[f]);
-        f32x4 o[2], osum;
-        attn_softmax_pv(s, vf[0], o, osum);
-        const float inv = __builtin_amdgcn_rcpf(osum[0]);
-        // blocked [row/16][col/32][16][32] layout: this head's 32 columns are exactly one column block
-        TO* orow = out + blk_off((long long)win * WIN_TOKENS + qf * 16 + l15, head * HEAD_DIM, ld_out) + g * 8;
-        const float y[8] = {o[0][0] * inv, o[0][1] * inv, o[0][2] * inv, o[0][3] * inv, o[1][0] * inv, o[1][1] * inv, o[1][2] * inv, o[1][3] * inv};
-        store8_planes<TO, NPL_O>(orow, out_plane, y);
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------------------------------------- //
-//  The same attention with the earth-specific bias GATHERED from its compact table ("bias gathered from the compact
-//  (3312, type, head) table in-kernel"): the expanded tiles above are 41 KB of the 86 KB a wave moves, and the kernel is bound by the
-//  CU's memory pipeline.  One workgroup = one (window type, head); its four waves walk the type's nW longitude windows, which all
+//
+// The earth-specific bias is GATHERED from its compact table ("bias gathered from the compact (3312, type, head) table
+// in-kernel"): expanded per (type, head) in the accumulator layout it would be 41 KB of the 86 KB a wave moves, and the kernel is bound
+// by the CU's memory pipeline.  One workgroup = one (window type, head); its four waves walk the type's nW longitude windows, which all
 //  share ONE bias.  The workgroup stages that bias in LDS once, from the prepared [144][24] fp16 form (prep_bias_compact: row =
 //  (z_q + 2 z_k) 36 + (h_q + 6 h_k), column = w_k - w_q + 11, shifted-window mask folded into the rows): a lane's four consecutive keys
 //  are then four consecutive fp16 of one row -- one ds_read_b64, IF the address is 8-byte aligned, which depends on w_q mod 4 only:
@@ -540,20 +444,13 @@ hipError_t op_qkv_attention(const Geom& g, const BlockW<f16>& b, const int* widx
 template <class P>
 hipError_t launch_attention(const AttnArgs<P>& a, hipStream_t stream) {
     constexpr int NPL_O = (P::NA > P::NW ? P::NA : P::NW);
-    if (a.bias_cmp) {
-        const int types = a.n_win / a.nW;
-        if (a.out_planes == 1)
-            hipLaunchKernelGGL((earth_attention2_kernel<typename P::T, 1>), dim3((unsigned)(types * a.heads)), dim3(256), 0, stream,
-                               a.q, a.k, a.vt, a.bias_cmp, a.out, a.out_plane, a.ld_out, a.nW, a.heads);
-        else
-            hipLaunchKernelGGL((earth_attention2_kernel<typename P::T, NPL_O>), dim3((unsigned)(types * a.heads)), dim3(256), 0, stream,
-                               a.q, a.k, a.vt, a.bias_cmp, a.out, a.out_plane, a.ld_out, a.nW, a.heads);
-        return hipGetLastError();
-    }
-    const long long waves = (long long)a.n_win * a.heads;
-    const unsigned blocks = (unsigned)((waves + 3) / 4);
-    hipLaunchKernelGGL((earth_attention_kernel<typename P::T, NPL_O>), dim3(blocks), dim3(256), 0, stream,
-                       a.q, a.k, a.vt, a.plane, a.bias_exp, a.out, a.out_plane, a.ld_out, a.n_win, a.nW, a.heads);
+    const int types = a.n_win / a.nW;
+    if (a.out_planes == 1)
+        hipLaunchKernelGGL((earth_attention2_kernel<typename P::T, 1>), dim3((unsigned)(types * a.heads)), dim3(256), 0, stream,
+                           a.q, a.k, a.vt, a.bias_cmp, a.out, a.out_plane, a.ld_out, a.nW, a.heads);
+    else
+        hipLaunchKernelGGL((earth_attention2_kernel<typename P::T, NPL_O>), dim3((unsigned)(types * a.heads)), dim3(256), 0, stream,
+                           a.q, a.k, a.vt, a.bias_cmp, a.out, a.out_plane, a.ld_out, a.nW, a.heads);
     return hipGetLastError();
 }
 

@@ -32,55 +32,15 @@ template hipError_t prep_weight<bf16, 2>(const float*, bf16*, long long, int, in
 template hipError_t prep_weight<f16, 1>(const float*, f16*, long long, int, int, int, long long, long long, int, int, hipStream_t);
 template hipError_t prep_weight<f16, 2>(const float*, f16*, long long, int, int, int, long long, long long, int, int, hipStream_t);
 
-// Earth-specific bias gathered from the compact (3312, types, heads) table into the attention kernel's accumulator
-// order (attention.hip, attn_key()): per (type, head, query fragment qf) one 2304-element tile laid out as
-//   [kb = 0..3][lane][8]   keys 32 kb + 8 (lane >> 4) + [0..7]  (fragment pair 2kb, 2kb+1: one 16-byte load per lane)
-//   [lane][4]              keys 128 + 4 (lane >> 4) + [0..3]    (fragment 8)
-// with q = 16 qf + (lane & 15) and
-//   index = (z_q + 2 z_k) * 23*36 + (h_q + 6 h_k) * 23 + (w_q - w_k + 11)   (pseudocode _construct_index)
-// Odd (rolled) blocks fold the shifted-window mask in: mask_value where q and key sit in different Swin
-// regions of the Z window / latitude window that mixes wrapped and unwrapped rows -- the LAST one when the block
-// rolls by -(1,3,6) first (roll = -1), the FIRST one when it rolls by +(1,3,6) first (roll = +1); longitude is
-// periodic -> never masked.
-__global__ void prep_bias_expand_kernel(const float* __restrict__ table, f16* __restrict__ out, int types, int heads, int nH, int roll, float mask_value, int transposed) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)types * heads * 81 * 256;
-    if (i >= total) return;
-    const int e = (int)(i % 2304);
-    long long rest = i / 2304;
-    const int qf = (int)(rest % 9); rest /= 9;
-    const int head = (int)(rest % heads);
-    const int type = (int)(rest / heads);
-    int lane, key;
-    if (e < 2048) { const int kb = e >> 9; lane = (e >> 3) & 63; key = 32 * kb + 8 * (lane >> 4) + (e & 7); }
-    else          { lane = ((e - 2048) >> 2) & 63; key = 128 + 4 * (lane >> 4) + (e & 3); }
-    const int q = qf * 16 + (lane & 15);
-    const int zq = q / 72, hq = (q / 12) % 6, wq = q % 12;
-    const int zk = key / 72, hk = (key / 12) % 6, wk = key % 12;
-    // transposed: the table is read as [key][query] -- the two meshgrid axes of position_index change roles
-    const int idx = transposed ? (zk + 2 * zq) * (23 * 36) + (hk + 6 * hq) * 23 + (wk - wq + 11) : (zq + 2 * zk) * (23 * 36) + (hq + 6 * hk) * 23 + (wq - wk + 11);
-    float v = table[((long long)idx * types + type) * heads + head];
-    if (roll) {
-        const int zi = type / nH, hi = type % nH;
-        const int nZ = types / nH;
-        const bool mz = (zi == (roll < 0 ? nZ - 1 : 0)) && (zq != zk);
-        const bool mh = (hi == (roll < 0 ? nH - 1 : 0)) && ((hq < 3) != (hk < 3));
-        if (mz || mh) v += mask_value;
-    }
-    out[i] = (f16)v;
-}
-
-hipError_t prep_bias_expand(const float* table, f16* out, int types, int heads, int nH, int roll, float mask_value, hipStream_t s, int transposed) {
-    const long long total = (long long)types * heads * 81 * 256;
-    hipLaunchKernelGGL(prep_bias_expand_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, table, out, types, heads, nH, roll, mask_value, transposed);
-    return hipGetLastError();
-}
-
-// The same table in the COMPACT form the second attention kernel gathers from (attention.hip, earth_attention2_kernel): per (type, head)
+// Earth-specific bias, from the (3312, types, heads) table indexed as in the pseudocode's _construct_index:
+//   index = (z_q + 2 z_k) * 23*36 + (h_q + 6 h_k) * 23 + (w_q - w_k + 11)
+// in the COMPACT form the attention kernels gather from (attention.hip, earth_attention2_kernel): per (type, head)
 // 144 rows r = (z_q + 2 z_k) 36 + (h_q + 6 h_k) of 24 fp16, column e = 22 - (w_q - w_k + 11) = w_k - w_q + 11 (reversed, so that
-// four consecutive keys w_k .. w_k + 3 of one query are four consecutive ASCENDING entries), column 23 zero.  The shifted-window
-// mask depends on (type, z_q, z_k, h_q, h_k) only -- exactly a row -- and is folded into the row.  6.9 KB per (type, head) where the
-// expanded form takes 41 KB.
+// four consecutive keys w_k .. w_k + 3 of one query are four consecutive ASCENDING entries), column 23 zero.  6.9 KB per (type, head).
+// Odd (rolled) blocks fold the shifted-window mask in: mask_value where q and key sit in different Swin regions of the Z window /
+// latitude window that mixes wrapped and unwrapped rows -- the LAST one when the block rolls by -(1,3,6) first (roll = -1), the FIRST
+// one when it rolls by +(1,3,6) first (roll = +1); longitude is periodic -> never masked.  The mask depends on (type, z_q, z_k, h_q, h_k)
+// only -- exactly a row -- and is folded into the row.
 __global__ void prep_bias_compact_kernel(const float* __restrict__ table, f16* __restrict__ out, int types, int heads, int nH, int roll, float mask_value, int transposed) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long total = (long long)types * heads * 3456;

@@ -16,7 +16,7 @@ struct Block2Args {
     float eps;
 };
 
-// two consecutive 1 KiB fragments; the scheduling barrier pins the reads HERE in program order (fused_mlp.hip: ld_pair)
+// two consecutive 1 KiB fragments; the scheduling barrier pins the reads HERE in program order (fused_mlp.hip)
 __device__ __forceinline__ void sk_ld2(const char* p, uint4 (&w)[2]) {
     w[0] = *reinterpret_cast<const uint4*>(p);
     w[1] = *reinterpret_cast<const uint4*>(p + 1024);

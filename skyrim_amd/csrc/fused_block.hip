@@ -5,7 +5,7 @@
 // t runs over the stream's tokens, win(t) = the inverse of the window table (window reverse + un-roll + crop as a GATHER of the
 // attention output's rows: the stream itself is read and written in whole 1 KiB blocks, and the tile count is that of the tokens --
 // 1024 tiles = 4 full rounds of the 256 CUs at 91 x 180 x 8, where the 5.5 % of padded window rows would make it 1080 = 5 rounds).
-// It is rowtile.hip's projection followed by fused_mlp.hip's MLP on the same register-resident rows:
+// It is a projection in the row-tile form of rowtile.hip followed by fused_mlp.hip's MLP on the same register-resident rows:
 //
 //   phase 1  projection: the wave's FM x 16 attention rows are MFMA B-operand fragments (hi / lo planes), the weights stream through
 //            LDS in blocks of 32 output columns (two stages, one barrier per block), the C outputs of a row end up in its lane quad's

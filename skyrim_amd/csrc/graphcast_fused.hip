@@ -32,7 +32,6 @@
 // the fly from fp32 rows, three MFMA terms, one 16-row group per wave, concatenated sources taken one after the other.
 //
 // gfx950 only.  One workgroup (4 waves, one per SIMD, 512 registers) per CU; grid = tiles.
-#include <cstdlib>
 #include "../../include/skyrim_graphcast.h"
 #include "gemm_dma.h"
 
@@ -72,11 +71,10 @@ struct EdgeArgs {
     float* heads;           // [tiles][512] continuation pieces (runs longer than a tile)
     float eps;
     long long* probe;       // nullable: [tiles][8] shader clocks of wave 0 at the phase boundaries (measurement only)
-    int xcd_order;          // 1: XCD x works through the contiguous tile range x (SKGC_XCD_TILE_ORDER=1); 0: launch order
 };
 
 // NB consecutive 1 KiB fragments per step through a ring of RD steps, read RD - 1 steps ahead of their MFMAs; the scheduling barrier pins
-// the reads in program order (fused_mlp.hip: ld_pair)
+// the reads in program order (fused_mlp.hip)
 template <int NB>
 __device__ __forceinline__ void fz_ld(const char* p, uint4 (&w)[NB]) {
 #pragma unroll
@@ -202,15 +200,11 @@ edge_update_kernel(const EdgeArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned lds_base = (unsigned)(size_t)smem;
     const char* lrd = smem + lane * 16;
-    // The tile of this workgroup: launch order, or (opt-in, SKGC_XCD_TILE_ORDER=1) XCD x working through the contiguous tile range x -- workgroups
-    // reach the 8 XCDs round-robin, so that keeps neighbouring tiles (receiver-sorted edges) on one L2.  Measured at full size: the processor
-    // kernel fetches 8 % less (1.41 -> 1.30 GB per launch; the sender rows still miss: the multi-mesh numbers its nodes level by level, not by
-    // position) and runs 0.8 % SLOWER (22.8 -> 23.0 ms per step over the 16 layers), so launch order stays the default.
-    int tile_id = blockIdx.x;
-    if (a.xcd_order) {
-        const int T = gridDim.x, q = T >> 3, r = T & 7, x = tile_id & 7, slot = tile_id >> 3;
-        tile_id = x < r ? x * (q + 1) + slot : r * (q + 1) + (x - r) * q + slot;
-    }
+    // The tile of this workgroup: launch order.  XCD x working through the contiguous tile range x instead (workgroups reach the 8 XCDs
+    // round-robin, so that keeps neighbouring tiles -- receiver-sorted edges -- on one L2) was measured at full size: the processor kernel
+    // fetches 8 % less (1.41 -> 1.30 GB per launch; the sender rows still miss: the multi-mesh numbers its nodes level by level, not by
+    // position) and runs 0.8 % SLOWER (22.8 -> 23.0 ms per step over the 16 layers).
+    const int tile_id = blockIdx.x;
     const long long tile0 = (long long)tile_id * FZ_TILE;
     auto stamp = [&](int k) {
         if (a.probe != nullptr && tid == 0) a.probe[(long long)blockIdx.x * 8 + k] = (long long)__builtin_amdgcn_s_memtime();
@@ -784,8 +778,6 @@ int skgc_edge_update(const skgc_edge_desc* d, void* stream) {
     a.recv = d->recv; a.w1f = static_cast<const f16*>(d->w1f); a.w2f = static_cast<const f16*>(d->w2f);
     a.b2 = d->b2; a.gamma = d->gamma; a.beta = d->beta; a.agg = d->agg; a.heads = d->heads; a.eps = 1e-5f;
     a.probe = d->probe;
-    static const bool xcd_order = getenv("SKGC_XCD_TILE_ORDER") != nullptr;
-    a.xcd_order = xcd_order ? 1 : 0;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (d->has_fc1) {
         if (d->w1_planes == 2) {

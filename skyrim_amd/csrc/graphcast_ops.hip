@@ -4,7 +4,6 @@
 // concat(edge latent, sender latent, receiver latent) from the three row-major sources through the edge's index arrays
 // (k-contiguous 32-byte reads), so a 3.1 M-edge x 1536-wide matrix (19 GB) stays virtual.  Same 3-term fp16 MFMA pipeline as
 // the SFNO GEMMs (strided_gemm.h / gemm.h); LayerNorm and the receiver sum are small HBM-bound kernels.
-#include <cstdlib>
 #include <type_traits>
 #include "../../include/skyrim_graphcast.h"
 #include "strided_gemm.h"
@@ -130,13 +129,11 @@ struct SinkRowsF32 {
 };
 
 // the tile spans the latent (N = 512): 128 rows x 512 columns, 8 waves as 2 x 4 with 64 x 128 wave tiles (96 MFMAs per wave and
-// k-step against one 64 KB weight k-tile; the 64-row tile TLN64 re-stages that weight tile twice as often)
-typedef TileCfg<64, 512, 32, 1, 8> TLN64;
+// k-step against one 64 KB weight k-tile; a 64-row tile would re-stage that weight tile twice as often)
 typedef TileCfg<128, 512, 32, 2, 4> TLN128;
 // groups of three rows summed after the LayerNorm (skgc_sum_desc::group == 3): 2 x 4 waves with 48 x 128 wave tiles, fragment a of a
 // wave tile = member a of its 16 groups, so the sum over the members is a sum over a lane's own registers
 typedef TileCfg<96, 512, 32, 2, 4> TLN96;
-static int ln_tile_rows() { static const int v = [] { const char* e = getenv("SKGC_LN_TILE"); return e ? atoi(e) : 128; }(); return v; }
 
 template <class TLN, bool RES>
 __global__ void __launch_bounds__(TLN::THREADS) linear_ln_kernel(const GemmArgs<PrecF16x3, ALStrided, EpLayerNorm<RowMapIndexed, SinkRowsF32<RES>>> g) {
@@ -358,7 +355,6 @@ int skgc_prepare_weight_perm8(const float* src, int N, int K, void* dst, long lo
 int skgc_linear_layer_norm(const float* a, long long lda, int K, const void* w, long long w_plane, int ldw, const float* bias, const float* gamma,
                            const float* beta, const float* res, float* out, long long rows, void* stream) {
     if (!a || !w || !gamma || !beta || !out || rows <= 0 || rows > 0x7fffffff || K <= 0 || lda < K || (ldw & 7) || ldw < K) return SKGC_E_ARG;
-    if (ln_tile_rows() == 64) return linear_layer_norm_t<TLN64>(a, lda, K, w, w_plane, ldw, bias, gamma, beta, res, out, rows, stream);
     return linear_layer_norm_t<TLN128>(a, lda, K, w, w_plane, ldw, bias, gamma, beta, res, out, rows, stream);
 }
 
@@ -382,7 +378,6 @@ int skgc_sum_linear_layer_norm(const skgc_sum_desc* d, void* stream) {
         return sum3_linear_layer_norm(d, al, stream);
     }
     if (d->group != 0 && d->group != 1) return SKGC_E_ARG;
-    if (ln_tile_rows() == 64) return sum_linear_layer_norm_t<TLN64>(d, al, stream);
     return sum_linear_layer_norm_t<TLN128>(d, al, stream);
 }
 

@@ -23,13 +23,12 @@ struct LinW { const T* w; long long plane; int ldw; };   // [N][ldw] hi plane (+
 template <class T>
 struct BlockW {
     LinW<T> qkv, proj, fc1, fc2;
-    const T *w1f, *w2f;      // fc1 / fc2 in the fused MLP's fragment order (fused_mlp.hip), or null
-    const T *projf, *qkvf;   // proj / qkv in the row-tile kernels' fragment order (rowtile.hip), or null
+    const T *w1f, *w2f;      // fc1 / fc2 in the fused MLP's fragment order (prep_mlp_weights: the block kernel, fused_block.hip), or null
+    const T *projf, *qkvf;   // proj / qkv in the row-tile fragment order (prep_rowtile_weights: fused_block.hip / rowtile.hip), or null
     const T *projh, *w1h, *w2h;   // proj / fc1 / fc2 in fragment order, HI PLANE ONLY: the two-term block kernel (fused_block2.hip), or null
     const T* qkvh;                // qkv in fragment order, hi plane only: the one-term QKV of the term plan, or null
     const float *qkv_b, *proj_b, *fc1_b, *fc2_b, *n1_g, *n1_b, *n2_g, *n2_b;
-    const f16* bias_exp;     // [types][heads][9][9][64][4] (+ shifted-window mask on odd blocks): the first attention kernel; or null
-    const f16* bias_cmp;     // [types][heads][144][24] compact, w reversed (+ mask): the second attention kernel; or null
+    const f16* bias_cmp;     // [types][heads][144][24] compact, w reversed (+ shifted-window mask on odd blocks): the attention kernels
 };
 
 template <class T>
@@ -65,9 +64,7 @@ struct Work {
 template <class P>
 struct AttnArgs {
     const f16 *q, *k, *vt;
-    long long plane;
-    const f16* bias_exp;
-    const f16* bias_cmp;     // non-null: earth_attention2_kernel (bias gathered from the compact table staged in LDS)
+    const f16* bias_cmp;     // earth_attention2_kernel: the bias is gathered from the compact table staged in LDS
     typename P::T* out;
     long long out_plane;
     int ld_out, n_win, nW, heads;
@@ -91,11 +88,9 @@ template <class P> hipError_t op_fc1(const Geom&, const BlockW<typename P::T>&, 
 template <class P> hipError_t op_fc2(const Geom&, const BlockW<typename P::T>&, int res, typename P::T* Xs, const Work<P>&, hipStream_t);
 template <class P> hipError_t op_down(const Geom&, const ModelW<typename P::T>&, const typename P::T* X1s, typename P::T* X2s, const Work<P>&, hipStream_t);
 template <class P> hipError_t op_up(const Geom&, const ModelW<typename P::T>&, const typename P::T* X2s, typename P::T* X4s, const Work<P>&, hipStream_t);
-// fc1 -> GELU -> fc2 -> LayerNorm -> residual in one kernel (3-term modes); weights from prep_mlp_weights
-template <class P> hipError_t op_mlp_fused(const Geom&, const BlockW<typename P::T>&, int res, typename P::T* Xs, const Work<P>&, hipStream_t);
+// fc1 / fc2 in the fragment order of the block kernels (fused_mlp.hip)
 template <class T> hipError_t prep_mlp_weights(const float* w1, const float* w2, T* w1f, T* w2f, int C, hipStream_t, int planes = 2);
-// row-tile forms of proj (+ LayerNorm + window reverse + residual) and of the 2-term QKV linear (rowtile.hip)
-template <class P> hipError_t op_proj_rowtile(const Geom&, const BlockW<typename P::T>&, const int* widx, int res, typename P::T* Xs, const Work<P>&, hipStream_t);
+// row-tile form of the 2-term QKV linear (rowtile.hip)
 hipError_t op_qkv_rowtile(const Geom&, const BlockW<f16>&, const int* widx, int res, const f16* Xs, const Work<PrecF16x3>&, hipStream_t);
 template <class T> hipError_t prep_rowtile_weights(const float* w, T* wf, int N, int K, hipStream_t, int planes = 2);
 // the 2-term / 1-term QKV linear and the window attention as ONE kernel: q / k / v stay in registers (attention.hip); out_planes as AttnArgs'
@@ -110,8 +105,7 @@ template <class T> hipError_t merge_planes(const T* planes, long long plane, flo
 // prepare-time helpers (aux.hip)
 template <class T, int NW>
 hipError_t prep_weight(const float* src, T* dst, long long plane, int N, int K, int ldd, long long sn, long long sk, int blocked, int perm, hipStream_t);
-hipError_t prep_bias_expand(const float* table, f16* out, int types, int heads, int nH, int roll, float mask_value, hipStream_t, int transposed = 0);   // roll: 0 | -1 | +1
-hipError_t prep_bias_compact(const float* table, f16* out, int types, int heads, int nH, int roll, float mask_value, hipStream_t, int transposed = 0);
+hipError_t prep_bias_compact(const float* table, f16* out, int types, int heads, int nH, int roll, float mask_value, hipStream_t, int transposed = 0);   // roll: 0 | -1 | +1
 hipError_t prep_qkv_rows(const float* w, const float* b, float* w_out, float* b_out, int C, int heads, hipStream_t);   // (heads, 3, hd) -> (3, heads, hd) rows
 hipError_t prep_window_index(int* idx, int Z, int H, int W, int Hp, int top, int roll, hipStream_t, int surface_last = 0);
 hipError_t prep_window_inverse(const int* idx, int n, int* inv, hipStream_t);

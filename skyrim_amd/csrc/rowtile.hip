@@ -1,12 +1,9 @@
-// Attention-side linears of an EarthSpecificBlock in the row-tile form of fused_mlp.hip: the token rows of a wavefront live in
-// REGISTERS as MFMA operand fragments for the whole kernel (loaded once, 16 bytes per lane), LDS holds only weights, streamed by
-// LDS-DMA in FRAGMENT order (one KiB = what one ds_read_b128 wave instruction consumes, lane-linear, no swizzle) in blocks of 32
+// The QKV linear of an EarthSpecificBlock in the row-tile form of the block kernels (fused_block.hip): the token rows of a wavefront
+// live in REGISTERS as MFMA operand fragments for the whole kernel (loaded once, 16 bytes per lane), LDS holds only weights, streamed
+// by LDS-DMA in FRAGMENT order (one KiB = what one ds_read_b128 wave instruction consumes, lane-linear, no swizzle) in blocks of 32
 // output columns, double-buffered, one barrier per block.  Against the tiled GEMMs of gemm_dma.h this halves the bytes that cross
-// LDS (no activation tile) and makes the epilogues wave-local:
+// LDS (no activation tile) and makes the epilogue wave-local:
 //
-//   rt_proj_kernel   x[dest(m)] += LayerNorm(norm1)( ao[m] Wp^T + b ),  m over window-ordered rows, dest = window table (reverse +
-//                    un-roll + crop; -1 = padding).  3 MFMA terms.  A row's C outputs stay in the wave's accumulators until the end
-//                    -> LayerNorm = in-lane sums + two shuffles (no LDS, no barrier); residual rows gathered, 16-byte loads / stores.
 //   rt_qkv_kernel    Q (scaled), K -> [win][head][144][32], V -> [win][head][32][144] fp16 from the stream's hi plane (2 MFMA terms:
 //                    Q / K / V tolerate an 11-bit A operand).  Rows are gathered through the window table (pad + roll +
 //                    partition).  grid.y = 3 selects Q, K or V: one output head (32 columns) per weight block, stored at once.
@@ -25,157 +22,6 @@ __device__ __forceinline__ void rt_ld_pair(const char* p, uint4 (&w)[2]) {
     w[0] = *reinterpret_cast<const uint4*>(p);
     w[1] = *reinterpret_cast<const uint4*>(p + 1024);
     __builtin_amdgcn_sched_barrier(0);          // keep the reads HERE, ahead of the MFMAs that follow (see fused_mlp.hip)
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------- //
-//  proj + LayerNorm + window reverse + residual
-// ------------------------------------------------------------------------------------------------------------------------------- //
-template <int C_, int FM_, int NWAVES_, int WPE_>
-struct ProjShape {
-    static constexpr int C = C_, FM = FM_, NWAVES = NWAVES_, THREADS = 64 * NWAVES_, WPE = WPE_;
-    static constexpr int KS = C / 32, CF = C / 16, NCH = C / 32, BM = NWAVES * FM * 16;
-    static constexpr int W_BLK = KS * 2 * 2;          // KiB per block of 32 output columns: [ks][n][plane]
-    static constexpr int STAGE = W_BLK * 1024;
-    static constexpr int SMEM = 2 * STAGE + 3 * C * 4;
-    static_assert(W_BLK % NWAVES == 0, "DMA blocks per wave");
-};
-
-template <class T>
-struct ProjArgs {
-    const T* ao; long long ao_plane;       // attention output, window-ordered rows, blocked layout [M/16][C/32][16][32]
-    int M;                                 // window rows (multiple of 144)
-    T* xs; long long xs_plane;             // residual stream planes
-    const int* widx;                       // row -> stream token, -1 = padding
-    const T* wf;                           // proj weights in fragment order (prep_rowtile_weights)
-    const float *bias, *gamma, *beta;
-    float eps;
-};
-
-template <class T, class S>
-__global__ void __launch_bounds__(S::THREADS) __attribute__((amdgpu_waves_per_eu(S::WPE, S::WPE)))
-rt_proj_kernel(const ProjArgs<T> a) {
-    constexpr int C = S::C, FM = S::FM, KS = S::KS, CF = S::CF, NCH = S::NCH, NWAVES = S::NWAVES, DEPTH = 3, NS = KS * 2;
-    typedef typename OpT<T>::v8 v8;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* tab = reinterpret_cast<float*>(smem + 2 * S::STAGE);
-    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned lds_base = (unsigned)(size_t)smem;
-    auto issue = [&](int j) {
-        const T* src = a.wf + ((long long)j * S::W_BLK << 9) + lane * 8;
-        const unsigned dst = lds_base + (unsigned)((j & 1) * S::STAGE);
-#pragma unroll
-        for (int i = 0; i < S::W_BLK / NWAVES; ++i) {
-            const int b = wave + i * NWAVES;
-            glds16(src + (b << 9), dst + (unsigned)(b << 10));
-        }
-    };
-    issue(0);
-    for (int i = tid; i < C; i += S::THREADS) { tab[i] = a.bias[i]; tab[C + i] = a.gamma[i]; tab[2 * C + i] = a.beta[i]; }
-
-    const long long rb0 = (long long)blockIdx.x * (S::BM / 16) + wave * FM;
-    v8 xh[FM][KS], xl[FM][KS];
-    bool live[FM];
-#pragma unroll
-    for (int t = 0; t < FM; ++t) {
-        live[t] = (rb0 + t) * 16 < a.M;
-        const T* p = a.ao + ((live[t] ? rb0 + t : 0) * KS << 9) + l15 * 32 + g * 8;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            xh[t][ks] = *reinterpret_cast<const v8*>(p + (ks << 9));
-            xl[t][ks] = *reinterpret_cast<const v8*>(p + (ks << 9) + a.ao_plane);
-        }
-    }
-    // destination rows of the epilogue (window reverse + un-roll + crop): fetched now, their latency hides under the main loop
-    int dest[FM];
-#pragma unroll
-    for (int t = 0; t < FM; ++t) dest[t] = live[t] ? a.widx[(rb0 + t) * 16 + l15] : -1;
-#pragma unroll
-    for (int t = 0; t < FM; ++t) {
-        asm volatile("" : "+v"(dest[t]));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { asm volatile("" : "+v"(xh[t][ks])); asm volatile("" : "+v"(xl[t][ks])); }
-    }
-
-    f32x4 yacc[FM][CF];
-#pragma unroll
-    for (int t = 0; t < FM; ++t)
-#pragma unroll
-        for (int c = 0; c < CF; ++c) yacc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                               // block j landed; every wave is done with block j - 1
-        if (j + 1 < NCH) issue(j + 1);
-        const char* st = smem + (j & 1) * S::STAGE;
-        uint4 ring[DEPTH][2];
-#pragma unroll
-        for (int s = 0; s < DEPTH - 1 && s < NS; ++s) rt_ld_pair(st + ((s * 2) << 10) + lane * 16, ring[s % DEPTH]);
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            if (s + DEPTH - 1 < NS) rt_ld_pair(st + (((s + DEPTH - 1) * 2) << 10) + lane * 16, ring[(s + DEPTH - 1) % DEPTH]);
-            const int ks = s >> 1, c = 2 * j + (s & 1);
-            const uint4 wh = ring[s % DEPTH][0], wl = ring[s % DEPTH][1];
-#pragma unroll
-            for (int t = 0; t < FM; ++t) yacc[t][c] = OpT<T>::mfma(as_v8<T>(wl), xh[t][ks], yacc[t][c]);
-#pragma unroll
-            for (int t = 0; t < FM; ++t) yacc[t][c] = OpT<T>::mfma(as_v8<T>(wh), xl[t][ks], yacc[t][c]);
-#pragma unroll
-            for (int t = 0; t < FM; ++t) yacc[t][c] = OpT<T>::mfma(as_v8<T>(wh), xh[t][ks], yacc[t][c]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-
-    const float* tg = tab + C;
-    const float* tbe = tab + 2 * C;
-#pragma unroll
-    for (int t = 0; t < FM; ++t) {
-        // residual rows first (gathered 16-byte loads; the input fragments are dead, their registers take the old values)
-        const bool ok = dest[t] >= 0;
-        const T* old = a.xs + blk_off(ok ? dest[t] : 0, g * 8, C);
-        v8 oh[KS], ol[KS];
-#pragma unroll
-        for (int bp = 0; bp < KS; ++bp) {
-            oh[bp] = *reinterpret_cast<const v8*>(old + (bp << 9));
-            ol[bp] = *reinterpret_cast<const v8*>(old + (bp << 9) + a.xs_plane);
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int bp = 0; bp < KS; ++bp) {
-            const int n = 32 * bp + 8 * g;
-            const float4 b0 = *reinterpret_cast<const float4*>(tab + n), b1 = *reinterpret_cast<const float4*>(tab + n + 4);
-            add8(yacc[t][2 * bp], yacc[t][2 * bp + 1], b0, b1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s += yacc[t][2 * bp][r] + yacc[t][2 * bp + 1][r];
-        }
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
-        const float mean = s * (1.0f / C);
-        float q = 0.f;
-#pragma unroll
-        for (int c = 0; c < CF; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const float d = yacc[t][c][r] - mean; q += d * d; }
-        q += __shfl_xor(q, 16);
-        q += __shfl_xor(q, 32);
-        const float rstd = rsqrtf(q * (1.0f / C) + a.eps);
-        if (!ok) continue;
-        T* dst = a.xs + blk_off(dest[t], g * 8, C);
-#pragma unroll
-        for (int bp = 0; bp < KS; ++bp) {
-            const int n = 32 * bp + 8 * g;
-            const float4 g0 = *reinterpret_cast<const float4*>(tg + n), g1 = *reinterpret_cast<const float4*>(tg + n + 4);
-            const float4 e0 = *reinterpret_cast<const float4*>(tbe + n), e1 = *reinterpret_cast<const float4*>(tbe + n + 4);
-            const f32x4 &x = yacc[t][2 * bp], &z = yacc[t][2 * bp + 1];
-            const float y[8] = {(x[0] - mean) * rstd * g0.x + e0.x, (x[1] - mean) * rstd * g0.y + e0.y, (x[2] - mean) * rstd * g0.z + e0.z, (x[3] - mean) * rstd * g0.w + e0.w,
-                                (z[0] - mean) * rstd * g1.x + e1.x, (z[1] - mean) * rstd * g1.y + e1.y, (z[2] - mean) * rstd * g1.z + e1.z, (z[3] - mean) * rstd * g1.w + e1.w};
-            float v[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v[i] = ((float)oh[bp][i] + (float)ol[bp][i]) + y[i];
-            store8_planes<T, 2>(dst + (bp << 9), a.xs_plane, v);
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------- //
@@ -367,29 +213,6 @@ hipError_t prep_rowtile_weights(const float* w, T* wf, int N, int K, hipStream_t
 }
 template hipError_t prep_rowtile_weights<bf16>(const float*, bf16*, int, int, hipStream_t, int);
 template hipError_t prep_rowtile_weights<f16>(const float*, f16*, int, int, hipStream_t, int);
-
-template <class T, class S>
-static hipError_t launch_proj(const ProjArgs<T>& a, hipStream_t s) {
-    auto kern = rt_proj_kernel<T, S>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S::SMEM);
-    if (e != hipSuccess) return e;
-    const unsigned grid = (unsigned)((a.M + S::BM - 1) / S::BM);
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(S::THREADS), S::SMEM, s, a);
-    return hipGetLastError();
-}
-
-template <class P>
-hipError_t op_proj_rowtile(const Geom& g, const BlockW<typename P::T>& b, const int* widx, int res, typename P::T* Xs, const Work<P>& wk, hipStream_t s) {
-    typedef typename P::T T;
-    static_assert(P::NA == 2 && P::NW == 2, "3-term path");
-    ProjArgs<T> a{wk.ao, wk.ao_plane, g.mwin[res], Xs, wk.xs_plane[res], widx, b.projf, b.proj_b, b.n1_g, b.n1_b, 1e-5f};
-    // C = 192: two 4-wave workgroups per CU, 32 rows per wave;  C = 384: one 8-wave workgroup, 16 rows per wave (fused_mlp.hip's findings)
-    if (res == 0) return launch_proj<T, ProjShape<192, 2, 4, 2>>(a, s);
-    return launch_proj<T, ProjShape<384, 1, 8, 2>>(a, s);
-}
-template hipError_t op_proj_rowtile<PrecBF16x3>(const Geom&, const BlockW<bf16>&, const int*, int, bf16*, const Work<PrecBF16x3>&, hipStream_t);
-template hipError_t op_proj_rowtile<PrecF16x3>(const Geom&, const BlockW<f16>&, const int*, int, f16*, const Work<PrecF16x3>&, hipStream_t);
 
 template <class S>
 static hipError_t launch_qkv(const QkvArgs& a, hipStream_t s) {

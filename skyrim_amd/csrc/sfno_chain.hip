@@ -17,8 +17,6 @@
 // 32 bp + 8 (lane >> 4) + [0..7]: exactly an input fragment of the NEXT pair, so TAIL chains two pairs without leaving registers.
 // Activations are [C][HW] fp32 (pixels contiguous): a fragment is fetched with 8 dword loads per lane (16 consecutive pixels
 // of 4 x 8 channels per instruction) and stored the same way.  HW must be a multiple of 16.  gfx950 only.
-#include <cstdlib>
-
 #include "gemm_dma.h"
 #include "../../include/skyrim_sfno.h"
 
@@ -385,18 +383,13 @@ hipError_t launch_chain(const ChainArgs& a, hipStream_t s) {
 // padded widths per shape class: {CP, HP, KXP, OP}
 constexpr int kShapes[2][4] = {{256, 512, 96, 96}, {64, 96, 32, 32}};
 
-// One 8-wave workgroup of 128 pixels per CU by default.  SKSFNO_CHAIN_WAVES=4: two independent 4-wave workgroups of 64 pixels per CU
-// (twice the weight traffic per pixel) -- measured equal at 721 x 1440 (18.54 vs 18.56 ms/step): the chunk loop, not the operand
-// loads / stores around it, sets the pace (with one chunk instead of all of them the three chains take 1.9 of their 4.9 ms).
+// One 8-wave workgroup of 128 pixels per CU.  Two independent 4-wave workgroups of 64 pixels per CU (twice the weight traffic per pixel)
+// measured equal at 721 x 1440 (18.54 vs 18.56 ms/step): the chunk loop, not the operand loads / stores around it, sets the pace (with one
+// chunk instead of all of them the three chains take 1.9 of their 4.9 ms).
 template <int MODE>
 hipError_t launch_mode(int shape, const ChainArgs& a, hipStream_t s) {
-    static const int waves = [] { const char* v = getenv("SKSFNO_CHAIN_WAVES"); return v ? atoi(v) : 8; }();
-    if (shape == 0) {
-        if (waves == 8) return launch_chain<ChainShape<MODE, kShapes[0][0], kShapes[0][1], kShapes[0][2], kShapes[0][3], 1, 8>>(a, s);
-        return launch_chain<ChainShape<MODE, kShapes[0][0], kShapes[0][1], kShapes[0][2], kShapes[0][3], 1, 4, 2>>(a, s);
-    }
-    if (waves == 8) return launch_chain<ChainShape<MODE, kShapes[1][0], kShapes[1][1], kShapes[1][2], kShapes[1][3], 1, 8>>(a, s);
-    return launch_chain<ChainShape<MODE, kShapes[1][0], kShapes[1][1], kShapes[1][2], kShapes[1][3], 1, 4, 2>>(a, s);
+    if (shape == 0) return launch_chain<ChainShape<MODE, kShapes[0][0], kShapes[0][1], kShapes[0][2], kShapes[0][3], 1, 8>>(a, s);
+    return launch_chain<ChainShape<MODE, kShapes[1][0], kShapes[1][1], kShapes[1][2], kShapes[1][3], 1, 8>>(a, s);
 }
 
 }  // namespace skp

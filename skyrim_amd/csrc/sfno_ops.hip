@@ -11,8 +11,6 @@
 // loader issues scalar loads when k is not the contiguous index; layout-specialised loaders are the next step.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../../include/skyrim_sfno.h"
 #include "strided_gemm.h"
 
@@ -23,7 +21,7 @@ namespace skp {
 // Two tiles.  TG (128 x 256, strided_gemm.h): 64 x 64 wave tiles, 162-177 VGPRs, ONE 8-wave workgroup per CU.  TS (128 x 128): 64 x 32 wave
 // tiles fit 128 VGPRs, so TWO 8-wave workgroups (16 waves) share a CU and one's loads / stores run under the other's MFMAs -- measured
 // a little faster for the DFTs (-9 %), the synthesis (-9 %) and dhconv (-5 %), slower for the Legendre analysis (N = 240 fits one 256-wide
-// tile: +15 %), which therefore keeps TG; 17.8 -> 17.6 ms/step in all (SKSFNO_TILE=256 / 128 force one tile).
+// tile: +15 %), which therefore keeps TG; 17.8 -> 17.6 ms/step in all.
 typedef TileCfg<128, 128, 32, 2, 4> TS;
 
 template <class PX, class AL, bool SWAP, class TC>
@@ -48,9 +46,9 @@ __device__ __forceinline__ void gemm_strided_body(GemmArgs<PX, AL, EpStrided>& g
     // (GraphCast's node-term GEMM, N = 1024 = 8 column tiles: 1.44 GB fetched per launch for an 84 MB operand).  Re-mapped, the workgroups
     // of one XCD (same launch index mod 8) walk a contiguous range of tiles, column tile fastest: a row tile's columns run side by side on one
     // L2.  The map is a bijection for any tile count (the first T mod 8 XCDs take one tile more).
-    int tx = blockIdx.x, ty = blockIdx.y;
-    if (bs.xcd_remap) {
-        const int gx = gridDim.x, T = gx * (int)gridDim.y, l = tx + gx * ty;
+    int tx, ty;
+    {
+        const int gx = gridDim.x, T = gx * (int)gridDim.y, l = (int)blockIdx.x + gx * (int)blockIdx.y;
         const int q = T >> 3, r = T & 7, x = l & 7, slot = l >> 3;
         const int v = x < r ? x * (q + 1) + slot : r * (q + 1) + (x - r) * q + slot;
         ty = v / gx;
@@ -144,12 +142,10 @@ int sksfno_gemm_run(const sksfno_gemm* d, void* stream) {
         return SKSFNO_E_ARG;
     const ALStrided al{d->a, d->M, d->K, d->a_m1, d->a_sm, d->a_sm2, d->a_sk, d->a_kscale, d->a_kshift, d->a2, d->a2_sk, d->a2_k_split};
     const EpStrided ep{d->out, d->bias, d->res_pre, d->res_post, d->o_m1, d->act, d->o_sm, d->o_sm2, d->o_sn};
-    static const bool no_remap = getenv("SKSFNO_NO_XCD_REMAP") != nullptr;                                     // A/B switch (tools/r4_remap.sh)
-    const BatchStrides bs{d->a_sb, d->w_sb, d->o_sb, d->k_lo_step, d->m_cap0, d->m_cap_step, no_remap ? 0 : 1};
+    const BatchStrides bs{d->a_sb, d->w_sb, d->o_sb, d->k_lo_step, d->m_cap0, d->m_cap_step};
     // rows contiguous in the output (NCHW activations): un-swapped order gives 4 consecutive rows per lane
     const bool swap = !(d->o_sm == 1 && d->o_sn != 1);
-    static const int tile_env = [] { const char* v = getenv("SKSFNO_TILE"); return v ? atoi(v) : 0; }();      // 128 / 256: force one tile
-    const bool wide = tile_env == 256 || (tile_env != 128 && !swap && d->N > 128 && d->N <= 256);            // one 256-wide tile covers N
+    const bool wide = !swap && d->N > 128 && d->N <= 256;            // one 256-wide tile covers N
     const int bn = wide ? TG::BN : TS::BN;
     const dim3 grid((d->N + bn - 1) / bn, (d->M + TG::BM - 1) / TG::BM, d->batch);
     static_assert(TG::BM == TS::BM && TG::THREADS == TS::THREADS, "the two tiles share the row split and the block size");
@@ -180,8 +176,7 @@ int sksfno_gemm_run(const sksfno_gemm* d, void* stream) {
     };
     // the loader without per-element predicates wherever the operand allows it (strided_gemm.h: ALFast)
     const long long a_extent = (long long)((d->M - 1) / d->a_m1) * d->a_sm2 + (long long)(d->a_m1 < d->M ? d->a_m1 - 1 : d->M - 1) * d->a_sm + (long long)(d->K - 1) * d->a_sk;
-    static const bool no_fast = getenv("SKSFNO_NO_FAST_LOADER") != nullptr;
-    const bool fast = !no_fast && d->terms != 2 && !d->a_kscale && !d->a2 && (d->K & 7) == 0 && d->a_sm >= 0 && d->a_sm2 >= 0 && d->a_sk > 0 && a_extent < (1ll << 30);
+    const bool fast = d->terms != 2 && !d->a_kscale && !d->a2 && (d->K & 7) == 0 && d->a_sm >= 0 && d->a_sm2 >= 0 && d->a_sk > 0 && a_extent < (1ll << 30);
     const bool vec = fast && d->a_sk == 1 && (reinterpret_cast<size_t>(d->a) & 15) == 0 && !(d->a_sm & 3) && !(d->a_sm2 & 3) && !(d->a_sb & 3);
     if (vec)       launch(PrecF16x3{}, ALFast<true>{d->a, d->M, d->K, d->a_m1, d->a_sm, d->a_sm2, d->a_sk});
     else if (fast) launch(PrecF16x3{}, ALFast<false>{d->a, d->M, d->K, d->a_m1, d->a_sm, d->a_sm2, d->a_sk});

@@ -219,6 +219,6 @@ struct EpStrided {
 
 typedef TileCfg<128, 256, 32, 2, 4> TG;      // wide N: the fp32 A operand is fetched and split once per 256 output columns
 
-struct BatchStrides { long long a, w, o; int k_lo_step, m_cap0, m_cap_step, xcd_remap; };
+struct BatchStrides { long long a, w, o; int k_lo_step, m_cap0, m_cap_step; };
 
 }  // namespace skp

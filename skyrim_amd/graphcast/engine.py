@@ -116,7 +116,7 @@ class GraphcastEngine:
         # SKGC_EXERCISE_COLLECTIVES=1: run the two exchanges of the sharded step even with ONE rank (the collectives then copy a rank's data onto
         # itself): the cheapest proof that the default torch.distributed / RCCL branch loads and runs on a 1-GPU box (tests/test_rccl_gpu.py)
         self.exercise = bool(os.environ.get("SKGC_EXERCISE_COLLECTIVES")) and self.world == 1
-        self.shard_mesh = (self.world > 1 or self.exercise) and not os.environ.get("SKGC_REPLICATED_MESH")
+        self.shard_mesh = self.world > 1 or self.exercise
         if not torch.cuda.is_available():
             raise RuntimeError("GraphcastEngine needs an MI355X: the GraphCast path has no CPU fallback")
         if self.cfg.latent % 8 != 0:
@@ -127,27 +127,24 @@ class GraphcastEngine:
         full = graph or build_graph(self.cfg.n_lat, self.cfg.n_lon, self.cfg.splits)
         # The multi-mesh numbers its nodes level by level; the engine works on a spatially coherent numbering (Morton order of the node
         # positions) so that the sender rows gathered for neighbouring receivers -- neighbouring tiles of the receiver-sorted edge list -- are
-        # neighbours in memory too.  Mesh nodes never leave the engine: invisible outside (SKGC_MESH_ORDER=level keeps the caller's numbering).
-        if os.environ.get("SKGC_MESH_ORDER", "spatial") != "level":
-            full = renumber_mesh(full, spatial_order(full.mesh_pos))
+        # neighbours in memory too.  Mesh nodes never leave the engine: invisible outside.
+        full = renumber_mesh(full, spatial_order(full.mesh_pos))
         self.lat0, self.lat1 = latitude_band(self.cfg.n_lat, self.rank, self.world)
         self.graph = full if self.world == 1 else shard_graph(full, self.cfg.n_lat, self.cfg.n_lon, self.rank, self.world)
         self.prepared = False
         self.profiling = False
         self._events = []
-        self.fused_ln = self.cfg.latent == 512 and not os.environ.get("SKGC_UNFUSED_LN")
+        self.fused_ln = self.cfg.latent == 512
         # edge MLPs by distributivity (fc1 of concat(e, v_s[send], v_r[recv]) = e W_e^T + (v_s W_s^T)[send] + (v_r W_r^T)[recv]): the node
         # terms once per node, the edge term once per layer (once per model for the encoder / decoder, whose edge latents are
         # input-independent); needs the fused Linear + LayerNorm kernel (latent 512)
-        self.split_edges = self.fused_ln and not os.environ.get("SKGC_CONCAT_EDGES")
+        self.split_edges = self.fused_ln
         # round 4: every interaction-network update as ONE kernel (csrc/graphcast_fused.hip): edge update + receiver sum on packed rows with
         # one-plane fp16 edge operands, node updates on fp32 rows with three MFMA terms.  SKGC_UNFUSED=1 keeps the round-3 kernel sequence.
         self.fused = self.split_edges and not os.environ.get("SKGC_UNFUSED")
         # planes of the processor edge MLPs' first Linear (edge part): 1 = W_e as one fp16 plane (one MFMA term: +1.4e-4 of the predicted
-        # increment at production width and depth, tools/graphcast_numerics.py), 2 = hi/lo planes (two terms)
-        self.w1_planes = int(os.environ.get("SKGC_W1_PLANES", "1"))
-        if self.w1_planes not in (1, 2):
-            raise ValueError("SKGC_W1_PLANES is 1 or 2")
+        # increment at production width and depth, tools/graphcast_numerics.py); the edge kernel also takes 2 = hi/lo planes (two terms)
+        self.w1_planes = 1
         self.state_shape = (self.cfg.n_vars, self.lat1 - self.lat0, self.cfg.n_lon)
 
     def release(self):

@@ -190,7 +190,7 @@ class PanguEngine:
                  roll_sign: int = -1, mask_value: float = -100.0, mlp: str = "fused", term_plan: int | None = None,
                  surface: str = "first", qkv_order: str = "3hd", bias_index: str = "qk"):
         """``roll_sign`` / ``mask_value`` / ``geom.pad``: the conventions the public pseudocode leaves open.
-        ``mlp``: "fused" (default; one kernel per MLP in the 3-term modes, csrc/fused_mlp.hip) or "split" (two tiled GEMMs).
+        ``mlp``: "fused" (default; proj + MLP as one kernel per block in the 3-term modes, csrc/fused_block.hip) or "split" (tiled GEMMs).
         ``term_plan``: per-layer two-term mask (include/skyrim_pangu.h); None = the precision name's own.
         ``surface`` / ``qkv_order`` / ``bias_index``: three more open conventions (oracle: Conventions of the same names), prepare-time only."""
         self.lib = load_library()

@@ -152,19 +152,14 @@ class SfnoEngine:
         """``terms``: MFMA terms per GEMM -- 3: activations and constants as fp16 hi/lo pairs (fp32-class, ~1e-6 vs the oracle);
         2: activations rounded to one fp16 plane (faster; error measured in tests/test_sfno_gpu.py).
         ``fused``: encoder, block MLPs (+ norm1) and decoder as one pixel-wise chain kernel each (sfno_chain.hip) instead of GEMM by
-        GEMM; default on (``SKYRIM_SFNO_UNFUSED=1`` switches it off) wherever the widths fit a compiled shape class and the pixel count
-        of the grid is a multiple of 16 -- otherwise that stage runs GEMM by GEMM."""
+        GEMM; default on wherever the widths fit a compiled shape class and the pixel count of the grid is a multiple of 16 -- otherwise
+        that stage runs GEMM by GEMM."""
         self.cfg = cfg or SfnoConfig()
         if terms not in (2, 3):
             raise ValueError("terms must be 2 or 3")
         self.terms = terms
-        self.fused = (os.environ.get("SKYRIM_SFNO_UNFUSED", "0") != "1") if fused is None else bool(fused)
+        self.fused = True if fused is None else bool(fused)
         self.chain = None                 # shape class of the fused chains, set by load_params
-        # layout of the longitude spectrum between the DFT and Legendre GEMMs: "order" = [order, re/im][C][lat], "channel" = [C][order, re/im][lat]
-        # grid-changing blocks: the inner skip as a channel mix of the SH coefficients instead of a 1x1 convolution on the output grid
-        self.skip_in_spectrum = os.environ.get("SKYRIM_SFNO_GRID_SKIP", "0") != "1"
-        self.f_ana = os.environ.get("SKSFNO_F_ANA", "order")
-        self.f_syn = os.environ.get("SKSFNO_F_SYN", "order")
         if not torch.cuda.is_available():
             raise RuntimeError("SfnoEngine needs an MI355X: the SFNO path has no CPU fallback")
         self.lib = load_library()
@@ -184,7 +179,7 @@ class SfnoEngine:
     def release(self):
         """Drop every prepared matrix, table and work buffer (GlobalModel.release_model).  The C ABI holds no state of its own -- all device
         memory is torch tensors owned here -- so this IS the teardown; the engine is unusable until ``load_params`` runs again."""
-        keep = ("cfg", "terms", "fused", "skip_in_spectrum", "f_ana", "f_syn", "lib", "device", "state_shape", "_label", "profiling")
+        keep = ("cfg", "terms", "fused", "lib", "device", "state_shape", "_label", "profiling")
         kept = {k: v for k, v in vars(self).items() if k in keep}
         self.__dict__.clear()
         self.__dict__.update(kept)
@@ -221,7 +216,7 @@ class SfnoEngine:
                 mix[:, :e, e:] = -wi
                 mix[:, e:, :e] = wi
                 mix[:, e:, e:] = wr
-                if self.skip_in_spectrum and i in (0, c.num_layers - 1):
+                if i in (0, c.num_layers - 1):
                     # grid-changing block: the inner skip is a channel mix of the coefficients (see step()) -- the same matrix for every
                     # degree and for the real and the imaginary part, i.e. one more term on the diagonal blocks of the dhconv matrices
                     ws = g("inner_skip.weight").float()
@@ -367,12 +362,6 @@ class SfnoEngine:
         # truncated DFT, one batch per channel: rows = latitudes, k = longitude -> spectrum [order, re/im][C][ldl] (order-major, so
         # that the Legendre GEMM of one order reads k = latitude contiguously)
         self._label = "dft"
-        if self.f_ana == "channel":        # spectrum [C][order, re/im][ldl]: the DFT of a channel writes one dense region
-            self._gemm(x, tr["dft"], self.b_f, H, Wd, 2 * Mm, batch=C, a_sb=H * Wd, a_sm=Wd, a_sk=1, o_sb=2 * Mm * ldl, o_sm=1, o_sn=ldl, w_batched=False)
-            self._label = "legendre_analysis"
-            self._gemm(self.b_f, tr["ana"], self.b_coef, 2 * C, H, L, batch=Mm, a_sb=2 * ldl, a_m1=C, a_sm=2 * Mm * ldl, a_sm2=ldl, a_sk=1,
-                       o_sb=2 * C, o_sm=1, o_sn=Mm * 2 * C)
-            return
         self._gemm(x, tr["dft"], self.b_f, H, Wd, 2 * Mm, batch=C, a_sb=H * Wd, a_sm=Wd, a_sk=1, o_sb=ldl, o_sm=1, o_sn=C * ldl, w_batched=False)
         # per order m: rows (re/im, channel), k = latitude
         self._label = "legendre_analysis"
@@ -385,12 +374,6 @@ class SfnoEngine:
         H, Wd, Mm, L, ldl = tr["n_lat"], tr["n_lon"], c.mmax, c.lmax, self.ldl
         self._label = "legendre_synthesis"
         # order m only has degrees l >= m: the contraction over l starts at (the 32-aligned floor of) m
-        if self.f_syn == "channel":        # spectrum [C][order, re/im][ldl]: the inverse DFT of a channel reads one dense region
-            self._gemm(coef, tr["syn"], self.b_f, 2 * C, L, H, batch=Mm, a_sb=2 * C, a_sm=1, a_sk=Mm * 2 * C,
-                       o_sb=2 * ldl, o_m1=C, o_sm=2 * Mm * ldl, o_sm2=ldl, o_sn=1, k_lo_step=1)
-            self._label = "idft"
-            self._gemm(self.b_f, tr["idft"], out, H, 2 * Mm, Wd, batch=C, a_sb=2 * Mm * ldl, a_sm=1, a_sk=ldl, o_sb=H * Wd, o_sm=Wd, o_sn=1, w_batched=False, **kw)
-            return
         self._gemm(coef, tr["syn"], self.b_f, 2 * C, L, H, batch=Mm, a_sb=2 * C, a_sm=1, a_sk=Mm * 2 * C,
                    o_sb=2 * C * ldl, o_sm=ldl, o_sn=1, k_lo_step=1)
         self._label = "idft"
@@ -435,7 +418,7 @@ class SfnoEngine:
                 self._gemm(self.b_coef, blk["mix"], self.b_mixed, c.mmax, 2 * e, 2 * e, batch=c.lmax, a_sb=c.mmax * 2 * e, a_sm=2 * e, a_sk=1,
                            o_sb=c.mmax * 2 * e, o_sm=2 * e, o_sn=1, m_cap0=1, m_cap_step=1)      # degree l has orders m <= l only
                 outer = "_outer" if tout is self.tr["outer"] else ""
-                if tin is not tout and self.skip_in_spectrum:
+                if tin is not tout:
                     # the residual of a grid-changing block is iSHT(coef): band-limited, so the 1x1 inner skip commutes with the synthesis --
                     # skip(iSHT(coef)) = iSHT(W_skip coef), a channel mix of the COEFFICIENTS with the same matrix for every degree: it is
                     # part of this block's dhconv matrices (load_params).  What is left: the bias on the (l, m) = (0, 0) coefficient (a

@@ -490,9 +490,10 @@ def test_switchable_conventions_match_the_oracle(toy, conv):
 
 
 def test_fused_mlp_kernel_matches_the_two_gemm_path_and_the_oracle(toy, ref):
-    """csrc/fused_mlp.hip (fc1 -> GELU -> fc2 -> LayerNorm -> residual in one kernel, token tile and hidden in registers) against
-    the two tiled GEMMs of round 1 and against the oracle: one block at each resolution (C = 192: 64 tokens per wave, C = 384:
-    32) and the whole step; the toy grid's token counts (4992, 1344) are not multiples of the 256 / 128-token tiles."""
+    """mlp="fused": csrc/fused_block.hip (proj -> LayerNorm -> residual -> fc1 -> GELU -> fc2 -> LayerNorm -> residual in one kernel,
+    token tile and hidden in registers, the MLP scheme of csrc/fused_mlp.hip) against mlp="split" (the tiled GEMMs of round 1) and
+    against the oracle: one block at each resolution (C = 192: 32 tokens per wave, C = 384: 16) and the whole step; the toy grid's
+    token counts (4992, 1344) are not multiples of the 256 / 128-token tiles."""
     from skyrim_amd.pangu.engine import PanguEngine
     g, params, x = toy
     taps, y_ref = ref

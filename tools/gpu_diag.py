@@ -114,19 +114,14 @@ def run(prec, g, params, x):
         yb = eng.block(layer, i, xin.to(dev))
         print(f" block layer{layer}.block{i}:")
         nq = ref["q"].numel()
-        # expanded bias check
+        # compact bias check (csrc/aux.hip, prep_bias_compact): per (type, head) row (z_q + 2 z_k) 36 + (h_q + 6 h_k), column w_k - w_q + 11
         blk = {(1, 0): 0, (1, 1): 1, (2, 0): 2, (2, 1): 3}[(layer, i)]
-        be = eng.debug_buffer(f"bias_exp{blk}", torch.float16).float().cpu()
         types, heads = ref["bias"].shape[:2]
         full = ref["bias"] + (ref["mask"][:, 0][:, None] if ref["mask"] is not None else 0)
-        be = be.reshape(types, heads, 9, 2304)
-        lane = torch.arange(64)
-        q_of = (torch.arange(9)[:, None] * 16 + (lane & 15)[None, :])                      # [qf][lane]
-        k_pair = 32 * torch.arange(4)[:, None, None] + 8 * (lane >> 4)[None, :, None] + torch.arange(8)[None, None, :]   # [kb][lane][8]
-        k_last = 128 + 4 * (lane >> 4)[:, None] + torch.arange(4)[None, :]                 # [lane][4]
-        exp_pair = full[:, :, q_of[:, None, :, None].expand(9, 4, 64, 8), k_pair[None].expand(9, 4, 64, 8)].reshape(types, heads, 9, 2048)
-        exp_last = full[:, :, q_of[:, :, None].expand(9, 64, 4), k_last[None].expand(9, 64, 4)].reshape(types, heads, 9, 256)
-        report("bias_exp", be, torch.cat([exp_pair, exp_last], dim=-1))
+        be = eng.debug_buffer(f"bias_exp{blk}", torch.float16).float().cpu().reshape(types, heads, 144, 24)
+        qi, ki = torch.meshgrid(torch.arange(144), torch.arange(144), indexing="ij")
+        row = (qi // 72 + 2 * (ki // 72)) * 36 + (qi // 12) % 6 + 6 * ((ki // 12) % 6)
+        report("bias_cmp", be[:, :, row, ki % 12 - qi % 12 + 11], full)
         for name in ("q", "k", "vt"):
             got = planes(eng.debug_buffer(name, torch.uint8), nq, 1, torch.float16)
             report(name, got, ref[name])
