@@ -102,8 +102,13 @@ def get_data_source(channel_names, initial_condition_source: str = "synthetic", 
 def get_initial_condition_for_model(model, data_source, time: datetime.datetime) -> torch.Tensor:
     """(B=1, n_history_levels, C, lat, lon) float32 on ``model.device`` -- earth2mip.initial_conditions'
     function of the same name as the reference calls it (utils.py:20)."""
+    grid = getattr(model, "grid", None)
+    n_lat = len(grid.lat) if grid is not None and hasattr(grid, "lat") else None
     arrs = []
     for k in range(model.n_history_levels - 1, -1, -1):
-        arrs.append(np.asarray(data_source[time - k * model.time_step], dtype=np.float32))
+        a = np.asarray(data_source[time - k * model.time_step], dtype=np.float32)
+        if n_lat == 720 and a.ndim >= 2 and a.shape[-2] == 721:
+            a = a[..., :720, :]          # 0.25-degree source, grid without the south-pole row (FourCastNet v1): earth2mip drops the last row
+        arrs.append(a)
     x = torch.from_numpy(np.stack(arrs))
     return x.to(model.device).unsqueeze(0)

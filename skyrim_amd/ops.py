@@ -10,6 +10,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     sfno_gemm / sfno_instance_norm / sfno_chain / sfno_instance_stats
     gc_gather_gemm / gc_linear_layer_norm / gc_sum_linear_layer_norm / gc_layer_norm / gc_segment_sum
     gc_edge_update / gc_segment_fixup / gc_node_mlp      (the fused interaction-network updates, csrc/graphcast_fused.hip)
+    fcn_layer_norm / fcn_mlp / fcn_spectral_mlp          (FourCastNet v1, include/skyrim_fcn.h)
 """
 from __future__ import annotations
 
@@ -310,6 +311,56 @@ def _gc_node_mlp(src, src_off, ld, w1f, w2f, b1, b2, gamma, beta, res, res_off: 
         _ok(lib.skgc_node_mlp(ctypes.byref(d), _stream(out)), "skgc_node_mlp")
 
 
+# ---- FourCastNet v1 ------------------------------------------------------------------------------------------------------------ #
+def _fcn():
+    from .fcn import engine
+    return engine.load_library()
+
+
+def _frag16(t, what: str, dev):
+    if t.dtype != torch.float16 or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what} must be the fp16 planes of skfcn_prepare_mlp_weights on the same device")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _fcn_layer_norm(x, gamma, beta, out, rows: int, C: int, eps: float) -> None:
+    lib = _fcn()
+    dev = x.device
+    if x.numel() < rows * C or out.numel() < rows * C:
+        raise ValueError("fcn_layer_norm: x / out smaller than rows x C")
+    with torch.cuda.device(dev):
+        _ok(lib.skfcn_layer_norm(_f32(x, "x"), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _f32(out, "out", dev), rows, C, eps, _stream(x)),
+            "skfcn_layer_norm", lib.skfcn_error_string)
+
+
+def _fcn_mlp(x, w1f, w2f, b1, b2, gamma, beta, out, rows: int, C: int, hidden: int, eps: float) -> None:
+    from .fcn import engine
+    lib = _fcn()
+    dev = x.device
+    if x.numel() < rows * C or out.numel() < rows * C or w1f.numel() != 2 * C * hidden or w2f.numel() != 2 * C * hidden:
+        raise ValueError("fcn_mlp: tensor sizes do not match rows, C and hidden")
+    d = engine.MlpDesc(_f32(x, "x").value, _f32(out, "out", dev).value, rows, C, hidden, _f32(gamma, "gamma", dev).value, _f32(beta, "beta", dev).value,
+                       eps, _frag16(w1f, "w1f", dev).value, _frag16(w2f, "w2f", dev).value, _f32(b1, "b1", dev).value, _f32(b2, "b2", dev).value)
+    with torch.cuda.device(dev):
+        _ok(lib.skfcn_mlp_run(ctypes.byref(d), _stream(x)), "skfcn_mlp_run", lib.skfcn_error_string)
+
+
+def _fcn_spectral_mlp(z, w1f, w2f, b1e, b2e, geom: list[int], lam: float) -> None:
+    from .fcn import engine
+    lib = _fcn()
+    dev = z.device
+    if len(geom) != 6:
+        raise ValueError("fcn_spectral_mlp: geom = [rows, m1, sm, sm2, im_off, nblocks]")
+    rows, m1, sm, sm2, im_off, nb = geom
+    last = ((rows - 1) // m1) * sm2 + ((rows - 1) % m1) * sm + im_off + engine.SPECTRAL_BLOCK * nb
+    if z.numel() < last or w1f.numel() != 2 * nb * 192 * 192 or w2f.numel() != 2 * nb * 192 * 192 or b1e.numel() != nb * 192 or b2e.numel() != nb * 192:
+        raise ValueError("fcn_spectral_mlp: tensor sizes do not match the geometry")
+    d = engine.SpectralMlpDesc(_f32(z, "z").value, rows, sm, sm2, im_off, m1, nb, _frag16(w1f, "w1f", dev).value, _frag16(w2f, "w2f", dev).value,
+                               _f32(b1e, "b1e", dev).value, _f32(b2e, "b2e", dev).value, lam)
+    with torch.cuda.device(dev):
+        _ok(lib.skfcn_spectral_mlp(ctypes.byref(d), _stream(z)), "skfcn_spectral_mlp", lib.skfcn_error_string)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -336,6 +387,10 @@ _SCHEMAS = [
     ("gc_segment_fixup(Tensor(a!) agg, Tensor heads, Tensor nodes, Tensor first, Tensor tiles) -> ()", _gc_segment_fixup),
     ("gc_node_mlp(Tensor[] src, int[] src_off, int[] ld, Tensor w1f, Tensor w2f, Tensor b1, Tensor b2, Tensor gamma, Tensor beta, Tensor? res, int res_off, "
      "int ld_res, Tensor(a!) out, int out_off, int ld_out, int rows) -> ()", _gc_node_mlp),
+    ("fcn_layer_norm(Tensor x, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int C, float eps) -> ()", _fcn_layer_norm),
+    ("fcn_mlp(Tensor x, Tensor w1f, Tensor w2f, Tensor b1, Tensor b2, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int C, int hidden, "
+     "float eps) -> ()", _fcn_mlp),
+    ("fcn_spectral_mlp(Tensor(a!) z, Tensor w1f, Tensor w2f, Tensor b1e, Tensor b2e, int[] geom, float lam) -> ()", _fcn_spectral_mlp),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
