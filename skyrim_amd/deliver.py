@@ -15,34 +15,27 @@ from __future__ import annotations
 
 import ctypes
 import os
-from pathlib import Path
 
 import numpy as np
 
-_LIB_PATH = Path(__file__).resolve().parent / "lib" / "libskyrim_io.so"
-ABI_VERSION = 1             # include/skyrim_io.h SKIO_ABI_VERSION
-EXPORTS = ["skio_abi_version", "skio_bswap32"]
+from . import native
+
+SPEC = native.Spec("skyrim_io", "SKYRIM_IO_LIB", "skio", 1, {               # include/skyrim_io.h SKIO_ABI_VERSION
+    "skio_abi_version": (ctypes.c_int, []),
+    "skio_bswap32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+}, " -- the big-endian delivery of a saving rollout has no host fallback (SKYRIM_SAVE_BE=0 turns it off)")
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+
 _lib = None
 
 
 def load_library() -> ctypes.CDLL:
-    """Load libskyrim_io.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
+    """libskyrim_io.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    path = os.environ.get("SKYRIM_IO_LIB", str(_LIB_PATH))
-    if not os.path.exists(path):
-        raise RuntimeError(f"HIP delivery library not found at {path}; build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-                           " -- the big-endian delivery of a saving rollout has no host fallback (SKYRIM_SAVE_BE=0 turns it off)")
-    lib = ctypes.CDLL(path)
-    lib.skio_abi_version.restype = ctypes.c_int
-    lib.skio_bswap32.restype = ctypes.c_int
-    lib.skio_bswap32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    got = lib.skio_abi_version()
-    if got != ABI_VERSION:
-        raise RuntimeError(f"{path} is ABI v{got}, this host code binds v{ABI_VERSION}: rebuild (`make -C skyrim_amd/csrc`)")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
 
 
 def bswap32(src, dst, stream) -> None:
@@ -52,9 +45,8 @@ def bswap32(src, dst, stream) -> None:
         raise ValueError("bswap32 wants contiguous device tensors")
     if src.element_size() != 4 or dst.element_size() != 4 or src.numel() != dst.numel():
         raise ValueError(f"bswap32: {tuple(src.shape)} {src.dtype} -> {tuple(dst.shape)} {dst.dtype}")
-    rc = load_library().skio_bswap32(src.data_ptr(), dst.data_ptr(), src.numel(), stream.cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"skio_bswap32 failed ({rc})")
+    lib = load_library()
+    native.check(lib.skio_bswap32(src.data_ptr(), dst.data_ptr(), src.numel(), stream.cuda_stream), "skio_bswap32", lib)
 
 
 class ImagePart:

@@ -14,19 +14,13 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
+from .. import native
 from .spec import FcnConfig, param_spec
 
-_LIB_PATH = Path(__file__).resolve().parent.parent / "lib" / "libskyrim_fcn.so"
-EXPORTS = ["skfcn_abi_version", "skfcn_error_string", "skfcn_prepare_weight", "skfcn_prepare_mlp_weights", "skfcn_patch_embed",
-           "skfcn_layer_norm", "skfcn_spectral_mlp", "skfcn_spectral_run", "skfcn_mlp_run", "skfcn_head_run"]
-ABI_VERSION = 1
-E_ARG, E_HIP = -1, -2
 SPECTRAL_BLOCK = 96            # block size the spectral MLP kernel is compiled for
 TOKEN_WIDTHS = (192, 768)      # embed widths the token MLP kernel is compiled for
 
@@ -63,42 +57,29 @@ class HeadDesc(ctypes.Structure):
                 ("cout", _I), ("himg", _I), ("wimg", _I), ("patch", _I), ("embed", _I)]
 
 
+SPEC = native.Spec("skyrim_fcn", "SKYRIM_FCN_LIB", "skfcn", 1, {             # include/skyrim_fcn.h SKFCN_ABI_VERSION
+    "skfcn_abi_version": (_I, []),
+    "skfcn_error_string": (ctypes.c_char_p, [_I]),
+    "skfcn_prepare_weight": (_I, [_P, _LL, _LL, _I, _I, _P, _LL, _I, _P]),
+    "skfcn_prepare_mlp_weights": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "skfcn_patch_embed": (_I, [ctypes.POINTER(PatchEmbedDesc), _P]),
+    "skfcn_layer_norm": (_I, [_P, _P, _P, _P, _LL, _I, _F, _P]),
+    "skfcn_spectral_mlp": (_I, [ctypes.POINTER(SpectralMlpDesc), _P]),
+    "skfcn_spectral_run": (_I, [ctypes.POINTER(SpectralDesc), _P]),
+    "skfcn_mlp_run": (_I, [ctypes.POINTER(MlpDesc), _P]),
+    "skfcn_head_run": (_I, [ctypes.POINTER(HeadDesc), _P]),
+})
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+
 _lib = None
 
 
-def load_library():
+def load_library() -> ctypes.CDLL:
     global _lib
-    if _lib is not None:
-        return _lib
-    path = os.environ.get("SKYRIM_FCN_LIB", str(_LIB_PATH))
-    if not os.path.exists(path):
-        raise RuntimeError(f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')")
-    lib = ctypes.CDLL(path)
-    lib.skfcn_error_string.restype = ctypes.c_char_p
-    lib.skfcn_error_string.argtypes = [_I]
-    lib.skfcn_prepare_weight.argtypes = [_P, _LL, _LL, _I, _I, _P, _LL, _I, _P]
-    lib.skfcn_prepare_mlp_weights.argtypes = [_P, _P, _I, _I, _I, _I, _P, _P, _P]
-    lib.skfcn_patch_embed.argtypes = [ctypes.POINTER(PatchEmbedDesc), _P]
-    lib.skfcn_layer_norm.argtypes = [_P, _P, _P, _P, _LL, _I, _F, _P]
-    lib.skfcn_spectral_mlp.argtypes = [ctypes.POINTER(SpectralMlpDesc), _P]
-    lib.skfcn_spectral_run.argtypes = [ctypes.POINTER(SpectralDesc), _P]
-    lib.skfcn_mlp_run.argtypes = [ctypes.POINTER(MlpDesc), _P]
-    lib.skfcn_head_run.argtypes = [ctypes.POINTER(HeadDesc), _P]
-    for name in EXPORTS:
-        if name != "skfcn_error_string":
-            getattr(lib, name).restype = _I
-    _lib = lib
-    return lib
-
-
-def check(code: int, what: str):
-    if code != 0:
-        msg = load_library().skfcn_error_string(code).decode()
-        raise RuntimeError(f"{what} failed with code {code} ({msg})")
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
 
 
 # ---- constant matrices ------------------------------------------------------------------------------------------------------------ #
@@ -134,20 +115,6 @@ def complex_block_matrices(w: torch.Tensor, b: torch.Tensor):
     return torch.cat([top, bot], 1).contiguous(), torch.cat([b[0], b[1]], 1).contiguous()
 
 
-class _Weight:
-    """A constant matrix [N][K] as fp16 hi/lo planes [N][ldw] on the device."""
-
-    def __init__(self, eng, w: torch.Tensor):
-        w = w.float().contiguous().to(eng.device)
-        self.N, self.K = w.shape
-        self.ldw = (self.K + 7) // 8 * 8
-        self.plane = self.N * self.ldw
-        self.buf = torch.empty(2 * self.plane, dtype=torch.float16, device=eng.device)
-        check(eng.lib.skfcn_prepare_weight(w.data_ptr(), self.K, 1, self.N, self.K, self.buf.data_ptr(), self.plane, self.ldw, eng._stream()),
-              "skfcn_prepare_weight")
-        torch.cuda.current_stream(eng.device).synchronize()
-
-
 class _Pairs:
     """``batch`` expand / contract pairs w1 [batch][H][K], w2 [batch][N][H] as fragment-order fp16 hi/lo planes."""
 
@@ -159,8 +126,8 @@ class _Pairs:
         a, b = w1.float().contiguous().to(eng.device), w2.float().contiguous().to(eng.device)
         self.w1f = torch.empty(2 * batch * H * K, dtype=torch.float16, device=eng.device)
         self.w2f = torch.empty(2 * batch * N * H, dtype=torch.float16, device=eng.device)
-        check(eng.lib.skfcn_prepare_mlp_weights(a.data_ptr(), b.data_ptr(), K, H, N, batch, self.w1f.data_ptr(), self.w2f.data_ptr(), eng._stream()),
-              "skfcn_prepare_mlp_weights")
+        native.check(eng.lib.skfcn_prepare_mlp_weights(a.data_ptr(), b.data_ptr(), K, H, N, batch, self.w1f.data_ptr(), self.w2f.data_ptr(),
+                                                       native.stream(eng.device)), "skfcn_prepare_mlp_weights", eng.lib)
         torch.cuda.current_stream(eng.device).synchronize()
 
 
@@ -175,14 +142,12 @@ class FcnEngine:
         if not 0 < c.km <= c.w // 2 + 1:
             raise ValueError(f"kept_lon_modes {c.km} outside (0, {c.w // 2 + 1}]")
         self.lib = load_library()
-        if self.lib.skfcn_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libskyrim_fcn.so ABI {self.lib.skfcn_abi_version()} != {ABI_VERSION}")
         self.device = torch.device(device)
         self.state_shape = (c.in_chans, c.n_lat, c.n_lon)
         self.prepared = False
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
+        return native.HiLoWeight(self.device, self.lib.skfcn_prepare_weight, w)
 
     def release(self):
         """Drop every prepared matrix and work buffer (the C ABI holds no state of its own)."""
@@ -204,15 +169,15 @@ class FcnEngine:
             mean, std = p["norm.mean"], p["norm.std"]
             self.kscale = f32((1.0 / std).repeat_interleave(P * P))
             self.kshift = f32((-mean / std).repeat_interleave(P * P))
-            self.embed_w = _Weight(self, p["patch_embed.proj.weight"].reshape(e, -1))
+            self.embed_w = self._weight(p["patch_embed.proj.weight"].reshape(e, -1))
             self.embed_b = f32(p["patch_embed.proj.bias"])
             self.pos = f32(p["pos_embed"].reshape(c.tokens, e))
             # head: rows n = (p1 P + p2) cout + c scaled by std_c, bias mean_c
             cidx = torch.arange(c.out_chans * P * P) % c.out_chans
-            self.head_w = _Weight(self, p["head.weight"] * std[cidx][:, None])
+            self.head_w = self._weight(p["head.weight"] * std[cidx][:, None])
             self.head_b = f32(mean[cidx])
             mats = dft_matrices(c.h, c.w, c.km)
-            self.dft = {k: _Weight(self, torch.from_numpy(v)) for k, v in mats.items()}
+            self.dft = {k: self._weight(torch.from_numpy(v)) for k, v in mats.items()}
             self.blocks = []
             for i in range(c.depth):
                 b = f"blocks.{i}."
@@ -236,7 +201,7 @@ class FcnEngine:
         d = PatchEmbedDesc(x.data_ptr(), self.kscale.data_ptr(), self.kshift.data_ptr(), self.embed_w.buf.data_ptr(), self.embed_w.plane,
                            self.embed_w.ldw, self.embed_b.data_ptr(), self.pos.data_ptr(), out.data_ptr(), c.in_chans, c.n_lat, c.n_lon,
                            c.patch, c.embed_dim)
-        check(self.lib.skfcn_patch_embed(ctypes.byref(d), self._stream()), "skfcn_patch_embed")
+        native.check(self.lib.skfcn_patch_embed(ctypes.byref(d), native.stream(self.device)), "skfcn_patch_embed", self.lib)
 
     def spectral(self, i: int, t: torch.Tensor):
         c, blk, D = self.cfg, self.blocks[i], self.dft
@@ -245,19 +210,19 @@ class FcnEngine:
                          D["fw"].plane, D["fl"].plane, D["il"].plane, D["iw"].plane, D["fw"].ldw, D["fl"].ldw, D["il"].ldw, D["iw"].ldw,
                          c.h, c.w, c.embed_dim, c.km, c.num_blocks, blk["spec"].w1f.data_ptr(), blk["spec"].w2f.data_ptr(),
                          blk["b1e"].data_ptr(), blk["b2e"].data_ptr(), c.sparsity_threshold)
-        check(self.lib.skfcn_spectral_run(ctypes.byref(d), self._stream()), "skfcn_spectral_run")
+        native.check(self.lib.skfcn_spectral_run(ctypes.byref(d), native.stream(self.device)), "skfcn_spectral_run", self.lib)
 
     def token_mlp(self, i: int, x: torch.Tensor, out: torch.Tensor):
         c, blk = self.cfg, self.blocks[i]
         d = MlpDesc(x.data_ptr(), out.data_ptr(), c.tokens, c.embed_dim, c.hidden, blk["g2"].data_ptr(), blk["be2"].data_ptr(), c.eps,
                     blk["mlp"].w1f.data_ptr(), blk["mlp"].w2f.data_ptr(), blk["fb1"].data_ptr(), blk["fb2"].data_ptr())
-        check(self.lib.skfcn_mlp_run(ctypes.byref(d), self._stream()), "skfcn_mlp_run")
+        native.check(self.lib.skfcn_mlp_run(ctypes.byref(d), native.stream(self.device)), "skfcn_mlp_run", self.lib)
 
     def head(self, t: torch.Tensor, y: torch.Tensor):
         c = self.cfg
         d = HeadDesc(t.data_ptr(), self.head_w.buf.data_ptr(), self.head_w.plane, self.head_w.ldw, self.head_b.data_ptr(), y.data_ptr(),
                      c.out_chans, c.n_lat, c.n_lon, c.patch, c.embed_dim)
-        check(self.lib.skfcn_head_run(ctypes.byref(d), self._stream()), "skfcn_head_run")
+        native.check(self.lib.skfcn_head_run(ctypes.byref(d), native.stream(self.device)), "skfcn_head_run", self.lib)
 
     def step(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """One 6-h step: fp32 (in_chans, n_lat, n_lon) on the engine device -> (out_chans, n_lat, n_lon)."""

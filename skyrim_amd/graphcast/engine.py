@@ -15,20 +15,15 @@ from __future__ import annotations
 
 import ctypes
 import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from .. import ops
+from .. import native, ops
 from ..sfno import engine as _sf
 from . import fused as _fz
 from .mesh import renumber_mesh, spatial_order, GraphStructure, build_graph, grouped_rows_by3, latitude_band, shard_graph
 from .spec import N_FORCING, N_STATIC, GraphcastConfig, mlp_names, param_spec
-
-_LIB_PATH = Path(__file__).resolve().parent.parent / "lib" / "libskyrim_graphcast.so"
-EXPORTS = ["skgc_abi_version", "skgc_gather_gemm", "skgc_layer_norm", "skgc_segment_sum", "skgc_prepare_weight_perm8",
-           "skgc_linear_layer_norm", "skgc_sum_linear_layer_norm", "skgc_edge_update", "skgc_segment_fixup", "skgc_node_mlp"]
 
 
 class GatherDesc(ctypes.Structure):
@@ -58,41 +53,31 @@ class NodeDesc(ctypes.Structure):
                 ("ld_res", ctypes.c_longlong), ("out", ctypes.c_void_p), ("ld_out", ctypes.c_longlong), ("rows", ctypes.c_longlong)]
 
 
+_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+# ABI 5 = K-outer w1f of skgc_node_mlp: the fragment orders this module packs (fused.py) belong to ONE generation of kernels
+SPEC = native.Spec("skyrim_graphcast", "SKYRIM_GRAPHCAST_LIB", "skgc", 5, {  # include/skyrim_graphcast.h SKGC_ABI_VERSION
+    "skgc_abi_version": (_I, []),
+    "skgc_gather_gemm": (_I, [ctypes.POINTER(GatherDesc), _P]),
+    "skgc_layer_norm": (_I, [_P] * 5 + [_LL, _I, _P]),
+    "skgc_segment_sum": (_I, [_P] * 4 + [_I, _I, _P]),
+    "skgc_prepare_weight_perm8": (_I, [_P, _I, _I, _P, _LL, _I, _P]),
+    "skgc_linear_layer_norm": (_I, [_P, _LL, _I, _P, _LL, _I] + [_P] * 5 + [_LL, _P]),
+    "skgc_sum_linear_layer_norm": (_I, [ctypes.POINTER(SumDesc), _P]),
+    "skgc_edge_update": (_I, [ctypes.POINTER(EdgeDesc), _P]),
+    "skgc_segment_fixup": (_I, [_P] * 5 + [_I, _P]),
+    "skgc_node_mlp": (_I, [ctypes.POINTER(NodeDesc), _P]),
+})
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+
 _lib = None
-ABI_VERSION = 5            # include/skyrim_graphcast.h SKGC_ABI_VERSION: 5 = K-outer w1f of skgc_node_mlp
 
 
-def load_library():
+def load_library() -> ctypes.CDLL:
     global _lib
-    if _lib is not None:
-        return _lib
-    path = os.environ.get("SKYRIM_GRAPHCAST_LIB", str(_LIB_PATH))
-    if not os.path.exists(path):
-        raise RuntimeError(f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')")
-    lib = ctypes.CDLL(path)
-    lib.skgc_gather_gemm.argtypes = [ctypes.POINTER(GatherDesc), ctypes.c_void_p]
-    lib.skgc_layer_norm.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
-    lib.skgc_segment_sum.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
-    lib.skgc_prepare_weight_perm8.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
-    lib.skgc_linear_layer_norm.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int] + \
-        [ctypes.c_void_p] * 5 + [ctypes.c_longlong, ctypes.c_void_p]
-    lib.skgc_sum_linear_layer_norm.argtypes = [ctypes.POINTER(SumDesc), ctypes.c_void_p]
-    lib.skgc_edge_update.argtypes = [ctypes.POINTER(EdgeDesc), ctypes.c_void_p]
-    lib.skgc_segment_fixup.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p]
-    lib.skgc_node_mlp.argtypes = [ctypes.POINTER(NodeDesc), ctypes.c_void_p]
-    for name in EXPORTS:
-        getattr(lib, name).restype = ctypes.c_int
-    # the fragment orders this module packs (fused.py) belong to ONE generation of kernels: a stale build, or a SKYRIM_GRAPHCAST_LIB variant
-    # from other sources, would read them as something else and produce silently wrong node updates
-    if lib.skgc_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"{path}: skgc ABI {lib.skgc_abi_version()}, this package packs for ABI {ABI_VERSION} (include/skyrim_graphcast.h); rebuild the library")
-    _lib = lib
-    return lib
-
-
-def _check(code: int, what: str):
-    if code != 0:
-        raise RuntimeError(f"{what} failed with code {code}")
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
 
 
 class GraphcastEngine:
@@ -157,8 +142,9 @@ class GraphcastEngine:
         self.prepared = False
         self._events = []
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
+        """A constant matrix as the fp16 hi/lo planes the SFNO GEMM (sksfno_gemm_run) reads."""
+        return native.HiLoWeight(self.device, self.sf.sksfno_prepare_weight, w)
 
     # ---- profiling (same contract as SfnoEngine) ---------------------------------------------------- #
     def _mark(self, label: str, flops: float = 0.0, terms: float = 3.0):
@@ -274,7 +260,6 @@ class GraphcastEngine:
         c, g, dev, L = self.cfg, self.graph, self.device, self.cfg.latent
         f32 = lambda t: t.float().contiguous().to(dev)  # noqa: E731
         i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)  # noqa: E731
-        weng = type("W", (), {"device": dev, "lib": self.sf, "_stream": self._stream})()
         upos = torch.from_numpy(_fz.unit_at_pos(L))
 
         def pack(edges):
@@ -321,7 +306,7 @@ class GraphcastEngine:
         F["g2m"].update(mlp_frags("g2m.edge"))
         F["g2m"]["static"] = blocked(self.e1_0, F["g2m"]["row_edge"], cols)
         w1 = p["g2m.edge.fc1.weight"]
-        F["g2m"]["w_s"] = _sf._Weight(weng, w1[:, L:2 * L][upos])
+        F["g2m"]["w_s"] = self._weight(w1[:, L:2 * L][upos])
         # multi-mesh: edge latents live in the packed order as one fp16 plane; [W_s; W_r] in "pos" rows with b1 folded into the sender term
         me = g.mesh_edges[self.me0:self.me1]
         F["mesh"] = pack(me)
@@ -333,7 +318,7 @@ class GraphcastEngine:
             name = f"proc.{i}.edge"
             w1, b1 = p[name + ".fc1.weight"], p[name + ".fc1.bias"]
             d = mlp_frags(name, 0, L)
-            d["w_sr"] = _sf._Weight(weng, torch.cat([w1[:, L:2 * L][upos], w1[:, 2 * L:][upos]], dim=0))
+            d["w_sr"] = self._weight(torch.cat([w1[:, L:2 * L][upos], w1[:, 2 * L:][upos]], dim=0))
             d["b_sr"] = f32(torch.cat([b1[upos], torch.zeros(L, dtype=b1.dtype)]))
             F[name] = d
         # mesh -> grid
@@ -341,7 +326,7 @@ class GraphcastEngine:
         F["m2g"].update(mlp_frags("m2g.edge"))
         F["m2g"]["static"] = blocked(self.e2_0, F["m2g"]["row_edge"], cols)
         w1 = p["m2g.edge.fc1.weight"]
-        F["m2g"]["w_s"], F["m2g"]["w_r"] = _sf._Weight(weng, w1[:, L:2 * L][upos]), _sf._Weight(weng, w1[:, 2 * L:][upos])
+        F["m2g"]["w_s"], F["m2g"]["w_r"] = self._weight(w1[:, L:2 * L][upos]), self._weight(w1[:, 2 * L:][upos])
         F["m2g"]["zero_agg"] = bool((np.bincount(g.m2g_edges[:, 1], minlength=g.n_grid) == 0).any())
         # node updates: fragment-order weights, three-term kernel
         for name in ["g2m.mesh_node", "g2m.grid_node", "m2g.grid_node"] + [f"proc.{i}.node" for i in range(c.steps)]:
@@ -415,27 +400,27 @@ class GraphcastEngine:
             f32 = lambda t: t.float().contiguous().to(dev)  # noqa: E731
             p = {k: v.double() for k, v in params.items() if k != "static"}
             mean, std, dstd = p["norm.mean"], p["norm.std"], p["norm.diff_std"]
-            weng = type("W", (), {"device": dev, "lib": self.sf, "_stream": self._stream})()       # what sfno's _Weight needs
             self.m = {}
             for name, d_in, d_out, ln in mlp_names(c):
                 w2, b2 = p[name + ".fc2.weight"], p[name + ".fc2.bias"]
                 if name == "out":                                       # fold the residual's de-normalisation into the last layer
                     w2, b2 = w2 * dstd[:, None], b2 * dstd
-                self.m[name] = dict(fc1=_sf._Weight(weng, p[name + ".fc1.weight"]), b1=f32(p[name + ".fc1.bias"]),
-                                    fc2=_sf._Weight(weng, w2), b2=f32(b2),
+                self.m[name] = dict(fc1=self._weight(p[name + ".fc1.weight"]), b1=f32(p[name + ".fc1.bias"]),
+                                    fc2=self._weight(w2), b2=f32(b2),
                                     g=f32(p[name + ".ln.weight"]) if ln else None, b=f32(p[name + ".ln.bias"]) if ln else None)
                 if self.split_edges and name.endswith(".edge") and not name.startswith("embed"):
                     w1 = p[name + ".fc1.weight"]
                     d = self.m[name]
-                    d["w_e"] = _sf._Weight(weng, w1[:, :L])
+                    d["w_e"] = self._weight(w1[:, :L])
                     if name.startswith("proc."):
-                        d["w_sr"] = _sf._Weight(weng, torch.cat([w1[:, L:2 * L], w1[:, 2 * L:]], dim=0))
+                        d["w_sr"] = self._weight(torch.cat([w1[:, L:2 * L], w1[:, 2 * L:]], dim=0))
                     else:
-                        d["w_s"], d["w_r"] = _sf._Weight(weng, w1[:, L:2 * L]), _sf._Weight(weng, w1[:, 2 * L:])
+                        d["w_s"], d["w_r"] = self._weight(w1[:, L:2 * L]), self._weight(w1[:, 2 * L:])
                 if ln and self.fused_ln:                                 # perm8 copy of the second Linear for the fused Linear + LayerNorm kernel
                     src = f32(w2)
                     planes = torch.empty(2 * L * L, dtype=torch.float16, device=dev)
-                    _check(self.lib.skgc_prepare_weight_perm8(src.data_ptr(), L, L, planes.data_ptr(), L * L, L, self._stream()), "skgc_prepare_weight_perm8")
+                    native.check(self.lib.skgc_prepare_weight_perm8(src.data_ptr(), L, L, planes.data_ptr(), L * L, L, native.stream(dev)),
+                                 "skgc_prepare_weight_perm8", self.lib)
                     torch.cuda.current_stream(dev).synchronize()
                     self.m[name]["fc2p"] = (planes, L * L, L)
             n_state = 2 * c.n_vars

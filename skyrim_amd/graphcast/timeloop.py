@@ -16,13 +16,13 @@ from __future__ import annotations
 
 import datetime
 import math
-from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from .. import weights
 from ..labeled import DataArray, Dataset
+from ..timeloop import EngineTimeLoop, Grid
 from .engine import GraphcastEngine
 from .spec import CHANNELS, N_FORCING, GraphcastConfig, init_synthetic, synthetic_states
 
@@ -34,16 +34,6 @@ DATASET_VARS = [("geopotential", "z", True), ("specific_humidity", "q", True), (
                 ("10m_u_component_of_wind", "u10m", False), ("10m_v_component_of_wind", "v10m", False),
                 ("2m_temperature", "t2m", False), ("mean_sea_level_pressure", "msl", False),
                 ("toa_incident_solar_radiation", "tp06", False)]
-
-
-@dataclass
-class Grid:
-    lat: list
-    lon: list
-
-    @property
-    def shape(self):
-        return (len(self.lat), len(self.lon))
 
 
 class StateDataset(Dataset):
@@ -84,9 +74,8 @@ class _Stepper:
         return (time, StateDataset(loop, cur, nxt, [time - loop.time_step, time]), rng), nxt.unsqueeze(0)
 
 
-class GraphcastTimeLoop:
+class GraphcastTimeLoop(EngineTimeLoop):
     n_history_levels = 2
-    time_step = datetime.timedelta(hours=6)
 
     def __init__(self, params: dict | None = None, cfg: GraphcastConfig | None = None, device: str | torch.device = "cuda:0", seed: int = 0):
         """``params``: state dict keyed by ``spec.param_spec``; default: the torch file named by ``SKYRIM_GRAPHCAST_WEIGHTS``
@@ -97,9 +86,7 @@ class GraphcastTimeLoop:
         if params is None:
             params = weights.resolve("SKYRIM_GRAPHCAST_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed), "graphcast")
         self.engine.load_params(params)
-        names = CHANNELS if self.cfg.n_vars == len(CHANNELS) else [f"c{i}" for i in range(self.cfg.n_vars)]
-        self.in_channel_names = list(names)
-        self.out_channel_names = list(names)
+        self._channels(CHANNELS, self.cfg.n_vars)
         self.grid = Grid(list(np.linspace(90.0, -90.0, self.cfg.n_lat)), list(np.arange(self.cfg.n_lon) * (360.0 / self.cfg.n_lon)))
         self.stepper = _Stepper(self)
         # latitude / longitude planes of the insolation proxy, cached on the device (float64: the proxy is compared with spec.forcings)
@@ -119,15 +106,6 @@ class GraphcastTimeLoop:
             kw = {k: st[k] for k in ("mean", "std", "diff_std", "static", "in_perm", "out_perm") if k in st.files}
             return checkpoint.load(os.path.join(path, "params.npz"), self.cfg, **kw)
         return torch.load(path, map_location="cpu")
-
-    @property
-    def device(self):
-        return self.engine.device
-
-    def to(self, device):
-        if torch.device(device) != self.engine.device:
-            raise NotImplementedError("the engine's buffers are bound to one GPU; build a new GraphcastTimeLoop for another device")
-        return self
 
     def synthetic_state(self, seed: int) -> torch.Tensor:
         """Initial-condition hook of the synthetic DataSource (no network for GFS / ERA5 here)."""

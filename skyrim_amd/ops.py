@@ -18,13 +18,11 @@ import ctypes
 
 import torch
 
+from . import native
+
 _NS = "skyrim_hip"
 _lib = torch.library.Library(_NS, "DEF")
 _registered = False
-
-
-def _stream(t: torch.Tensor):
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _f32(t: torch.Tensor, what: str, dev=None):
@@ -33,14 +31,20 @@ def _f32(t: torch.Tensor, what: str, dev=None):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _i32(t, what: str, dev):
+    if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous int32 tensor on {dev}")
+    return t.data_ptr()
+
+
+def _f16(t, what: str, dev):
+    if t.dtype != torch.float16 or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous float16 tensor on {dev}")
+    return t.data_ptr()
+
+
 def _opt(t, off_bytes: int = 0):
     return None if t is None else ctypes.c_void_p(t.data_ptr() + off_bytes)
-
-
-def _ok(code: int, what: str, strerror=None):
-    if code != 0:
-        msg = strerror(code).decode() if strerror is not None else ""
-        raise RuntimeError(f"{what} failed: {msg} (code {code})")
 
 
 # ---- Pangu ---------------------------------------------------------------------------------------------------------------- #
@@ -52,38 +56,38 @@ def _pangu():
 def _pangu_step(ctx: int, x: torch.Tensor, out: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(x.device):
-        _ok(lib.skpangu_step(ctypes.c_void_p(ctx), _f32(x, "x"), _f32(out, "out", x.device), _stream(x)), "skpangu_step", lib.skpangu_error_string)
+        native.check(lib.skpangu_step(ctypes.c_void_p(ctx), _f32(x, "x"), _f32(out, "out", x.device), native.stream(x.device)), "skpangu_step", lib)
 
 
 def _pangu_patch_embed(ctx: int, x: torch.Tensor, out: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(x.device):
-        _ok(lib.skpangu_patch_embed(ctypes.c_void_p(ctx), _f32(x, "x"), _f32(out, "out", x.device), _stream(x)), "skpangu_patch_embed", lib.skpangu_error_string)
+        native.check(lib.skpangu_patch_embed(ctypes.c_void_p(ctx), _f32(x, "x"), _f32(out, "out", x.device), native.stream(x.device)), "skpangu_patch_embed", lib)
 
 
 def _pangu_block(ctx: int, layer: int, block: int, x: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(x.device):
-        _ok(lib.skpangu_block(ctypes.c_void_p(ctx), layer, block, _f32(x, "x"), _stream(x)), "skpangu_block", lib.skpangu_error_string)
+        native.check(lib.skpangu_block(ctypes.c_void_p(ctx), layer, block, _f32(x, "x"), native.stream(x.device)), "skpangu_block", lib)
 
 
 def _pangu_downsample(ctx: int, x1: torch.Tensor, out: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(x1.device):
-        _ok(lib.skpangu_downsample(ctypes.c_void_p(ctx), _f32(x1, "x1"), _f32(out, "out", x1.device), _stream(x1)), "skpangu_downsample", lib.skpangu_error_string)
+        native.check(lib.skpangu_downsample(ctypes.c_void_p(ctx), _f32(x1, "x1"), _f32(out, "out", x1.device), native.stream(x1.device)), "skpangu_downsample", lib)
 
 
 def _pangu_upsample(ctx: int, x2: torch.Tensor, out: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(x2.device):
-        _ok(lib.skpangu_upsample(ctypes.c_void_p(ctx), _f32(x2, "x2"), _f32(out, "out", x2.device), _stream(x2)), "skpangu_upsample", lib.skpangu_error_string)
+        native.check(lib.skpangu_upsample(ctypes.c_void_p(ctx), _f32(x2, "x2"), _f32(out, "out", x2.device), native.stream(x2.device)), "skpangu_upsample", lib)
 
 
 def _pangu_patch_recover(ctx: int, skip: torch.Tensor, x4: torch.Tensor, out: torch.Tensor) -> None:
     lib = _pangu()
     with torch.cuda.device(skip.device):
-        _ok(lib.skpangu_patch_recover(ctypes.c_void_p(ctx), _f32(skip, "skip"), _f32(x4, "x4", skip.device), _f32(out, "out", skip.device), _stream(skip)),
-            "skpangu_patch_recover", lib.skpangu_error_string)
+        native.check(lib.skpangu_patch_recover(ctypes.c_void_p(ctx), _f32(skip, "skip"), _f32(x4, "x4", skip.device), _f32(out, "out", skip.device), native.stream(skip.device)),
+            "skpangu_patch_recover", lib)
 
 
 # ---- SFNO ------------------------------------------------------------------------------------------------------------------ #
@@ -108,15 +112,15 @@ def _sfno_gemm(a, w, out, bias, res_pre, res_post, a_kscale, a_kshift, a2, geom)
                         _opt(out, 4 * g["o_off"]), g["o_sb"], g["o_m1"], g["o_sm"], g["o_sm2"], g["o_sn"], g["M"], g["N"], g["K"], g["batch"], g["act"],
                         g["k_lo_step"], g["m_cap0"], g["m_cap_step"], _opt(a_kscale), _opt(a_kshift), _opt(a2), g["a2_sk"], g["a2_k_split"], g["terms"])
     with torch.cuda.device(a.device):
-        _ok(lib.sksfno_gemm_run(ctypes.byref(d), _stream(a)), "sksfno_gemm_run")
+        native.check(lib.sksfno_gemm_run(ctypes.byref(d), native.stream(a.device)), "sksfno_gemm_run", lib)
 
 
 def _sfno_instance_norm(x, gamma, beta, out, C: int, HW: int, eps: float) -> None:
     from .sfno import engine
     lib = engine.load_library()
     with torch.cuda.device(x.device):
-        _ok(lib.sksfno_instance_norm(_f32(x, "x"), _f32(gamma, "gamma", x.device), _f32(beta, "beta", x.device), _f32(out, "out", x.device), C, HW, eps, _stream(x)),
-            "sksfno_instance_norm")
+        native.check(lib.sksfno_instance_norm(_f32(x, "x"), _f32(gamma, "gamma", x.device), _f32(beta, "beta", x.device), _f32(out, "out", x.device), C, HW, eps, native.stream(x.device)),
+            "sksfno_instance_norm", lib)
 
 
 def _sfno_chain(mode: int, shape: int, y, x, res, out, HW: int, C: int, KX: int, OUT: int, w1f, w2f, v1f, v2f, tab) -> None:
@@ -136,7 +140,7 @@ def _sfno_chain(mode: int, shape: int, y, x, res, out, HW: int, C: int, KX: int,
     d = engine.ChainDesc(mode, shape, y.data_ptr(), _opt(x), res.data_ptr(), out.data_ptr(), HW, C, KX, OUT, w1f.data_ptr(), w2f.data_ptr(),
                          _opt(v1f), _opt(v2f), tab.data_ptr())
     with torch.cuda.device(dev):
-        _ok(lib.sksfno_chain_run(ctypes.byref(d), _stream(y)), "sksfno_chain_run")
+        native.check(lib.sksfno_chain_run(ctypes.byref(d), native.stream(y.device)), "sksfno_chain_run", lib)
 
 
 def _sfno_instance_stats(x, gamma, beta, tab, shift_off: int, C: int, HW: int, eps: float) -> None:
@@ -146,8 +150,8 @@ def _sfno_instance_stats(x, gamma, beta, tab, shift_off: int, C: int, HW: int, e
     if tab.numel() < shift_off + C or x.numel() < C * HW:
         raise ValueError("sfno_instance_stats: tab or x too small")
     with torch.cuda.device(dev):
-        _ok(lib.sksfno_instance_stats(_f32(x, "x"), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _f32(tab, "tab", dev),
-                                      ctypes.c_void_p(tab.data_ptr() + 4 * shift_off), C, HW, eps, _stream(x)), "sksfno_instance_stats")
+        native.check(lib.sksfno_instance_stats(_f32(x, "x"), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _f32(tab, "tab", dev),
+                                      ctypes.c_void_p(tab.data_ptr() + 4 * shift_off), C, HW, eps, native.stream(x.device)), "sksfno_instance_stats", lib)
 
 
 # ---- GraphCast -------------------------------------------------------------------------------------------------------------- #
@@ -171,7 +175,7 @@ def _gc_gather_gemm(src, idx, width, w, w_plane: int, ldw: int, bias, out, M: in
     d.bias = _f32(bias, "bias", dev).value
     d.out, d.ldo, d.M, d.N, d.act = _f32(out, "out").value, N, M, N, act
     with torch.cuda.device(dev):
-        _ok(lib.skgc_gather_gemm(ctypes.byref(d), _stream(out)), "skgc_gather_gemm")
+        native.check(lib.skgc_gather_gemm(ctypes.byref(d), native.stream(out.device)), "skgc_gather_gemm", lib)
 
 
 def _gc_linear_layer_norm(a, lda: int, K: int, w, w_plane: int, ldw: int, bias, gamma, beta, res, out, rows: int) -> None:
@@ -179,8 +183,8 @@ def _gc_linear_layer_norm(a, lda: int, K: int, w, w_plane: int, ldw: int, bias, 
     lib = engine.load_library()
     dev = out.device
     with torch.cuda.device(dev):
-        _ok(lib.skgc_linear_layer_norm(_f32(a, "a", dev), lda, K, ctypes.c_void_p(w.data_ptr()), w_plane, ldw, _f32(bias, "bias", dev), _f32(gamma, "gamma", dev),
-                                       _f32(beta, "beta", dev), _opt(res), _f32(out, "out"), rows, _stream(out)), "skgc_linear_layer_norm")
+        native.check(lib.skgc_linear_layer_norm(_f32(a, "a", dev), lda, K, ctypes.c_void_p(w.data_ptr()), w_plane, ldw, _f32(bias, "bias", dev), _f32(gamma, "gamma", dev),
+                                       _f32(beta, "beta", dev), _opt(res), _f32(out, "out"), rows, native.stream(out.device)), "skgc_linear_layer_norm", lib)
 
 
 def _gc_sum_linear_layer_norm(src, src_off, ld, idx, K: int, act: int, w, w_plane: int, ldw: int, bias, gamma, beta, res, out, rows: int, group: int = 0) -> None:
@@ -202,7 +206,7 @@ def _gc_sum_linear_layer_norm(src, src_off, ld, idx, K: int, act: int, w, w_plan
     d.res = res.data_ptr() if res is not None else None
     d.out, d.rows, d.group = _f32(out, "out").value, rows, group
     with torch.cuda.device(dev):
-        _ok(lib.skgc_sum_linear_layer_norm(ctypes.byref(d), _stream(out)), "skgc_sum_linear_layer_norm")
+        native.check(lib.skgc_sum_linear_layer_norm(ctypes.byref(d), native.stream(out.device)), "skgc_sum_linear_layer_norm", lib)
 
 
 def _gc_layer_norm(x, gamma, beta, res, out, rows: int, N: int) -> None:
@@ -210,7 +214,7 @@ def _gc_layer_norm(x, gamma, beta, res, out, rows: int, N: int) -> None:
     lib = engine.load_library()
     dev = out.device
     with torch.cuda.device(dev):
-        _ok(lib.skgc_layer_norm(_f32(x, "x", dev), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _opt(res), _f32(out, "out"), rows, N, _stream(out)), "skgc_layer_norm")
+        native.check(lib.skgc_layer_norm(_f32(x, "x", dev), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _opt(res), _f32(out, "out"), rows, N, native.stream(out.device)), "skgc_layer_norm", lib)
 
 
 def _gc_segment_sum(e, offsets, out, acc, n_nodes: int, N: int) -> None:
@@ -220,19 +224,7 @@ def _gc_segment_sum(e, offsets, out, acc, n_nodes: int, N: int) -> None:
     if offsets.dtype != torch.int32 or offsets.device != dev:
         raise ValueError("gc_segment_sum: offsets are int32 on the same device")
     with torch.cuda.device(dev):
-        _ok(lib.skgc_segment_sum(_f32(e, "e", dev), ctypes.c_void_p(offsets.data_ptr()), _f32(out, "out"), _opt(acc), n_nodes, N, _stream(out)), "skgc_segment_sum")
-
-
-def _i32(t, what: str, dev):
-    if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{what}: expected a contiguous int32 tensor on {dev}")
-    return t.data_ptr()
-
-
-def _f16(t, what: str, dev):
-    if t.dtype != torch.float16 or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{what}: expected a contiguous float16 tensor on {dev}")
-    return t.data_ptr()
+        native.check(lib.skgc_segment_sum(_f32(e, "e", dev), ctypes.c_void_p(offsets.data_ptr()), _f32(out, "out"), _opt(acc), n_nodes, N, native.stream(out.device)), "skgc_segment_sum", lib)
 
 
 def _gc_edge_update(e_in, e_out, term, term_off, ld, idx, recv, w1f, w2f, b2, gamma, beta, agg, heads, rows: int, probe=None, w1_planes: int = 2) -> None:
@@ -272,7 +264,7 @@ def _gc_edge_update(e_in, e_out, term, term_off, ld, idx, recv, w1f, w2f, b2, ga
         raise ValueError("gc_edge_update: w1f holds w1_planes planes of [512][512] in fragment order")
     d.probe = probe.data_ptr() if probe is not None else None
     with torch.cuda.device(dev):
-        _ok(lib.skgc_edge_update(ctypes.byref(d), _stream(agg)), "skgc_edge_update")
+        native.check(lib.skgc_edge_update(ctypes.byref(d), native.stream(agg.device)), "skgc_edge_update", lib)
 
 
 def _gc_segment_fixup(agg, heads, nodes, first, tiles) -> None:
@@ -280,8 +272,8 @@ def _gc_segment_fixup(agg, heads, nodes, first, tiles) -> None:
     lib = engine.load_library()
     dev = agg.device
     with torch.cuda.device(dev):
-        _ok(lib.skgc_segment_fixup(_f32(agg, "agg"), _f32(heads, "heads", dev), ctypes.c_void_p(_i32(nodes, "nodes", dev)), ctypes.c_void_p(_i32(first, "first", dev)),
-                                   ctypes.c_void_p(_i32(tiles, "tiles", dev)), nodes.numel(), _stream(agg)), "skgc_segment_fixup")
+        native.check(lib.skgc_segment_fixup(_f32(agg, "agg"), _f32(heads, "heads", dev), ctypes.c_void_p(_i32(nodes, "nodes", dev)), ctypes.c_void_p(_i32(first, "first", dev)),
+                                   ctypes.c_void_p(_i32(tiles, "tiles", dev)), nodes.numel(), native.stream(agg.device)), "skgc_segment_fixup", lib)
 
 
 def _gc_node_mlp(src, src_off, ld, w1f, w2f, b1, b2, gamma, beta, res, res_off: int, ld_res: int, out, out_off: int, ld_out: int, rows: int) -> None:
@@ -308,7 +300,7 @@ def _gc_node_mlp(src, src_off, ld, w1f, w2f, b1, b2, gamma, beta, res, res_off: 
         raise ValueError("gc_node_mlp: out smaller than rows x 512")
     d.out, d.ld_out, d.rows = _f32(out, "out").value + 4 * out_off, ld_out, rows
     with torch.cuda.device(dev):
-        _ok(lib.skgc_node_mlp(ctypes.byref(d), _stream(out)), "skgc_node_mlp")
+        native.check(lib.skgc_node_mlp(ctypes.byref(d), native.stream(out.device)), "skgc_node_mlp", lib)
 
 
 # ---- FourCastNet v1 ------------------------------------------------------------------------------------------------------------ #
@@ -317,20 +309,14 @@ def _fcn():
     return engine.load_library()
 
 
-def _frag16(t, what: str, dev):
-    if t.dtype != torch.float16 or t.device != dev or not t.is_contiguous():
-        raise ValueError(f"{what} must be the fp16 planes of skfcn_prepare_mlp_weights on the same device")
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _fcn_layer_norm(x, gamma, beta, out, rows: int, C: int, eps: float) -> None:
     lib = _fcn()
     dev = x.device
     if x.numel() < rows * C or out.numel() < rows * C:
         raise ValueError("fcn_layer_norm: x / out smaller than rows x C")
     with torch.cuda.device(dev):
-        _ok(lib.skfcn_layer_norm(_f32(x, "x"), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _f32(out, "out", dev), rows, C, eps, _stream(x)),
-            "skfcn_layer_norm", lib.skfcn_error_string)
+        native.check(lib.skfcn_layer_norm(_f32(x, "x"), _f32(gamma, "gamma", dev), _f32(beta, "beta", dev), _f32(out, "out", dev), rows, C, eps, native.stream(x.device)),
+            "skfcn_layer_norm", lib)
 
 
 def _fcn_mlp(x, w1f, w2f, b1, b2, gamma, beta, out, rows: int, C: int, hidden: int, eps: float) -> None:
@@ -340,9 +326,9 @@ def _fcn_mlp(x, w1f, w2f, b1, b2, gamma, beta, out, rows: int, C: int, hidden: i
     if x.numel() < rows * C or out.numel() < rows * C or w1f.numel() != 2 * C * hidden or w2f.numel() != 2 * C * hidden:
         raise ValueError("fcn_mlp: tensor sizes do not match rows, C and hidden")
     d = engine.MlpDesc(_f32(x, "x").value, _f32(out, "out", dev).value, rows, C, hidden, _f32(gamma, "gamma", dev).value, _f32(beta, "beta", dev).value,
-                       eps, _frag16(w1f, "w1f", dev).value, _frag16(w2f, "w2f", dev).value, _f32(b1, "b1", dev).value, _f32(b2, "b2", dev).value)
+                       eps, _f16(w1f, "w1f", dev), _f16(w2f, "w2f", dev), _f32(b1, "b1", dev).value, _f32(b2, "b2", dev).value)
     with torch.cuda.device(dev):
-        _ok(lib.skfcn_mlp_run(ctypes.byref(d), _stream(x)), "skfcn_mlp_run", lib.skfcn_error_string)
+        native.check(lib.skfcn_mlp_run(ctypes.byref(d), native.stream(x.device)), "skfcn_mlp_run", lib)
 
 
 def _fcn_spectral_mlp(z, w1f, w2f, b1e, b2e, geom: list[int], lam: float) -> None:
@@ -355,10 +341,10 @@ def _fcn_spectral_mlp(z, w1f, w2f, b1e, b2e, geom: list[int], lam: float) -> Non
     last = ((rows - 1) // m1) * sm2 + ((rows - 1) % m1) * sm + im_off + engine.SPECTRAL_BLOCK * nb
     if z.numel() < last or w1f.numel() != 2 * nb * 192 * 192 or w2f.numel() != 2 * nb * 192 * 192 or b1e.numel() != nb * 192 or b2e.numel() != nb * 192:
         raise ValueError("fcn_spectral_mlp: tensor sizes do not match the geometry")
-    d = engine.SpectralMlpDesc(_f32(z, "z").value, rows, sm, sm2, im_off, m1, nb, _frag16(w1f, "w1f", dev).value, _frag16(w2f, "w2f", dev).value,
+    d = engine.SpectralMlpDesc(_f32(z, "z").value, rows, sm, sm2, im_off, m1, nb, _f16(w1f, "w1f", dev), _f16(w2f, "w2f", dev),
                                _f32(b1e, "b1e", dev).value, _f32(b2e, "b2e", dev).value, lam)
     with torch.cuda.device(dev):
-        _ok(lib.skfcn_spectral_mlp(ctypes.byref(d), _stream(z)), "skfcn_spectral_mlp", lib.skfcn_error_string)
+        native.check(lib.skfcn_spectral_mlp(ctypes.byref(d), native.stream(z.device)), "skfcn_spectral_mlp", lib)
 
 
 _SCHEMAS = [

@@ -9,11 +9,10 @@ from __future__ import annotations
 
 import ctypes
 import os
-from pathlib import Path
 
 import torch
 
-from .. import ops
+from .. import native, ops
 from .spec import PanguGeometry
 
 PREC_BF16X3 = 0
@@ -51,8 +50,6 @@ DEFAULT_ROUNDING = "compensated"
 # When even three terms everywhere disagree with the tiled three-term reference by GUARD_TOL the weights themselves are the problem: FloatingPointError.
 GUARD_TOL = float(os.environ.get("SKYRIM_PANGU_GUARD_TOL", "5e-4"))
 
-_LIB_PATH = Path(__file__).resolve().parent.parent / "lib" / "libskyrim_pangu.so"
-
 
 class SkConfig(ctypes.Structure):
     _fields_ = [("n_lat", ctypes.c_int), ("n_lon", ctypes.c_int), ("precision", ctypes.c_int),
@@ -71,61 +68,39 @@ class SkStageStat(ctypes.Structure):
                 ("flops", ctypes.c_double), ("bytes", ctypes.c_double)]
 
 
-EXPORTS = [
-    "skpangu_abi_version", "skpangu_error_string", "skpangu_query_sizes", "skpangu_param_info",
-    "skpangu_create", "skpangu_destroy", "skpangu_prepare", "skpangu_calibrate", "skpangu_step", "skpangu_patch_embed",
-    "skpangu_block", "skpangu_downsample", "skpangu_upsample", "skpangu_patch_recover",
-    "skpangu_debug_buffer", "skpangu_profile", "skpangu_profile_read",
-]
+_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+SPEC = native.Spec("skyrim_pangu", "SKYRIM_PANGU_LIB", "skpangu", 6, {       # include/skyrim_pangu.h SKPANGU_ABI_VERSION
+    "skpangu_abi_version": (_I, []),
+    "skpangu_error_string": (ctypes.c_char_p, [_I]),
+    "skpangu_query_sizes": (_I, [ctypes.POINTER(SkConfig), ctypes.POINTER(SkSizes)]),
+    "skpangu_param_info": (_I, [ctypes.POINTER(SkConfig), _I, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(_LL), ctypes.POINTER(_I),
+                                ctypes.POINTER(_LL * 6)]),
+    "skpangu_create": (_I, [ctypes.POINTER(SkConfig), _P, ctypes.c_size_t, _P, ctypes.c_size_t, ctypes.POINTER(_P)]),
+    "skpangu_destroy": (None, [_P]),
+    "skpangu_prepare": (_I, [_P, _P, _P]),
+    "skpangu_calibrate": (_I, [_P, _P, _P, _P]),
+    "skpangu_step": (_I, [_P, _P, _P, _P]),
+    "skpangu_patch_embed": (_I, [_P, _P, _P, _P]),
+    "skpangu_block": (_I, [_P, _I, _I, _P, _P]),
+    "skpangu_downsample": (_I, [_P, _P, _P, _P]),
+    "skpangu_upsample": (_I, [_P, _P, _P, _P]),
+    "skpangu_patch_recover": (_I, [_P, _P, _P, _P, _P]),
+    "skpangu_debug_buffer": (_I, [_P, ctypes.c_char_p, ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_size_t)]),
+    "skpangu_profile": (_I, [_P, _I]),
+    "skpangu_profile_read": (_I, [_P, ctypes.POINTER(SkStageStat), _I, ctypes.POINTER(_I)]),
+}, " -- there is no CPU fallback for the Pangu hot path")
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
 
 _lib = None
-ABI_VERSION = 6            # include/skyrim_pangu.h SKPANGU_ABI_VERSION
 
 
 def load_library() -> ctypes.CDLL:
-    """Load libskyrim_pangu.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
+    """libskyrim_pangu.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
     global _lib
-    if _lib is not None:
-        return _lib
-    path = os.environ.get("SKYRIM_PANGU_LIB", str(_LIB_PATH))
-    if not os.path.exists(path):
-        raise RuntimeError(
-            f"HIP engine library not found at {path}; build it with `python -c 'import __graft_entry__ as g; g.build()'`"
-            " -- there is no CPU fallback for the Pangu hot path")
-    lib = ctypes.CDLL(path)
-    vp, ci, cll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-    lib.skpangu_abi_version.restype = ci
-    lib.skpangu_error_string.restype = ctypes.c_char_p
-    lib.skpangu_error_string.argtypes = [ci]
-    lib.skpangu_query_sizes.argtypes = [ctypes.POINTER(SkConfig), ctypes.POINTER(SkSizes)]
-    lib.skpangu_param_info.argtypes = [ctypes.POINTER(SkConfig), ci, ctypes.c_char_p, ctypes.c_size_t,
-                                       ctypes.POINTER(cll), ctypes.POINTER(ci), ctypes.POINTER(cll * 6)]
-    lib.skpangu_create.argtypes = [ctypes.POINTER(SkConfig), vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(vp)]
-    lib.skpangu_destroy.argtypes = [vp]
-    lib.skpangu_destroy.restype = None
-    lib.skpangu_prepare.argtypes = [vp, vp, vp]
-    lib.skpangu_calibrate.argtypes = [vp, vp, vp, vp]
-    lib.skpangu_step.argtypes = [vp, vp, vp, vp]
-    lib.skpangu_patch_embed.argtypes = [vp, vp, vp, vp]
-    lib.skpangu_block.argtypes = [vp, ci, ci, vp, vp]
-    lib.skpangu_downsample.argtypes = [vp, vp, vp, vp]
-    lib.skpangu_upsample.argtypes = [vp, vp, vp, vp]
-    lib.skpangu_patch_recover.argtypes = [vp, vp, vp, vp, vp]
-    lib.skpangu_debug_buffer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
-    lib.skpangu_profile.argtypes = [vp, ci]
-    lib.skpangu_profile_read.argtypes = [vp, ctypes.POINTER(SkStageStat), ci, ctypes.POINTER(ci)]
-    for name in EXPORTS:
-        getattr(lib, name)
-    if lib.skpangu_abi_version() != ABI_VERSION:              # a stale build or a SKYRIM_PANGU_LIB variant from other sources
-        raise RuntimeError(f"{path}: skpangu ABI {lib.skpangu_abi_version()}, this package binds ABI {ABI_VERSION} (include/skyrim_pangu.h); rebuild the library")
-    _lib = lib
-    return lib
-
-
-def _check(code: int, what: str):
-    if code != 0:
-        msg = load_library().skpangu_error_string(code).decode()
-        raise RuntimeError(f"{what} failed: {msg} (code {code})")
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
 
 
 PAD_MODES = {"centre": 0, "back": 1}
@@ -153,7 +128,8 @@ def make_config(geom: PanguGeometry, precision: str = DEFAULT_PRECISION, roll_si
 def query_sizes(geom: PanguGeometry, precision: str = DEFAULT_PRECISION, cfg: SkConfig | None = None) -> SkSizes:
     cfg = cfg or make_config(geom, precision)
     out = SkSizes()
-    _check(load_library().skpangu_query_sizes(ctypes.byref(cfg), ctypes.byref(out)), "skpangu_query_sizes")
+    lib = load_library()
+    native.check(lib.skpangu_query_sizes(ctypes.byref(cfg), ctypes.byref(out)), "skpangu_query_sizes", lib)
     return out
 
 
@@ -166,8 +142,8 @@ def param_table(geom: PanguGeometry, precision: str = DEFAULT_PRECISION) -> list
     for i in range(n):
         name = ctypes.create_string_buffer(128)
         off, nd, shape = ctypes.c_longlong(), ctypes.c_int(), (ctypes.c_longlong * 6)()
-        _check(lib.skpangu_param_info(ctypes.byref(cfg), i, name, 128, ctypes.byref(off), ctypes.byref(nd), ctypes.byref(shape)),
-               "skpangu_param_info")
+        native.check(lib.skpangu_param_info(ctypes.byref(cfg), i, name, 128, ctypes.byref(off), ctypes.byref(nd), ctypes.byref(shape)),
+               "skpangu_param_info", lib)
         out.append((name.value.decode(), off.value, tuple(shape[j] for j in range(nd.value))))
     return out
 
@@ -222,9 +198,9 @@ class PanguEngine:
             self._prepared = torch.empty(self.sizes.prepared_bytes, dtype=torch.uint8, device=self.device)
             self._workspace = torch.empty(self.sizes.workspace_bytes, dtype=torch.uint8, device=self.device)
         ctx = ctypes.c_void_p()
-        _check(self.lib.skpangu_create(ctypes.byref(self.cfg), self._prepared.data_ptr(), self.sizes.prepared_bytes,
+        native.check(self.lib.skpangu_create(ctypes.byref(self.cfg), self._prepared.data_ptr(), self.sizes.prepared_bytes,
                                        self._workspace.data_ptr(), self.sizes.workspace_bytes, ctypes.byref(ctx)),
-               "skpangu_create")
+               "skpangu_create", self.lib)
         self._ctx = ctx
 
     @property
@@ -245,9 +221,6 @@ class PanguEngine:
             self.release()
 
     # ------------------------------------------------------------------ #
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _chk_dev(self, t: torch.Tensor, shape=None):
         if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
             raise ValueError("expected a contiguous float32 tensor on the engine device")
@@ -305,7 +278,7 @@ class PanguEngine:
                 if tuple(t.shape) != shape:
                     raise ValueError(f"{name}: expected {shape}, got {tuple(t.shape)}")
                 master[off:off + t.numel()] = t.reshape(-1).to(self.device, torch.float32)
-            _check(self.lib.skpangu_prepare(self._ctx, master.data_ptr(), self._stream()), "skpangu_prepare")
+            native.check(self.lib.skpangu_prepare(self._ctx, master.data_ptr(), native.stream(self.device)), "skpangu_prepare", self.lib)
             torch.cuda.current_stream(self.device).synchronize()
         self._master = master if self.term_plan else None       # skpangu_calibrate re-reads weights and biases from it
 
@@ -351,8 +324,8 @@ class PanguEngine:
         else:
             with torch.cuda.device(self.device):
                 x = None if state is None else state.to(self.device, torch.float32).contiguous()   # None: back to the master biases
-                _check(self.lib.skpangu_calibrate(self._ctx, self._master.data_ptr(), None if x is None else self._chk_dev(x, self.state_shape),
-                                                  self._stream()), "skpangu_calibrate")
+                native.check(self.lib.skpangu_calibrate(self._ctx, self._master.data_ptr(), None if x is None else self._chk_dev(x, self.state_shape),
+                                                  native.stream(self.device)), "skpangu_calibrate", self.lib)
                 torch.cuda.current_stream(self.device).synchronize()
         self.calibrated_on = None if state is None else "state"
 
@@ -446,12 +419,12 @@ class PanguEngine:
 
     def profile(self, on: bool):
         """Record HIP events between the launches of ``step`` (per-stage kernel time, bench.py)."""
-        _check(self.lib.skpangu_profile(self._ctx, 1 if on else 0), "skpangu_profile")
+        native.check(self.lib.skpangu_profile(self._ctx, 1 if on else 0), "skpangu_profile", self.lib)
 
     def profile_read(self) -> list[dict]:
         arr = (SkStageStat * 32)()
         n = ctypes.c_int()
-        _check(self.lib.skpangu_profile_read(self._ctx, arr, 32, ctypes.byref(n)), "skpangu_profile_read")
+        native.check(self.lib.skpangu_profile_read(self._ctx, arr, 32, ctypes.byref(n)), "skpangu_profile_read", self.lib)
         return [dict(name=arr[i].name.decode(), launches=arr[i].launches, total_ms=arr[i].total_ms,
                      flops=arr[i].flops, bytes=arr[i].bytes) for i in range(n.value)]
 
@@ -495,7 +468,7 @@ class PanguEngine:
     def debug_buffer(self, name: str, dtype: torch.dtype) -> torch.Tensor:
         """Copy of an internal buffer as a flat tensor of ``dtype`` (tests only)."""
         ptr, nbytes = ctypes.c_void_p(), ctypes.c_size_t()
-        _check(self.lib.skpangu_debug_buffer(self._ctx, name.encode(), ctypes.byref(ptr), ctypes.byref(nbytes)), "skpangu_debug_buffer")
+        native.check(self.lib.skpangu_debug_buffer(self._ctx, name.encode(), ctypes.byref(ptr), ctypes.byref(nbytes)), "skpangu_debug_buffer", self.lib)
         torch.cuda.synchronize(self.device)
         for base in (self._workspace, self._prepared):
             off = ptr.value - base.data_ptr()

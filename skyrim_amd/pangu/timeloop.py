@@ -16,23 +16,13 @@ from __future__ import annotations
 
 import datetime
 import os
-from dataclasses import dataclass
 
 import torch
 
 from .. import weights
+from ..timeloop import EngineTimeLoop, Grid
 from .engine import DEFAULT_PRECISION, PanguEngine
 from .spec import CHANNELS, PanguGeometry, init_synthetic
-
-
-@dataclass
-class Grid:
-    lat: list
-    lon: list
-
-    @property
-    def shape(self):
-        return (len(self.lat), len(self.lon))
 
 
 def _load_weights(path: str, geom: PanguGeometry) -> dict:
@@ -69,12 +59,10 @@ def _load_state(path: str, geom: PanguGeometry) -> torch.Tensor:
     return t.contiguous()
 
 
-class PanguTimeLoop:
+class PanguTimeLoop(EngineTimeLoop):
     # sigma: 512 x 2^-22 = 1.2e-4 of an O(1) signal.  An API divergence: the reference accepts any state; here an initial condition beyond the
     # limit raises FloatingPointError (one blocking .item() per forecast).  SKYRIM_PANGU_RANGE_LIMIT=<sigma> (or `inf`) overrides it.
     RANGE_LIMIT = float(os.environ.get("SKYRIM_PANGU_RANGE_LIMIT", "512"))
-    n_history_levels = 1
-    time_step = datetime.timedelta(hours=6)
     in_channel_names = list(CHANNELS)
     out_channel_names = list(CHANNELS)
 
@@ -122,18 +110,9 @@ class PanguTimeLoop:
         self._std = params["norm.std"].to(self.engine.device, torch.float32).reshape(-1, 1, 1)
 
     @property
-    def device(self):
-        return self.engine.device
-
-    @property
     def term_plan(self) -> int:
         """The MFMA term plan the 6-h engine runs with (the default unless its load-time guard fell back; engine.guard_report has the figures)."""
         return self.engine.term_plan_in_effect
-
-    def to(self, device):
-        if torch.device(device) != self.engine.device:
-            raise NotImplementedError("the engine's arenas are bound to one GPU; build a new PanguTimeLoop for another device")
-        return self
 
     def take_pending_check(self):
         """(flag tensor, step, hint) of the last yielded state's non-finite check, taken OUT of the running loop -- the caller promises to read

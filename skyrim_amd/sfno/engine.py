@@ -16,19 +16,14 @@ de-normalisation is folded into the decoder's last matrix, the big-skip concat i
 from __future__ import annotations
 
 import ctypes
-import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from .. import ops
+from .. import native, ops
 from .sht import ShtMatrices
 from .spec import SfnoConfig, param_spec
 
-_LIB_PATH = Path(__file__).resolve().parent.parent / "lib" / "libskyrim_sfno.so"
-EXPORTS = ["sksfno_abi_version", "sksfno_prepare_weight", "sksfno_gemm_run", "sksfno_instance_norm",
-           "sksfno_chain_dims", "sksfno_prepare_chain_weights", "sksfno_instance_stats", "sksfno_chain_run"]
 CHAIN_ENC, CHAIN_MLP, CHAIN_TAIL = 0, 1, 2
 
 
@@ -51,63 +46,31 @@ class ChainDesc(ctypes.Structure):                      # sksfno_chain
                 ("w1f", ctypes.c_void_p), ("w2f", ctypes.c_void_p), ("v1f", ctypes.c_void_p), ("v2f", ctypes.c_void_p), ("tab", ctypes.c_void_p)]
 
 
+_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+SPEC = native.Spec("skyrim_sfno", "SKYRIM_SFNO_LIB", "sksfno", 2, {          # include/skyrim_sfno.h SKSFNO_ABI_VERSION
+    "sksfno_abi_version": (_I, []),
+    "sksfno_prepare_weight": (_I, [_P, _LL, _LL, _I, _I, _P, _LL, _I, _P]),
+    "sksfno_gemm_run": (_I, [ctypes.POINTER(GemmDesc), _P]),
+    "sksfno_instance_norm": (_I, [_P, _P, _P, _P, _I, _LL, ctypes.c_float, _P]),
+    "sksfno_chain_dims": (_I, [_I] + [ctypes.POINTER(_I)] * 4),
+    "sksfno_prepare_chain_weights": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "sksfno_instance_stats": (_I, [_P] * 5 + [_I, _LL, ctypes.c_float, _P]),
+    "sksfno_chain_run": (_I, [ctypes.POINTER(ChainDesc), _P]),
+})
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+
 _lib = None
 
 
-def load_library():
+def load_library() -> ctypes.CDLL:
     global _lib
-    if _lib is not None:
-        return _lib
-    path = os.environ.get("SKYRIM_SFNO_LIB", str(_LIB_PATH))
-    if not os.path.exists(path):
-        raise RuntimeError(f"{path} not found: build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')")
-    lib = ctypes.CDLL(path)
-    lib.sksfno_abi_version.restype = ctypes.c_int
-    lib.sksfno_prepare_weight.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
-    lib.sksfno_gemm_run.argtypes = [ctypes.POINTER(GemmDesc), ctypes.c_void_p]
-    lib.sksfno_instance_norm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                         ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
-    lib.sksfno_chain_dims.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_int)] * 4
-    lib.sksfno_prepare_chain_weights.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p]
-    lib.sksfno_instance_stats.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
-    lib.sksfno_chain_run.argtypes = [ctypes.POINTER(ChainDesc), ctypes.c_void_p]
-    for name in EXPORTS:
-        getattr(lib, name).restype = ctypes.c_int
-    _lib = lib
-    return lib
-
-
-def _check(code: int, what: str):
-    if code != 0:
-        raise RuntimeError(f"{what} failed with code {code}")
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
 
 
 _BIG = 1 << 30       # "no split" value for the two-level row index
-
-
-class _Weight:
-    """A constant matrix [batch][N][K] prepared as fp16 hi/lo planes on the device."""
-
-    def __init__(self, eng, w: torch.Tensor):
-        w = w.float().contiguous()
-        if w.dim() == 2:
-            w = w[None]
-        self.batch, self.N, self.K = w.shape
-        self.ldw = (self.K + 7) // 8 * 8
-        per = self.N * self.ldw
-        self.plane = self.batch * per
-        self.w_sb = per
-        self.buf = torch.empty(2 * self.plane, dtype=torch.float16, device=eng.device)
-        chunk = max(1, (256 << 20) // (self.N * self.K * 4))          # upload at most ~256 MB of fp32 at a time
-        for b0 in range(0, self.batch, chunk):
-            src = w[b0:b0 + chunk].to(eng.device)
-            for j in range(src.shape[0]):
-                dst = self.buf.data_ptr() + 2 * (b0 + j) * per
-                _check(eng.lib.sksfno_prepare_weight(src[j].data_ptr(), self.K, 1, self.N, self.K, dst, self.plane, self.ldw, eng._stream()),
-                       "sksfno_prepare_weight")
-            torch.cuda.current_stream(eng.device).synchronize()
 
 
 def chain_shapes(lib) -> list[tuple[int, int, int, int]]:
@@ -115,7 +78,7 @@ def chain_shapes(lib) -> list[tuple[int, int, int, int]]:
     out = []
     for k in range(2):
         v = [ctypes.c_int() for _ in range(4)]
-        _check(lib.sksfno_chain_dims(k, *[ctypes.byref(t) for t in v]), "sksfno_chain_dims")
+        native.check(lib.sksfno_chain_dims(k, *[ctypes.byref(t) for t in v]), "sksfno_chain_dims", lib)
         out.append(tuple(t.value for t in v))
     return out
 
@@ -130,8 +93,8 @@ class _Pair:
         a, b = w1.float().contiguous().to(eng.device), w2.float().contiguous().to(eng.device)
         self.w1f = torch.empty(2 * H * K, dtype=torch.float16, device=eng.device)
         self.w2f = torch.empty(2 * N * H, dtype=torch.float16, device=eng.device)
-        _check(eng.lib.sksfno_prepare_chain_weights(a.data_ptr(), b.data_ptr(), K, H, N, self.w1f.data_ptr(), self.w2f.data_ptr(), eng._stream()),
-               "sksfno_prepare_chain_weights")
+        native.check(eng.lib.sksfno_prepare_chain_weights(a.data_ptr(), b.data_ptr(), K, H, N, self.w1f.data_ptr(), self.w2f.data_ptr(),
+                                                          native.stream(eng.device)), "sksfno_prepare_chain_weights", eng.lib)
         torch.cuda.current_stream(eng.device).synchronize()
 
 
@@ -173,8 +136,8 @@ class SfnoEngine:
         self.state_shape = (c.in_chans, c.n_lat, c.n_lon)
         self._label = "gemm"
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
+        return native.HiLoWeight(self.device, self.lib.sksfno_prepare_weight, w)
 
     def release(self):
         """Drop every prepared matrix, table and work buffer (GlobalModel.release_model).  The C ABI holds no state of its own -- all device
@@ -201,9 +164,9 @@ class SfnoEngine:
             # the input normalisation is applied by the GEMM's loader BEFORE the fp16 split (raw geopotential / pressure exceed
             # the fp16 range), the output de-normalisation is folded into the decoder's last matrix
             self.in_scale, self.in_shift = f32(1.0 / std), f32(-mean / std)
-            self.enc1 = _Weight(self, p["encoder.fc1.weight"])
+            self.enc1 = self._weight(p["encoder.fc1.weight"])
             self.enc1_b = f32(p["encoder.fc1.bias"])
-            self.enc2 = _Weight(self, p["encoder.fc2.weight"])
+            self.enc2 = self._weight(p["encoder.fc2.weight"])
             self.pos = f32(p["pos_embed"])
             e = c.embed_dim
             self.blocks = []
@@ -224,26 +187,26 @@ class SfnoEngine:
                     mix[:, e:, e:] += ws
                 self.blocks.append(dict(
                     n0_g=f32(g("norm0.weight")), n0_b=f32(g("norm0.bias")), n1_g=f32(g("norm1.weight")), n1_b=f32(g("norm1.bias")),
-                    mix=_Weight(self, mix), skip=_Weight(self, g("inner_skip.weight")), skip_b=f32(g("inner_skip.bias")),
-                    fc1=_Weight(self, g("mlp.fc1.weight")), fc1_b=f32(g("mlp.fc1.bias")),
-                    fc2=_Weight(self, g("mlp.fc2.weight")), fc2_b=f32(g("mlp.fc2.bias")),
+                    mix=self._weight(mix), skip=self._weight(g("inner_skip.weight")), skip_b=f32(g("inner_skip.bias")),
+                    fc1=self._weight(g("mlp.fc1.weight")), fc1_b=f32(g("mlp.fc1.bias")),
+                    fc2=self._weight(g("mlp.fc2.weight")), fc2_b=f32(g("mlp.fc2.bias")),
                     skip_b00=f32(g("inner_skip.bias") * (4.0 * np.pi) ** 0.5)))        # the bias as the (0, 0) coefficient of a constant field
                 del mix
             self.zero_a = torch.zeros(8, dtype=torch.float32, device=dev)
-            self.zero_w = _Weight(self, torch.zeros(e, 8))
+            self.zero_w = self._weight(torch.zeros(e, 8))
             # decoder.fc1 acts on concat(features, normalised input): one GEMM with two A sources along K (k < e: features,
             # k >= e: the raw state, normalised by the loader's per-k affine) when e is a multiple of 8, else two GEMMs
             wd = p["decoder.fc1.weight"]
             self.dec_fused = e % 8 == 0
             if self.dec_fused:
-                self.dec1 = _Weight(self, wd)
+                self.dec1 = self._weight(wd)
                 self.dec_scale = f32(torch.cat([torch.ones(e, dtype=torch.float64), 1.0 / std]))
                 self.dec_shift = f32(torch.cat([torch.zeros(e, dtype=torch.float64), -mean / std]))
             else:
-                self.dec1a = _Weight(self, wd[:, :e])
-                self.dec1b = _Weight(self, wd[:, e:])
+                self.dec1a = self._weight(wd[:, :e])
+                self.dec1b = self._weight(wd[:, e:])
             self.dec1_b = f32(p["decoder.fc1.bias"])
-            self.dec2 = _Weight(self, p["decoder.fc2.weight"] * std[: c.out_chans, None])
+            self.dec2 = self._weight(p["decoder.fc2.weight"] * std[: c.out_chans, None])
             self.dec2_b = f32(mean[: c.out_chans])
             self._prepare_chains(p, mean, std)
             # transforms: outer (equiangular 721 x 1440) and inner (Legendre-Gauss h x w)
@@ -251,8 +214,8 @@ class SfnoEngine:
             for key, (nlat, nlon, grid) in {"outer": (c.n_lat, c.n_lon, "equiangular"), "inner": (c.h, c.w, "legendre-gauss")}.items():
                 m = ShtMatrices(nlat, nlon, c.lmax, c.mmax, grid)
                 self.tr[key] = dict(n_lat=nlat, n_lon=nlon,
-                                    dft=_Weight(self, torch.from_numpy(m.dft)), idft=_Weight(self, torch.from_numpy(m.idft)),
-                                    ana=_Weight(self, torch.from_numpy(m.analysis)), syn=_Weight(self, torch.from_numpy(m.synthesis)))
+                                    dft=self._weight(torch.from_numpy(m.dft)), idft=self._weight(torch.from_numpy(m.idft)),
+                                    ana=self._weight(torch.from_numpy(m.analysis)), syn=self._weight(torch.from_numpy(m.synthesis)))
             # work buffers
             hw_o, hw_i = c.n_lat * c.n_lon, c.h * c.w
             hid = e * c.mlp_ratio
@@ -322,7 +285,7 @@ class SfnoEngine:
         self._events = []
         return list(out.values())
 
-    def _gemm(self, a, W: _Weight, out, M, K, N, *, a_sm, a_sk, o_sm, o_sn, batch=1, a_sb=0, o_sb=0, a_m1=_BIG, a_sm2=0,
+    def _gemm(self, a, W: native.HiLoWeight, out, M, K, N, *, a_sm, a_sk, o_sm, o_sn, batch=1, a_sb=0, o_sb=0, a_m1=_BIG, a_sm2=0,
               o_m1=_BIG, o_sm2=0, bias=None, res_pre=None, res_post=None, act=0, a_off=0, o_off=0, w_batched=None, k_lo_step=0, m_cap0=0, m_cap_step=0, a_kscale=None, a_kshift=None, a2=None, a2_sk=0, a2_k_split=0):
         if N != W.N or K != W.K:
             raise ValueError(f"GEMM {M}x{N}x{K} against a prepared [{W.N}][{W.K}] matrix")

@@ -113,9 +113,9 @@ def test_mesh_to_grid_edge_update_and_receiver_sum_in_one_kernel(monkeypatch):
     edge = torch.where(node < G, 3 * node.clamp(max=G - 1) + (v % 48) // 16, torch.zeros_like(v))
     i32 = lambda t: t.to(torch.int32).cuda()  # noqa: E731
     planes = torch.empty(2 * L * L, dtype=torch.float16, device="cuda")      # perm8 row order: what the fused Linear + LayerNorm kernels read
-    from skyrim_amd.graphcast.engine import _check
+    from skyrim_amd.native import check, stream
     wd = w.cuda().contiguous()
-    _check(eng.lib.skgc_prepare_weight_perm8(wd.data_ptr(), L, L, planes.data_ptr(), L * L, L, eng._stream()), "skgc_prepare_weight_perm8")
+    check(eng.lib.skgc_prepare_weight_perm8(wd.data_ptr(), L, L, planes.data_ptr(), L * L, L, stream(eng.device)), "skgc_prepare_weight_perm8", eng.lib)
     torch.cuda.synchronize()
     out = torch.full((G, L), float("nan"), device="cuda")
     torch.ops.skyrim_hip.gc_sum_linear_layer_norm([e.cuda(), vs.cuda(), vr.cuda()], [0, 0, 0], [L, L, L], [i32(edge), i32(send[edge]), i32(edge // 3)], L, 2,
@@ -218,8 +218,7 @@ def test_building_blocks_against_torch():
     s0, s1, s2 = torch.randn(rows, L, generator=gen), torch.randn(n0, L, generator=gen), torch.randn(n1, L, generator=gen)
     i1, i2 = torch.randint(0, n0, (rows,), generator=gen).int(), torch.randint(0, n1, (rows,), generator=gen).int()
     w, bias = torch.randn(L, 3 * L, generator=gen) / 10, torch.randn(L, generator=gen)
-    weng = type("W", (), {"device": eng.device, "lib": eng.sf, "_stream": eng._stream})()
-    W = E._sf._Weight(weng, w)
+    W = eng._weight(w)
     outd = torch.zeros(rows, L, device="cuda")
     eng._fc1(W, bias.cuda(), [(s0.cuda(), None, L), (s1.cuda(), i1.cuda(), L), (s2.cuda(), i2.cuda(), L)], rows, outd)
     ref = torch.nn.functional.silu(torch.cat([s0, s1[i1.long()], s2[i2.long()]], 1).double() @ w.double().T + bias.double())

@@ -115,7 +115,7 @@ def test_gemm_building_block_against_float64():
     a = torch.randn(B, M2, K, M1, generator=gen)                     # A[b](m, k) = a[b, m // 2, k, m % 2]
     w = torch.randn(B, N, K, generator=gen)
     bias, r1, r2 = torch.randn(N, generator=gen), torch.randn(B, N, M2, M1, generator=gen), torch.randn(B, N, M2, M1, generator=gen)
-    W = E._Weight(eng, w)
+    W = eng._weight(w)
     ad, out = a.cuda(), torch.zeros(B, N, M2, M1, device="cuda")
     eng._gemm(ad, W, out, M1 * M2, K, N, batch=B, a_sb=M2 * K * M1, a_m1=M1, a_sm=1, a_sm2=K * M1, a_sk=M1,
               o_sb=N * M2 * M1, o_m1=M1, o_sm=1, o_sm2=M1, o_sn=M2 * M1, bias=bias.cuda(), res_pre=r1.cuda(), res_post=r2.cuda(), act=1)
