@@ -43,7 +43,8 @@ typedef struct sksfno_gemm {
     int M, N, K, batch;
     int act;               /* 0 = none, 1 = erf-GELU, 2 = swish */
     /* ragged batches (spherical harmonics are zero for l < m): batch b contracts only k >= (b * k_lo_step) rounded down to a
-     * multiple of 32, and computes only rows m < m_cap0 + b * m_cap_step when m_cap_step > 0 (other rows are left untouched). */
+     * multiple of 32, and computes only rows m < m_cap0 + b * m_cap_step when m_cap_step > 0 (other rows are left untouched).
+     * A descriptor whose last batch would contract nothing (floor32((batch - 1) * k_lo_step) >= K) is refused with SKSFNO_E_ARG. */
     int k_lo_step, m_cap0, m_cap_step;
     /* optional per-k affine applied to A before it is split into fp16 hi/lo: A'(m, k) = A(m, k) * a_kscale[k] + a_kshift[k]
      * (input normalisation -- raw fields such as geopotential or pressure exceed the fp16 range); both or neither */

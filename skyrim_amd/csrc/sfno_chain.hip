@@ -18,6 +18,7 @@
 // Activations are [C][HW] fp32 (pixels contiguous): a fragment is fetched with 8 dword loads per lane (16 consecutive pixels
 // of 4 x 8 channels per instruction) and stored the same way.  HW must be a multiple of 16.  gfx950 only.
 #include "gemm_dma.h"
+#include "moments.h"
 #include "../../include/skyrim_sfno.h"
 
 namespace skp {
@@ -340,33 +341,12 @@ __global__ void prep_chain_w2_kernel(const float* __restrict__ w2, f16* __restri
 // ---- instance-norm statistics as the per-channel affine of the consumer:  scale = gamma rstd,  shift = beta - mean gamma rstd ---- //
 __global__ void __launch_bounds__(1024) instance_stats_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               float* __restrict__ scale, float* __restrict__ shift, long long HW, float eps) {
-    __shared__ float red[2][16];
-    const float* xc = x + (long long)blockIdx.x * HW;
-    const float pv = xc[0];                          // shifted one-pass moments (sfno_ops.hip: instance_norm_kernel)
-    float s = 0.f, q = 0.f;
-    if ((HW & 3) == 0) {
-        for (long long i = threadIdx.x; i < HW / 4; i += blockDim.x) {
-            const float4 v = reinterpret_cast<const float4*>(xc)[i];
-            const float a = v.x - pv, b = v.y - pv, c = v.z - pv, d = v.w - pv;
-            s += (a + b) + (c + d);
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    } else {
-        for (long long i = threadIdx.x; i < HW; i += blockDim.x) { const float d = xc[i] - pv; s += d; q += d * d; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); q += __shfl_xor(q, o); }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[0][wave] = s; red[1][wave] = q; }
-    __syncthreads();
+    const Moments mo = block_moments(x + (long long)blockIdx.x * HW, HW);       // one read of the channel (moments.h)
     if (threadIdx.x == 0) {
-        float ts = 0.f, tq = 0.f;
-        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { ts += red[0][w]; tq += red[1][w]; }
-        const float m1 = ts / (float)HW, m2 = tq / (float)HW;
-        const float rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + eps);
+        const float rstd = rsqrtf(mo.m2 / (float)HW + eps);
         const float gsc = gamma[blockIdx.x] * rstd;
         scale[blockIdx.x] = gsc;
-        shift[blockIdx.x] = beta[blockIdx.x] - (pv + m1) * gsc;
+        shift[blockIdx.x] = beta[blockIdx.x] - mo.mean * gsc;
     }
 }
 

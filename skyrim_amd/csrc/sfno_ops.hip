@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/skyrim_sfno.h"
+#include "moments.h"
 #include "strided_gemm.h"
 
 namespace skp {
@@ -72,44 +73,16 @@ __global__ void __launch_bounds__(TS::THREADS) __attribute__((amdgpu_waves_per_e
     gemm_strided_body<PX, AL, SWAP, TS>(g, bs);
 }
 
-// ---- instance norm over (H, W) per channel: two passes for the statistics, one to apply ---- //
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    float s = 0.f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-    return s;
-}
-
+// ---- instance norm over (H, W) per channel: one pass for the statistics (moments.h), one to apply ---- //
 __global__ void __launch_bounds__(1024) instance_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                              const float* __restrict__ beta, float* __restrict__ out, long long HW, float eps) {
-    __shared__ float red[16];
     const float* xc = x + (long long)blockIdx.x * HW;
     float* oc = out + (long long)blockIdx.x * HW;
     const bool v4 = (HW & 3) == 0;
-    // one pass for both moments, shifted by the channel's first value (var = E[(x-p)^2] - E[x-p]^2 keeps its digits as long as
-    // |mean - p| is a few standard deviations): 2 reads + 1 write of the tensor instead of 3 + 1
-    const float pv = xc[0];
-    float s = 0.f, q = 0.f;
-    if (v4) {
-        for (long long i = threadIdx.x; i < HW / 4; i += blockDim.x) {
-            const float4 v = reinterpret_cast<const float4*>(xc)[i];
-            const float a = v.x - pv, b = v.y - pv, c = v.z - pv, d = v.w - pv;
-            s += (a + b) + (c + d);
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    } else {
-        for (long long i = threadIdx.x; i < HW; i += blockDim.x) { const float d = xc[i] - pv; s += d; q += d * d; }
-    }
-    const float m1 = block_sum(s, red) / (float)HW;
-    const float m2 = block_sum(q, red) / (float)HW;
-    const float mean = pv + m1;
-    const float rstd = rsqrtf(fmaxf(m2 - m1 * m1, 0.f) + eps);
-    const float g = gamma[blockIdx.x] * rstd, b = beta[blockIdx.x] - mean * g;
+    // 2 reads + 1 write of the tensor instead of 3 + 1
+    const Moments mo = block_moments(xc, HW);
+    const float rstd = rsqrtf(mo.m2 / (float)HW + eps);
+    const float g = gamma[blockIdx.x] * rstd, b = beta[blockIdx.x] - mo.mean * g;
     if (v4) {
         for (long long i = threadIdx.x; i < HW / 4; i += blockDim.x) {
             const float4 v = reinterpret_cast<const float4*>(xc)[i];
@@ -138,7 +111,8 @@ int sksfno_gemm_run(const sksfno_gemm* d, void* stream) {
     if (!d || !d->a || !d->w || !d->out || d->M <= 0 || d->N <= 0 || d->K <= 0 || d->batch <= 0 || d->a_m1 <= 0 || d->o_m1 <= 0 ||
         (d->ldw & 7) || d->ldw < d->K || (d->act < 0 || d->act > 2) || d->k_lo_step < 0 || d->m_cap_step < 0 || (d->terms != 0 && d->terms != 2 && d->terms != 3) ||
         (d->a_kscale == nullptr) != (d->a_kshift == nullptr) || (d->a_kscale != nullptr && d->k_lo_step > 0) ||
-        (d->a2 != nullptr && (d->a2_k_split <= 0 || (d->a2_k_split & 7) || d->a2_k_split >= d->K || d->k_lo_step > 0 || d->batch != 1)))
+        (d->a2 != nullptr && (d->a2_k_split <= 0 || (d->a2_k_split & 7) || d->a2_k_split >= d->K || d->k_lo_step > 0 || d->batch != 1)) ||
+        (long long)(d->batch - 1) * d->k_lo_step / 32 * 32 >= d->K)     // a batch with nothing to contract (its output would stay unwritten)
         return SKSFNO_E_ARG;
     const ALStrided al{d->a, d->M, d->K, d->a_m1, d->a_sm, d->a_sm2, d->a_sk, d->a_kscale, d->a_kshift, d->a2, d->a2_sk, d->a2_k_split};
     const EpStrided ep{d->out, d->bias, d->res_pre, d->res_post, d->o_m1, d->act, d->o_sm, d->o_sm2, d->o_sn};

@@ -158,20 +158,26 @@ def test_restatement_filter_equals_explicit_dft_sum():
 
 
 def test_engine_dft_matrices_equal_torch_fft():
+    """The four DFT matrices against torch.fft in float64: even and odd h and w, the longitude Nyquist column kept (km = w // 2 + 1, w
+    even) or absent (w odd), km = 1.  The inverse gets a spectrum that is not Hermitian where the C2R has to drop something: random
+    imaginary parts in the m = 0 and the Nyquist column."""
     from skyrim_amd.fcn.engine import dft_matrices
-    h, w, km = 6, 12, 4
-    m = {k: torch.from_numpy(v) for k, v in dft_matrices(h, w, km).items()}
-    x = torch.randn(h, w, dtype=torch.float64)
-    U = torch.fft.rfft2(x, norm="ortho")[:, :km]
-    Y = (m["fw"] @ x.T).T.reshape(h, 2, km).reshape(2 * h, km)        # [2 h + ri][m]
-    Z = m["fl"] @ Y
-    assert torch.allclose(torch.complex(Z[0::2], Z[1::2]), U, atol=1e-12)
-    S = torch.randn(h, km, dtype=torch.complex128)                     # not Hermitian in m = 0
-    Zs = torch.stack([S.real, S.imag], 1).reshape(2 * h, km)
-    f = (m["iw"] @ (m["il"] @ Zs).reshape(h, 2 * km).T).T
-    full = torch.zeros(h, w // 2 + 1, dtype=torch.complex128)
-    full[:, :km] = S
-    assert torch.allclose(f, torch.fft.irfft2(full, s=(h, w), norm="ortho"), atol=1e-12)
+    gen = torch.Generator().manual_seed(0)
+    for h, w, km in [(6, 12, 4), (9, 16, 5), (8, 25, 13), (8, 24, 13), (5, 10, 6), (9, 9, 5), (7, 12, 1)]:
+        m = {k: torch.from_numpy(v) for k, v in dft_matrices(h, w, km).items()}
+        assert m["fw"].shape == (2 * km, w) and m["fl"].shape == m["il"].shape == (2 * h, 2 * h) and m["iw"].shape == (w, 2 * km)
+        x = torch.randn(h, w, dtype=torch.float64, generator=gen)
+        U = torch.fft.rfft2(x, norm="ortho")[:, :km]
+        Y = (m["fw"] @ x.T).T.reshape(h, 2, km).reshape(2 * h, km)        # [2 h + ri][m]
+        Z = m["fl"] @ Y
+        assert torch.allclose(torch.complex(Z[0::2], Z[1::2]), U, atol=1e-12), (h, w, km)
+        S = torch.complex(torch.randn(h, km, dtype=torch.float64, generator=gen), torch.randn(h, km, dtype=torch.float64, generator=gen))
+        assert (S[:, 0].imag.abs() > 0).all() and (w % 2 or km < w // 2 + 1 or (S[:, w // 2].imag.abs() > 0).all())
+        Zs = torch.stack([S.real, S.imag], 1).reshape(2 * h, km)
+        f = (m["iw"] @ (m["il"] @ Zs).reshape(h, 2 * km).T).T
+        full = torch.zeros(h, w // 2 + 1, dtype=torch.complex128)
+        full[:, :km] = S
+        assert torch.allclose(f, torch.fft.irfft2(full, s=(h, w), norm="ortho"), atol=1e-12), (h, w, km)
 
 
 class _Loop:

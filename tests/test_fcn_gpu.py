@@ -24,6 +24,8 @@ def _cfgs():
     return {
         "A": FcnConfig(n_lat=64, n_lon=128, patch=8, embed_dim=768, depth=2, num_blocks=8),
         "B": FcnConfig(n_lat=40, n_lon=120, patch=4, embed_dim=192, depth=3, num_blocks=2),     # 10 x 30 = 300 tokens
+        "C": FcnConfig(n_lat=36, n_lon=100, patch=4, embed_dim=192, depth=2, num_blocks=2, kept_lon_modes=13),    # odd h 9, odd w 25, every mode
+        "D": FcnConfig(n_lat=32, n_lon=96, patch=4, embed_dim=192, depth=2, num_blocks=2, kept_lon_modes=13),     # w 24, Nyquist column kept
     }
 
 
@@ -117,7 +119,7 @@ def test_head_kernel(toy_b):
 
 
 # ---- whole steps ------------------------------------------------------------------------------------------------------------------ #
-@pytest.mark.parametrize("name", ["A", "B"])
+@pytest.mark.parametrize("name", ["A", "B", "C", "D"])
 def test_step_matches_restatement(name):
     from skyrim_amd.fcn.spec import init_synthetic, synthetic_state
     cfg = _cfgs()[name]
