@@ -10,8 +10,11 @@ per rank (weak scaling, members are independent); the timed region ends with the
 forms the ensemble mean/spread of the final step.  Prints ONE JSON line on rank 0.  ``--dump-outputs DIR`` also writes what the last
 timed step computed as DIR/<name>.npy (inputs are seeded: the same arguments give the same inputs, so two builds compare output for output).
 
-At N = 1 the same line also carries, under "models", a short driver-timed run of the other two rows of the hot path (FourCastNet
-v2-small and GraphCast at 721x1440: ms per step, the roofline of the dominant stage, the committed profile it is read against);
+A plain run does only what that line's headline needs: set-up, warm-up, the timed steps (their per-stage events give the roofline),
+``--dump-outputs`` and the line.  ``--full`` adds, at N = 1, everything that takes runs of its own: the CPU baseline, parity against the
+oracle, the other precision modes, the reference-shaped host path and, under "models", a short timed run of the other two rows of
+the hot path (FourCastNet v2-small and GraphCast at 721x1440: ms per step, the roofline of the dominant stage, the committed profile it is
+read against); ``--no-cpu-baseline`` and the other ``--no-*`` switches leave pieces of it out.
 ``--model sfno|graphcast`` makes one of them the headline line instead.  Counter-derived fields (HBM traffic, MFMA-busy) are never
 measured in this run: they are read from the committed ``profiles/r03_<model>_pmc.json`` and are dropped -- with a note -- when that
 summary holds no kernel of the name the live run's dominant stage launches.
@@ -634,7 +637,7 @@ def run_graphcast(args, rank, local_rank, world, dist):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -642,11 +645,13 @@ def main():
     ap.add_argument("--precision", default=None, help="engine precision mode (default: skyrim_amd.pangu.engine.DEFAULT_PRECISION)")
     ap.add_argument("--n-lat", type=int, default=721)
     ap.add_argument("--n-lon", type=int, default=1440)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-alt-modes", action="store_true", help="skip the short runs of the other precision modes")
-    ap.add_argument("--members-per-gpu", type=int, default=2, help="pangu, N = 1: members advanced on separate streams in the members_per_gpu entry")
-    ap.add_argument("--no-models", action="store_true", help="pangu, N = 1: skip the short SFNO / GraphCast runs reported under \"models\"")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the timed steps, also what takes runs of its own: the CPU baseline and "
+                    "the parity checks against the oracle; pangu: also the other precision modes, the host paths and short SFNO / GraphCast runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the parity checks against the oracle")
+    ap.add_argument("--no-alt-modes", action="store_true", help="--full: skip the short runs of the other precision modes and host paths")
+    ap.add_argument("--members-per-gpu", type=int, default=2, help="pangu, --full: members advanced on separate streams in the members_per_gpu entry")
+    ap.add_argument("--no-models", action="store_true", help="pangu, --full: skip the short SFNO / GraphCast runs reported under \"models\"")
     ap.add_argument("--members", type=int, default=0, help="pangu, --gpus > 1: ensemble members in total, sharded round-robin over the ranks "
                     "(BASELINE configs[4]: --gpus 8 --members 50 --save-every 1 --gather); default: one member per rank")
     ap.add_argument("--save-every", type=int, default=0, help="ensemble mean / spread (and --gather) every this many steps; default: once, after the last step")
@@ -663,9 +668,16 @@ def main():
                     "exercise the multi-rank control flow on a box with fewer GPUs than ranks)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (rank 0's "
                     "states; with --gpus > 1 also the ensemble mean / spread) as DIR/<name>.npy, under 64 MB in all (a fixed sample of larger arrays)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if not args.full:          # a plain run: the headline line, nothing that takes runs of its own
+        args.no_cpu_baseline = args.no_parity = args.no_alt_modes = args.no_models = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -712,7 +724,6 @@ def main():
     if n_members < world:
         raise SystemExit("--members must be >= --gpus")
     mine = member_shard(n_members, rank, world)              # round-robin: 50 members on 8 ranks -> 7,7,6,6,6,6,6,6
-    x_host = synthetic_state(geom, 0, member=mine[0] if world > 1 else None)
     xs = [synthetic_state(geom, 0, member=m if world > 1 else None).to(dev) for m in mine]
     x = xs[0]
     save_every = args.save_every or args.steps
@@ -828,6 +839,7 @@ def main():
         if dumped:
             out["dump_outputs"] = dumped
         kept = {}
+        x_host = synthetic_state(geom, 0) if world == 1 and args.full else None     # the timed state before its first step
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params, geom, x_host, kept)
         if world == 1 and not args.no_parity:

@@ -41,3 +41,14 @@ def test_dump_is_float_bounded_and_the_same_sample_every_run(tmp_path):
 def test_steps_below_one_is_refused():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_plain_run_leaves_every_extra_run_to_full():
+    b = _bench()
+    extras = ("no_cpu_baseline", "no_parity", "no_alt_modes", "no_models")
+    plain = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, k) for k in extras)
+    full = b.parse_args(["--gpus", "1", "--full"])
+    assert full.full and not any(getattr(full, k) for k in extras)
+    part = b.parse_args(["--full", "--no-models"])
+    assert part.no_models and not part.no_parity

@@ -1,5 +1,5 @@
 #!/bin/bash
-# GPU box: the measurements kept under profiles/ for a round -- default bench lines of the three models, rocprofv3 --kernel-trace --stats
+# On an MI355X: the measurements kept under profiles/ for a round -- bench.py --full lines of the three models, rocprofv3 --kernel-trace --stats
 # of the same commands, and the counter passes (tools/pmc_collect.sh).  Everything lands in gpurun_out/final/ (gpurun merges that
 # directory back); copy <round>_* from there into profiles/ afterwards.
 #   bash tools/final_profiles.sh [models...]        (default: pangu sfno graphcast)
@@ -26,11 +26,11 @@ for m in $MODELS; do
 done
 for m in $MODELS; do
   case $m in
-    pangu) python bench.py > $O/${R}_bench_pangu_line.json 2> $O/bench_pangu.err      # stdout: the compact line the driver records
+    pangu) python bench.py --full > $O/${R}_bench_pangu_line.json 2> $O/bench_pangu.err   # stdout: the compact result line
            cp bench_detail.json $O/${R}_bench_pangu.json                             # the full record of the same run
            python bench.py --graph --no-cpu-baseline --no-parity --no-alt-modes --no-models > $O/${R}_bench_pangu_graph.json 2> $O/bench_pangu_graph.err ;;
-    sfno) python bench.py --model sfno > $O/${R}_bench_sfno.json 2> $O/bench_sfno.err ;;
-    graphcast) python bench.py --model graphcast --steps 5 > $O/${R}_bench_graphcast.json 2> $O/bench_graphcast.err ;;
+    sfno) python bench.py --model sfno --full > $O/${R}_bench_sfno.json 2> $O/bench_sfno.err ;;
+    graphcast) python bench.py --model graphcast --steps 5 --full > $O/${R}_bench_graphcast.json 2> $O/bench_graphcast.err ;;
   esac
   echo "bench $m rc=$?"
 done
