@@ -43,6 +43,11 @@ class GlobalEnsemble:
         missing = [n for n in model_names if n not in MODELS]
         if missing:
             raise ValueError(f"Models {missing} are not available in MODELS.")
+        steps = {n: getattr(MODELS[n], "model_time_step", datetime.timedelta(hours=6)) for n in model_names}
+        if len(set(steps.values())) > 1:
+            raise ValueError("ensemble members must share one time step (their predictions are averaged entry by entry): "
+                             + ", ".join(f"{n} {s.total_seconds() / 3600:g} h" for n, s in steps.items()))
+        self._time_step = next(iter(steps.values()), datetime.timedelta(hours=6))
         self.model_names = model_names
         self.ic_source = ic_source
         self.model_kwargs = dict(model_kwargs or {})
@@ -51,7 +56,7 @@ class GlobalEnsemble:
 
     @property
     def time_step(self):
-        return datetime.timedelta(hours=6)
+        return self._time_step
 
     def __repr__(self) -> str:
         return f"GlobalEnsemble({self.model_names})"

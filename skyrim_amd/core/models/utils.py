@@ -70,6 +70,7 @@ def run_basic_inference(model, n: int, data_source: Any, time: datetime, x=None,
             if hasattr(model, "__dict__"):
                 model._state_is_own_output = True                          # (a TimeLoop that range-checks initial conditions skips its own output)
         else:
+            _check_history_spacing(model, x)
             x = torch.as_tensor(np.asarray(x.values[-model.n_history_levels:]), dtype=torch.float32).to(model.device)
             x = x.unsqueeze(0)
             counters["state_uploads"] = counters.get("state_uploads", 0) + 1
@@ -84,6 +85,25 @@ def run_basic_inference(model, n: int, data_source: Any, time: datetime, x=None,
         if hasattr(loop, "close"):
             loop.close()        # lets the TimeLoop flush its deferred checks (FiniteGuard: the last yielded state) -- may raise; also runs
                                 # when the loop body itself raised, so that a generator is never left to the garbage collector
+
+
+def _check_history_spacing(model, x):
+    """A model whose input levels are spaced differently from its step (``history_time_step``: DLWP) reads the last time entries of an
+    array or file as its levels only if they are that far apart: a saved prediction holds states one STEP apart, not one level apart."""
+    spacing = getattr(model, "history_time_step", None)
+    n = model.n_history_levels
+    if spacing is None or n < 2:
+        return
+    times = getattr(x, "_coords", {}).get("time") if hasattr(x, "_coords") else None
+    if times is None or len(times) < n:
+        raise ValueError(f"this model reads {n} input levels {spacing} apart; the initial condition needs a time coordinate with at least "
+                         f"{n} entries")
+    t = np.asarray(times[-n:]).astype("datetime64[s]")
+    gaps = set(np.diff(t).astype("timedelta64[s]").astype(np.int64).tolist())
+    if gaps != {int(spacing.total_seconds())}:
+        raise ValueError(f"this model reads its last {n} input levels {spacing} apart, but the initial condition's last time entries are "
+                         f"{[str(v) for v in t]}: a saved step of this model holds states {getattr(model, 'time_step', '?')} apart and cannot be "
+                         f"restarted from; pass levels {spacing} apart")
 
 
 def _drain(model, loop, n: int, time, deliver=None, head=None, defer_check=False):
@@ -144,6 +164,9 @@ def _drain(model, loop, n: int, time, deliver=None, head=None, defer_check=False
             def verdict(host_flag=host_flag, step=step, hint=hint):
                 if not bool(host_flag.item()):
                     raise FloatingPointError(f"non-finite values in the state after step {step}: {hint}")
+    history = getattr(model, "history_for", None)
+    if history is not None and last:
+        last = history(last[-1]) or last    # the levels that continue the loop from its last state (DLWP: t + 6 h and t + 12 h)
     if hasattr(loop, "close"):
         loop.close()            # flush BEFORE the result is built: a non-finite last state must not be delivered (deferred: nothing pending)
     ready = image = None

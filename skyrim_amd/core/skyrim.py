@@ -42,6 +42,9 @@ class Skyrim:
         date: YYYYMMDD, time: HHMM, lead_time in hours (clipped down to a multiple of 6, at least 6)."""
         start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
         lead_time = adjust_lead_time(lead_time, step_size=6)
-        n_steps = int(lead_time // (self.model.time_step.total_seconds() / 3600))
+        step_h = self.model.time_step.total_seconds() / 3600
+        n_steps = int(lead_time // step_h)
+        if n_steps < 1:
+            raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {', '.join(self.model_names)}")
         pred, output_paths = self.model.rollout(start_time=start_time, n_steps=n_steps, save=save, save_config=save_config)
         return GlobalPrediction(pred, model_name=self.model_names), output_paths

@@ -105,8 +105,9 @@ def get_initial_condition_for_model(model, data_source, time: datetime.datetime)
     grid = getattr(model, "grid", None)
     n_lat = len(grid.lat) if grid is not None and hasattr(grid, "lat") else None
     arrs = []
+    spacing = getattr(model, "history_time_step", model.time_step)     # DLWP: 6-h levels under a 12-h step
     for k in range(model.n_history_levels - 1, -1, -1):
-        a = np.asarray(data_source[time - k * model.time_step], dtype=np.float32)
+        a = np.asarray(data_source[time - k * spacing], dtype=np.float32)
         if n_lat == 720 and a.ndim >= 2 and a.shape[-2] == 721:
             a = a[..., :720, :]          # 0.25-degree source, grid without the south-pole row (FourCastNet v1): earth2mip drops the last row
         arrs.append(a)

@@ -11,6 +11,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     gc_gather_gemm / gc_linear_layer_norm / gc_sum_linear_layer_norm / gc_layer_norm / gc_segment_sum
     gc_edge_update / gc_segment_fixup / gc_node_mlp      (the fused interaction-network updates, csrc/graphcast_fused.hip)
     fcn_layer_norm / fcn_mlp / fcn_spectral_mlp          (FourCastNet v1, include/skyrim_fcn.h)
+    dlwp_ingest / dlwp_conv / dlwp_egress                (DLWP, include/skyrim_dlwp.h)
 """
 from __future__ import annotations
 
@@ -347,6 +348,79 @@ def _fcn_spectral_mlp(z, w1f, w2f, b1e, b2e, geom: list[int], lam: float) -> Non
         native.check(lib.skfcn_spectral_mlp(ctypes.byref(d), native.stream(z.device)), "skfcn_spectral_mlp", lib)
 
 
+# ---- DLWP ---------------------------------------------------------------------------------------------------------------------- #
+def _dlwp():
+    from .dlwp import engine
+    return engine, engine.load_library()
+
+
+def _i32p(t, what: str, dev):
+    return ctypes.c_void_p(_i32(t, what, dev))
+
+
+def _dlwp_csr(ptr, col, S, rows: int, n_cols_src: int, dev, what: str):
+    if ptr.numel() != rows + 1 or col.numel() != S.numel():
+        raise ValueError(f"{what}: row_ptr must hold rows + 1 entries and col / S one per non-zero")
+    return _i32p(ptr, f"{what}.row_ptr", dev), _i32p(col, f"{what}.col", dev), _f32(S, f"{what}.S", dev)
+
+
+def _dlwp_ingest(x0, x1, center, inv_scale, row_ptr, col, S, lat, lon, statics, days0: float, days1: float, out, channels: int, ld_out: int) -> None:
+    engine, lib = _dlwp()
+    dev = out.device
+    cells = row_ptr.numel() - 1
+    points = x0.numel() // max(channels, 1)
+    if x0.numel() != x1.numel() or x0.numel() != channels * points or out.numel() < cells * ld_out or lat.numel() != cells or lon.numel() != cells \
+            or statics.numel() != 2 * cells or center.numel() != channels or inv_scale.numel() != channels:
+        raise ValueError("dlwp_ingest: tensor sizes do not match channels, the map's rows and ld_out")
+    if col.numel() and int(col.max()) >= points:
+        raise ValueError("dlwp_ingest: map columns outside the state")
+    for t, w in ((lat, "lat"), (lon, "lon")):
+        if t.dtype != torch.float64 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"dlwp_ingest: {w} must be a contiguous float64 tensor on {dev}")
+    rp, cl, sv = _dlwp_csr(row_ptr, col, S, cells, points, dev, "dlwp_ingest")
+    d = engine.IngestDesc(_f32(x0, "x0", dev), _f32(x1, "x1", dev), _f32(center, "center", dev), _f32(inv_scale, "inv_scale", dev), rp, cl, sv,
+                          lat.data_ptr(), lon.data_ptr(), _f32(statics, "statics", dev), days0, days1, _f32(out, "out", dev), channels, cells, points, ld_out)
+    with torch.cuda.device(dev):
+        native.check(lib.skdlwp_ingest(ctypes.byref(d), native.stream(dev)), "skdlwp_ingest", lib)
+
+
+def _dlwp_conv(src0, src1, pad, w, w_plane: int, w_polar: int, ldw: int, bias, out, geom: list[int], slope: float, clamp_max: float) -> None:
+    engine, lib = _dlwp()
+    dev = out.device
+    if len(geom) != 9:
+        raise ValueError("dlwp_conv: geom = [n, c0, c1, mode0, taps, cout, ld_out, act, flip_face]")
+    n, c0, c1, mode0, taps, cout, ld_out, act, flip = geom
+    n0 = {0: n, 1: 2 * n, 2: n // 2}.get(mode0, n)
+    if src0.numel() < 6 * n0 * n0 * c0 or (c1 and (src1 is None or src1.numel() < 6 * n * n * c1)) or out.numel() < 6 * n * n * ld_out \
+            or pad.numel() != 48 or bias.numel() != 2 * cout or w.numel() < w_plane + w_polar + cout * ldw or w_polar < cout * ldw \
+            or w_plane < w_polar + cout * ldw or ldw < taps * (c0 + c1):
+        raise ValueError("dlwp_conv: tensor sizes do not match the geometry")
+    faces, turns = pad.reshape(-1)[0::2], pad.reshape(-1)[1::2]
+    if int(faces.min()) < 0 or int(faces.max()) > 5 or int(turns.min()) < 0 or int(turns.max()) > 3:
+        raise ValueError("dlwp_conv: pad holds (face < 6, quarter turns < 4) pairs")
+    d = engine.ConvDesc(_f32(src0, "src0", dev), _f32(src1, "src1", dev) if src1 is not None else None, _i32p(pad, "pad", dev), _f16(w, "w", dev),
+                        w_plane, w_polar, ldw, _f32(bias, "bias", dev), _f32(out, "out", dev), n, c0, c1, mode0, taps, cout, ld_out, act, flip,
+                        slope, clamp_max)
+    with torch.cuda.device(dev):
+        native.check(lib.skdlwp_conv(ctypes.byref(d), native.stream(dev)), "skdlwp_conv", lib)
+
+
+def _dlwp_egress(y, row_ptr, col, S, center, scale, out6, out12, channels: int, ld_y: int) -> None:
+    engine, lib = _dlwp()
+    dev = y.device
+    points = row_ptr.numel() - 1
+    cells = y.numel() // max(ld_y, 1)
+    if out6.numel() != channels * points or out12.numel() != channels * points or center.numel() != channels or scale.numel() != channels:
+        raise ValueError("dlwp_egress: tensor sizes do not match channels and the map's rows")
+    if col.numel() and int(col.max()) >= cells:
+        raise ValueError("dlwp_egress: map columns outside the cube output")
+    rp, cl, sv = _dlwp_csr(row_ptr, col, S, points, cells, dev, "dlwp_egress")
+    d = engine.EgressDesc(_f32(y, "y", dev), rp, cl, sv, _f32(center, "center", dev), _f32(scale, "scale", dev), _f32(out6, "out6", dev),
+                          _f32(out12, "out12", dev), channels, cells, points, ld_y)
+    with torch.cuda.device(dev):
+        native.check(lib.skdlwp_egress(ctypes.byref(d), native.stream(dev)), "skdlwp_egress", lib)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -377,6 +451,12 @@ _SCHEMAS = [
     ("fcn_mlp(Tensor x, Tensor w1f, Tensor w2f, Tensor b1, Tensor b2, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int C, int hidden, "
      "float eps) -> ()", _fcn_mlp),
     ("fcn_spectral_mlp(Tensor(a!) z, Tensor w1f, Tensor w2f, Tensor b1e, Tensor b2e, int[] geom, float lam) -> ()", _fcn_spectral_mlp),
+    ("dlwp_ingest(Tensor x0, Tensor x1, Tensor center, Tensor inv_scale, Tensor row_ptr, Tensor col, Tensor S, Tensor lat, Tensor lon, "
+     "Tensor statics, float days0, float days1, Tensor(a!) out, int channels, int ld_out) -> ()", _dlwp_ingest),
+    ("dlwp_conv(Tensor src0, Tensor? src1, Tensor pad, Tensor w, int w_plane, int w_polar, int ldw, Tensor bias, Tensor(a!) out, int[] geom, "
+     "float slope, float clamp_max) -> ()", _dlwp_conv),
+    ("dlwp_egress(Tensor y, Tensor row_ptr, Tensor col, Tensor S, Tensor center, Tensor scale, Tensor(a!) out6, Tensor(b!) out12, int channels, "
+     "int ld_y) -> ()", _dlwp_egress),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
