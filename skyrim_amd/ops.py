@@ -12,6 +12,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     gc_edge_update / gc_segment_fixup / gc_node_mlp      (the fused interaction-network updates, csrc/graphcast_fused.hip)
     fcn_layer_norm / fcn_mlp / fcn_spectral_mlp          (FourCastNet v1, include/skyrim_fcn.h)
     dlwp_ingest / dlwp_conv / dlwp_egress                (DLWP, include/skyrim_dlwp.h)
+    fuxi_layer_norm / fuxi_window_attention / fuxi_resample   (FuXi, include/skyrim_fuxi.h)
 """
 from __future__ import annotations
 
@@ -421,6 +422,48 @@ def _dlwp_egress(y, row_ptr, col, S, center, scale, out6, out12, channels: int, 
         native.check(lib.skdlwp_egress(ctypes.byref(d), native.stream(dev)), "skdlwp_egress", lib)
 
 
+# ---- FuXi ---------------------------------------------------------------------------------------------------------------------- #
+def _fuxi():
+    from .fuxi import engine
+    return engine, engine.load_library()
+
+
+def _fuxi_layer_norm(x, res, gamma, beta, out, rows: int, C: int, eps: float) -> None:
+    engine, lib = _fuxi()
+    dev = out.device
+    if x.numel() < rows * C or out.numel() < rows * C or (res is not None and res.numel() < rows * C) or gamma.numel() != C or beta.numel() != C:
+        raise ValueError("fuxi_layer_norm: tensor sizes do not match rows and C")
+    with torch.cuda.device(dev):
+        native.check(lib.skfuxi_layer_norm(_f32(x, "x", dev), _f32(res, "res", dev) if res is not None else None, _f32(gamma, "gamma", dev),
+                                           _f32(beta, "beta", dev), _f32(out, "out", dev), rows, C, eps, native.stream(dev)), "skfuxi_layer_norm", lib)
+
+
+def _fuxi_window_attention(qkv, out, cpb, logit_scale, geom: list[int], mask_value: float, logit_max: float) -> None:
+    engine, lib = _fuxi()
+    dev = out.device
+    if len(geom) != 9:
+        raise ValueError("fuxi_window_attention: geom = [H, W, C, heads, wh, ww, sh, sw, mask_lon]")
+    H, W, C, heads, wh, ww, sh, sw, mlon = geom
+    if qkv.numel() != H * W * 3 * C or out.numel() != H * W * C or cpb.numel() != heads * (2 * wh - 1) * (2 * ww - 1) or logit_scale.numel() != heads:
+        raise ValueError("fuxi_window_attention: tensor sizes do not match the geometry")
+    d = engine.AttnDesc(_f32(qkv, "qkv", dev), _f32(out, "out", dev), _f32(cpb, "cpb", dev), _f32(logit_scale, "logit_scale", dev), H, W, C, heads,
+                        wh, ww, sh, sw, mlon, mask_value, logit_max, 1e-12)
+    with torch.cuda.device(dev):
+        native.check(lib.skfuxi_window_attention(ctypes.byref(d), native.stream(dev)), "skfuxi_window_attention", lib)
+
+
+def _fuxi_resample(src, mean, std, out, h_src: int, w_src: int, h_out: int, w_out: int, align_corners: bool) -> None:
+    engine, lib = _fuxi()
+    dev = out.device
+    ch = mean.numel()
+    if src.numel() != ch * h_src * w_src or out.numel() != ch * h_out * w_out or std.numel() != ch:
+        raise ValueError("fuxi_resample: tensor sizes do not match the geometry")
+    d = engine.ResampleDesc(_f32(src, "src", dev), _f32(mean, "mean", dev), _f32(std, "std", dev), _f32(out, "out", dev), ch, h_src, w_src, h_out, w_out,
+                            int(align_corners))
+    with torch.cuda.device(dev):
+        native.check(lib.skfuxi_resample(ctypes.byref(d), native.stream(dev)), "skfuxi_resample", lib)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -457,6 +500,11 @@ _SCHEMAS = [
      "float slope, float clamp_max) -> ()", _dlwp_conv),
     ("dlwp_egress(Tensor y, Tensor row_ptr, Tensor col, Tensor S, Tensor center, Tensor scale, Tensor(a!) out6, Tensor(b!) out12, int channels, "
      "int ld_y) -> ()", _dlwp_egress),
+    ("fuxi_layer_norm(Tensor x, Tensor? res, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int C, float eps) -> ()", _fuxi_layer_norm),
+    ("fuxi_window_attention(Tensor qkv, Tensor(a!) out, Tensor cpb, Tensor logit_scale, int[] geom, float mask_value, float logit_max) -> ()",
+     _fuxi_window_attention),
+    ("fuxi_resample(Tensor src, Tensor mean, Tensor std, Tensor(a!) out, int h_src, int w_src, int h_out, int w_out, bool align_corners) -> ()",
+     _fuxi_resample),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 

@@ -82,15 +82,18 @@ class Initializer:
     raw: object = None            # memoryview of raw_data, or None
     typed: list = field(default_factory=list)      # (field_no, wire_type, payload) of float_data / int32_data / int64_data / double_data
     external: dict = field(default_factory=dict)
+    base_dir: object = None       # opt-in (read_model(..., base_dir=)): the directory external_data locations are relative to
 
     def array(self) -> np.ndarray:
-        if self.external:
+        if self.external and self.base_dir is None:
             raise ValueError(f"{self.name}: external_data initializers are not supported (re-export with raw data)")
         dt = _DTYPES.get(self.dtype)
         if dt is None:
             raise ValueError(f"{self.name}: unsupported ONNX data type {self.dtype}")
         n = int(np.prod(self.dims)) if self.dims else 1
-        if self.raw is not None:
+        if self.external:
+            a = self._external(np.dtype(dt).newbyteorder("<"), n)
+        elif self.raw is not None:
             a = np.frombuffer(self.raw, dtype=np.dtype(dt).newbyteorder("<"), count=n)
         else:
             parts = []
@@ -107,6 +110,22 @@ class Initializer:
         if a.size != n:
             raise ValueError(f"{self.name}: {a.size} elements for shape {self.dims}")
         return a.reshape(self.dims)
+
+    def _external(self, dt: np.dtype, n: int) -> np.ndarray:
+        """The tensor's bytes from its external-data file (location relative to ``base_dir``, optional offset / length)."""
+        import os
+        loc = self.external.get("location", "")
+        base = os.path.realpath(os.fspath(self.base_dir))
+        path = os.path.realpath(os.path.join(base, loc))
+        if not loc or os.path.commonpath([base, path]) != base or not os.path.isfile(path):
+            raise ValueError(f"{self.name}: external_data location {loc!r} is not a file inside {base}")
+        off = int(self.external.get("offset", 0) or 0)
+        length = int(self.external.get("length", 0) or 0) or n * dt.itemsize
+        if length != n * dt.itemsize:
+            raise ValueError(f"{self.name}: external_data length {length} bytes for {n} elements of {dt.name}")
+        if off < 0 or off + length > os.path.getsize(path):
+            raise ValueError(f"{self.name}: external_data [{off}, {off + length}) outside {path}")
+        return np.fromfile(path, dtype=dt, count=n, offset=off)
 
 
 @dataclass
@@ -170,8 +189,9 @@ def _parse_node(buf) -> Node:
     return nd
 
 
-def read_model(path) -> Model:
-    """ModelProto (field 7 = graph) -> GraphProto (1 = node, 5 = initializer)."""
+def read_model(path, base_dir=None) -> Model:
+    """ModelProto (field 7 = graph) -> GraphProto (1 = node, 5 = initializer).  ``base_dir``: opt-in to initializers stored as
+    external data (files relative to that directory); without it such an initializer is refused when read."""
     f = open(path, "rb")
     mm = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
     buf = memoryview(mm)
@@ -181,6 +201,7 @@ def read_model(path) -> Model:
             for gno, gwt, gval in _fields(val):
                 if gno == 5 and gwt == 2:
                     t = _parse_tensor(gval)
+                    t.base_dir = base_dir
                     inits[t.name] = t
                 elif gno == 1 and gwt == 2:
                     nodes.append(_parse_node(gval))
@@ -231,7 +252,11 @@ def auto_map(model: Model, geom: PanguGeometry, window: int = 16) -> tuple[dict,
     """Best-effort {slot: [onnx_name, transform]}: walk the initializers in order of use and give each to the earliest
     still-empty slot (looking at most ``window`` slots ahead of the first empty one) that its shape can fill.  Returns the
     mapping and the list of unresolved slots.  Float tensors only; scalars and shape constants are skipped."""
-    slots = param_spec(geom)
+    return auto_map_slots(model, param_spec(geom), window)
+
+
+def auto_map_slots(model: Model, slots: list, window: int = 16) -> tuple[dict, list]:
+    """``auto_map`` over any list of (slot, shape) in order of use."""
     mapping, taken = {}, [False] * len(slots)
     first = 0
     for t, op in model.in_order_of_use():
