@@ -13,6 +13,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     fcn_layer_norm / fcn_mlp / fcn_spectral_mlp          (FourCastNet v1, include/skyrim_fcn.h)
     dlwp_ingest / dlwp_conv / dlwp_egress                (DLWP, include/skyrim_dlwp.h)
     fuxi_layer_norm / fuxi_window_attention / fuxi_resample   (FuXi, include/skyrim_fuxi.h)
+    fengwu_layer_norm / fengwu_window_attention             (FengWu, include/skyrim_fengwu.h)
 """
 from __future__ import annotations
 
@@ -464,6 +465,42 @@ def _fuxi_resample(src, mean, std, out, h_src: int, w_src: int, h_out: int, w_ou
         native.check(lib.skfuxi_resample(ctypes.byref(d), native.stream(dev)), "skfuxi_resample", lib)
 
 
+# ---- FengWu -------------------------------------------------------------------------------------------------------------------- #
+def _fengwu():
+    from .fengwu import engine
+    return engine, engine.load_library()
+
+
+def _fengwu_layer_norm(x, gamma, beta, out, rows: int, batch: int, C: int, eps: float) -> None:
+    engine, lib = _fengwu()
+    dev = out.device
+    if x.numel() < batch * rows * C or out.numel() < batch * rows * C or gamma.numel() != batch * C or beta.numel() != batch * C:
+        raise ValueError("fengwu_layer_norm: tensor sizes do not match rows, batch and C")
+    d = engine.LnDesc(_f32(x, "x", dev).value, _f32(gamma, "gamma", dev).value, _f32(beta, "beta", dev).value, _f32(out, "out", dev).value,
+                      rows, batch, C, 0, 0, 0, 0, eps)
+    with torch.cuda.device(dev):
+        native.check(lib.skfw_layer_norm(ctypes.byref(d), native.stream(dev)), "skfw_layer_norm", lib)
+
+
+def _fengwu_window_attention(qkv, qkv_bias, table, out, geom: list[int], scale: float) -> None:
+    """geom = [batch, Z, H, W, Zp, Hp, Wp, fz, fh, fw, wz, wh, ww, sz, sh, sw, types_z, types_y, C, heads] (include/skyrim_fengwu.h)."""
+    engine, lib = _fengwu()
+    dev = out.device
+    if len(geom) != 20:
+        raise ValueError("fengwu_window_attention: geom = [batch, Z, H, W, Zp, Hp, Wp, fz, fh, fw, wz, wh, ww, sz, sh, sw, types_z, types_y, C, heads]")
+    batch, Z, H, W = geom[:4]
+    wz, wh, ww = geom[10:13]
+    tz, ty, C, heads = geom[16:]
+    N = wz * wh * ww
+    tsb = tz * ty * heads * N * N
+    if qkv.numel() != batch * Z * H * W * 3 * C or out.numel() != batch * Z * H * W * C or qkv_bias.numel() != batch * 3 * C or table.numel() != batch * tsb:
+        raise ValueError("fengwu_window_attention: tensor sizes do not match the geometry")
+    d = engine.AttnDesc(_f32(qkv, "qkv", dev).value, _f32(qkv_bias, "qkv_bias", dev).value, _f32(table, "table", dev).value, _f32(out, "out", dev).value,
+                        tsb, *geom, scale)
+    with torch.cuda.device(dev):
+        native.check(lib.skfw_window_attention(ctypes.byref(d), native.stream(dev)), "skfw_window_attention", lib)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -505,6 +542,8 @@ _SCHEMAS = [
      _fuxi_window_attention),
     ("fuxi_resample(Tensor src, Tensor mean, Tensor std, Tensor(a!) out, int h_src, int w_src, int h_out, int w_out, bool align_corners) -> ()",
      _fuxi_resample),
+    ("fengwu_layer_norm(Tensor x, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int batch, int C, float eps) -> ()", _fengwu_layer_norm),
+    ("fengwu_window_attention(Tensor qkv, Tensor qkv_bias, Tensor table, Tensor(a!) out, int[] geom, float scale) -> ()", _fengwu_window_attention),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
