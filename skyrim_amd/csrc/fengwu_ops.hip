@@ -297,6 +297,9 @@ __device__ __forceinline__ void split_v8(const float (&v)[8], v8& h, v8& l) {
     l = as_v8<f16>(o[1]);
 }
 
+// P's scale before its fp16 split: p <= 1 stays below the fp16 maximum, and the lo plane of p >= 2^-18 stays normal
+constexpr float kPScale = 32768.0f;
+
 __device__ __forceinline__ f32x4 mfma3(const v8& ah, const v8& al, const v8& bh, const v8& bl, f32x4 c) {
     c = OpT<f16>::mfma(al, bh, c);
     c = OpT<f16>::mfma(ah, bl, c);
@@ -390,9 +393,16 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const skfw_attn_desc d
             p[i] = p[i] == -INFINITY ? 0.f : expf(p[i] - mn);
             lsum += p[i];
         }
-        // P^T as the B operand: k-slot (g, j) <-> key k0 + (j < 4 ? 4 g + j : 16 + 4 g + j - 4), exactly this lane's p[j]
+        // P^T as the B operand: k-slot (g, j) <-> key k0 + (j < 4 ? 4 g + j : 16 + 4 g + j - 4), exactly this lane's p[j], scaled by
+        // kPScale before the split (1/kPScale is folded into 1/lsum): unscaled, a p below 2^-3 leaves a subnormal lo plane that keeps
+        // only multiples of 2^-24, and over a sharp softmax of many keys those losses add up
         v8 ph, pl;
-        split_v8(p, ph, pl);
+        {
+            float ps[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ps[i] = p[i] * kPScale;
+            split_v8(ps, ph, pl);
+        }
         const float* vp[8];
         bool vok[8];
 #pragma unroll
@@ -415,7 +425,7 @@ __global__ void __launch_bounds__(256) window_attn_kernel(const skfw_attn_desc d
     lsum += __shfl_xor(lsum, 16);
     lsum += __shfl_xor(lsum, 32);
     if (q0 + l15 >= N || tq < 0) return;
-    const float inv = 1.0f / lsum;
+    const float inv = (1.0f / lsum) * (1.0f / kPScale);
     // o[db][r] = O[q0 + l15][16 db + 4 g + r]
     float* op = d.out + (bt * ntok + tq) * d.C + head * kHd + 4 * g;
 #pragma unroll
