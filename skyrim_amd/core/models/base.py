@@ -113,6 +113,21 @@ class GlobalModel:
         da = run_basic_inference(model=self.model, n=n_steps, data_source=self.data_source, time=start_time, x=None)
         return da.sel(channel=channels) if channels else da
 
+    def ensemble_forecast(self, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3,
+                          seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
+                          channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
+                          save_config: dict | None = None):
+        """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
+        starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
+        own TimeLoop generator, and at each lead time one HIP pass over the members gives the ``products`` (any of mean, spread, min, max),
+        the exceedance fractions ``exceed = {channel: [thresholds]}`` and the quantiles ``quantiles = {channel: [levels]}`` (at most 4
+        values per channel).  Returns an ``ensemble.EnsembleForecast``; its time axis holds the initial condition and every
+        ``save_every``-th step.  ``save=True`` writes one file per product and saved step, model field ``{model}-ens{M}-{product}``."""
+        from ... import ensemble
+        return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
+                            exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
+                            save=save, save_config=save_config)
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):
         """Final prediction (2 time entries) + the paths of the per-step files.

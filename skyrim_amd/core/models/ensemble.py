@@ -89,6 +89,10 @@ class GlobalEnsemble:
         """Subclasses should implement this method."""
         raise NotImplementedError
 
+    def ensemble_forecast(self, *args, **kwargs):
+        raise ValueError(f"ensemble_forecast perturbs the initial condition of ONE model; {self!r} is a multi-model ensemble -- build "
+                         "Skyrim(<one model name>) for a perturbed-IC ensemble, or use rollout for the multi-model mean")
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None):
         """Roll every member out, one at a time; returns (mean of the members' final predictions over the shared channels, paths of the per-step
         ensemble-mean files -- ``[]`` with ``save=False``).  The members' own per-step files stay where ``GlobalModel.rollout`` wrote them

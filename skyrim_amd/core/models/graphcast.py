@@ -117,6 +117,10 @@ class GraphcastModel(GlobalModel):
             logger.info(f"Forecast step {n + 1}/{n_steps} completed")
         return concat(parts, dim="time").assign_coords(time=times)
 
+    def ensemble_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper (initialize / step on a (time, Dataset, rng) state), not through "
+                                  "the TimeLoop generators ensemble_forecast interleaves; perturbed-IC ensembles cover the other six models")
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):
         """Final two time levels + per-step file paths; the stepper state is fed back step to step (never through a file).

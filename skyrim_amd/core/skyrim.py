@@ -37,6 +37,12 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.forecast(start_time=start_time, n_steps=n_steps, channels=channels or [])
 
+    def ensemble_forecast(self, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, **kwargs):
+        """Perturbed-initial-condition ensemble of the single model (``GlobalModel.ensemble_forecast`` has the arguments): the ensemble
+        mean / spread / min / max, exceedance fractions and quantiles at every lead time, as an ``EnsembleForecast``."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.ensemble_forecast(start_time, n_steps=n_steps, n_members=n_members, **kwargs)
+
     def predict(self, date: str, time: str, lead_time: int = 6, save: bool = False, save_config: dict | None = None):
         """Predict a single lead-time snapshot, optionally saving every intermediate step.
         date: YYYYMMDD, time: HHMM, lead_time in hours (clipped down to a multiple of 6, at least 6)."""

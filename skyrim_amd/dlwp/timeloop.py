@@ -31,6 +31,7 @@ class DlwpTimeLoop(EngineTimeLoop):
         if params is None:
             params = weights.resolve("SKYRIM_DLWP_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed), "dlwp")
         self.engine.load_params(params)
+        self.channel_std = torch.as_tensor(params["scale"]).float().reshape(-1)       # DLWP's own scaling constants: the scale of a perturbed ensemble member
         self._channels(CHANNELS, self.cfg.channels)
         lat, lon = latlon_axes(self.cfg)
         self.grid = Grid(list(lat), list(lon))
@@ -59,11 +60,11 @@ class DlwpTimeLoop(EngineTimeLoop):
         p = self.guard.take()
         return None if p is None else (p[0], p[1], self.guard.hint)
 
-    def _yield(self, time, older, newer, step, restart):
+    def _yield(self, time, older, newer, step, restart, guard):
         out = newer.unsqueeze(0)
         self._history = (out, [older.unsqueeze(0), out])
         if step > 0:
-            self.guard.push(newer, step)
+            guard.push(newer, step)
         return time, out, restart
 
     def __call__(self, time: datetime.datetime, x: torch.Tensor, restart=None):
@@ -72,14 +73,16 @@ class DlwpTimeLoop(EngineTimeLoop):
             raise ValueError(f"expected x of shape {shape} (states at time - 6 h and time), got {tuple(x.shape)}")
         x = x.to(self.device, torch.float32)
         older, newer = x[0, 0].contiguous().clone(), x[0, 1].contiguous().clone()
-        self.guard.pending = None
+        # the deferred check belongs to THIS generator (several may be open at once: skyrim_amd/ensemble.py interleaves one per member);
+        # ``self.guard`` names the one opened last, which is the one take_pending_check's caller is draining
+        guard = self.guard = weights.FiniteGuard(self.guard.hint)
         step = 0
         try:
-            yield self._yield(time, older, newer, step, restart)
+            yield self._yield(time, older, newer, step, restart, guard)
             while True:
                 older, newer = self.engine.call(older, newer, time)
                 time = time + self.time_step
                 step += 1
-                yield self._yield(time, older, newer, step, restart)
+                yield self._yield(time, older, newer, step, restart, guard)
         finally:
-            self.guard.check()
+            guard.check()

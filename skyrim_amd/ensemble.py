@@ -1,0 +1,329 @@
+"""Perturbed-initial-condition ensembles of ONE model (include/skyrim_ens.h).
+
+Three layers:
+
+* the binding of libskyrim_ens.so (``SPEC``, ``load_library``, ``perturb``, ``stats``, ``member_table``); the same calls are
+  ``torch.ops.skyrim_hip.ens_perturb / ens_stats`` (skyrim_amd/ops.py);
+* ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb``, ONE TimeLoop
+  generator per member advanced step-major (all members one step, then the statistics of that lead time), so only the members'
+  current states are alive on the GPU;
+* ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
+
+Members sharded over ranks stay with ``skyrim_amd/pangu/ensemble.py``; multi-MODEL ensembles are ``core/models/ensemble.py``.
+"""
+from __future__ import annotations
+
+import ctypes
+import datetime
+import math
+from dataclasses import dataclass, field
+
+import numpy as np
+import torch
+
+from . import native
+
+MAX_MEMBERS, MAX_THRESHOLDS, MAX_QUANTILES = 64, 4, 4          # include/skyrim_ens.h SKENS_MAX_*
+PRODUCTS = ("mean", "spread", "min", "max")
+_P = ctypes.c_void_p
+
+
+class StatsDesc(ctypes.Structure):
+    """skens_stats_desc."""
+    _fields_ = [("members", _P), ("M", ctypes.c_int), ("member_align", ctypes.c_int), ("offset", ctypes.c_size_t), ("n", ctypes.c_size_t),
+                ("mean", _P), ("spread", _P), ("min", _P), ("max", _P), ("exceed", _P), ("n_thr", ctypes.c_int),
+                ("thr", ctypes.c_float * MAX_THRESHOLDS), ("quant", _P), ("n_quant", ctypes.c_int),
+                ("q_index", ctypes.c_int * MAX_QUANTILES), ("q_frac", ctypes.c_float * MAX_QUANTILES)]
+
+
+SPEC = native.Spec("skyrim_ens", "SKYRIM_ENS_LIB", "skens", 1, {               # include/skyrim_ens.h SKENS_ABI_VERSION
+    "skens_abi_version": (ctypes.c_int, []),
+    "skens_perturb": (ctypes.c_int, [_P, _P, _P, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint32,
+                                     ctypes.c_uint32, ctypes.c_int, _P]),
+    "skens_stats": (ctypes.c_int, [ctypes.POINTER(StatsDesc), _P]),
+}, " -- ensemble members and statistics have no torch fallback")
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+_lib = None
+
+
+def load_library() -> ctypes.CDLL:
+    """libskyrim_ens.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
+    global _lib
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
+
+
+def quantile_position(level: float, M: int) -> tuple[int, float]:
+    """(index, fraction) of numpy's "linear" quantile of M sorted values: h = (M - 1) * level in double; the fraction is what the kernel
+    multiplies with in fp32, so a fraction that rounds up to 1 there becomes the next index."""
+    if not (0.0 <= level <= 1.0):
+        raise ValueError(f"quantile level {level} is outside [0, 1]")
+    h = (M - 1) * float(level)
+    k = min(int(math.floor(h)), M - 1)
+    f = float(np.float32(h - k))
+    if f >= 1.0:
+        k, f = k + 1, 0.0
+    if k >= M - 1:
+        k, f = M - 1, 0.0
+    return k, f
+
+
+def _dev_f32(t, what: str, dev=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError(f"{what}: expected a contiguous float32 tensor on {dev or 'the GPU'}")
+    return t.data_ptr()
+
+
+def perturb(x0: torch.Tensor, std: torch.Tensor, out: torch.Tensor, chan_stride: int, scale: float, seed: int, member_first: int) -> None:
+    """``out`` (``k * x0.numel()`` elements: members ``member_first .. member_first + k - 1``, one after the other) from the flat
+    (L, C, H, W) state ``x0`` and the C per-channel sigmas ``std``; ``chan_stride`` = H * W.  Queued on torch's current stream."""
+    dev = x0.device
+    px, ps, po = _dev_f32(x0, "ens_perturb: x0"), _dev_f32(std, "ens_perturb: std", dev), _dev_f32(out, "ens_perturb: out", dev)
+    n = x0.numel()
+    if n == 0 or out.numel() % n or out.numel() == 0:
+        raise ValueError(f"ens_perturb: out holds {out.numel()} elements, not a multiple of the state's {n}")
+    if not (0 <= seed < 2 ** 32 and 0 <= member_first < 2 ** 32):
+        raise ValueError("ens_perturb: seed and member are 32-bit (the generator's key)")
+    lib = load_library()
+    with torch.cuda.device(dev):
+        native.check(lib.skens_perturb(px, ps, po, n, chan_stride, std.numel(), scale, seed, member_first, out.numel() // n, native.stream(dev)),
+                     "skens_perturb", lib)
+
+
+def member_table(members) -> torch.Tensor:
+    """The device array of member pointers ``stats`` reads (one small upload; keep it while the members keep their storage)."""
+    return torch.tensor([t.data_ptr() for t in members], dtype=torch.int64).to(members[0].device)
+
+
+def stats(members, table: torch.Tensor, offset: int, n: int, mean=None, spread=None, min=None, max=None, exceed=None, thresholds=(),
+          quant=None, levels=()) -> None:
+    """One pass over the flat range [offset, offset + n) of the M ``members`` (equal-sized contiguous float32 device tensors; ``table`` =
+    ``member_table(members)``): the outputs that are not None are written at range-relative positions -- ``mean / spread / min / max``: n
+    elements, ``exceed``: len(thresholds) x n, ``quant``: len(levels) x n.  Queued on torch's current stream."""
+    M = len(members)
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"ens_stats: {M} members; 1 to {MAX_MEMBERS} are supported")
+    dev = members[0].device
+    align = 16
+    for t in members:
+        if _dev_f32(t, "ens_stats: member", dev) % 16:
+            align = 4
+        if t.numel() < offset + n:
+            raise ValueError(f"ens_stats: a member holds {t.numel()} elements, the range ends at {offset + n}")
+    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
+        raise ValueError("ens_stats: table must be member_table(members)")
+    if offset < 0 or n < 0 or len(thresholds) > MAX_THRESHOLDS or len(levels) > MAX_QUANTILES:
+        raise ValueError(f"ens_stats: at most {MAX_THRESHOLDS} thresholds and {MAX_QUANTILES} quantile levels, a non-negative range")
+    if (exceed is None) != (len(thresholds) == 0) or (quant is None) != (len(levels) == 0):
+        raise ValueError("ens_stats: exceed goes with thresholds, quant with levels")
+    d = StatsDesc()
+    d.members, d.M, d.member_align, d.offset, d.n = table.data_ptr(), M, align, offset, n
+    for name, t, rows in (("mean", mean, 1), ("spread", spread, 1), ("min", min, 1), ("max", max, 1), ("exceed", exceed, len(thresholds)),
+                          ("quant", quant, len(levels))):
+        if t is not None:
+            if _dev_f32(t, f"ens_stats: {name}", dev) and t.numel() != rows * n:
+                raise ValueError(f"ens_stats: {name} holds {t.numel()} elements, expected {rows * n}")
+            setattr(d, name, t.data_ptr())
+    d.n_thr, d.n_quant = len(thresholds), len(levels)
+    for k, v in enumerate(thresholds):
+        d.thr[k] = float(v)
+    for k, v in enumerate(levels):
+        d.q_index[k], d.q_frac[k] = quantile_position(v, M)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        native.check(lib.skens_stats(ctypes.byref(d), native.stream(dev)), "skens_stats", lib)
+
+
+# ---- the driver ---------------------------------------------------------------------------------------------------------------------- #
+@dataclass
+class EnsembleForecast:
+    """What ``ensemble_forecast`` returns.  ``mean / spread / min / max``: DataArray(time, channel, lat, lon) or None when not asked
+    for; ``exceedance[channel]``: (time, threshold, lat, lon) -- the fraction of members above each threshold; ``quantile[channel]``:
+    (time, quantile, lat, lon); ``members``: (member, time, channel, lat, lon) with ``keep_members=True``; ``paths``: the files written."""
+    model_name: str
+    n_members: int
+    seed: int
+    perturb_scale: float
+    mean: object = None
+    spread: object = None
+    min: object = None
+    max: object = None
+    exceedance: dict = field(default_factory=dict)
+    quantile: dict = field(default_factory=dict)
+    members: object = None
+    paths: list = field(default_factory=list)
+    forecast_id: str = ""
+
+
+def product_model_name(model_name: str, n_members: int, product: str) -> str:
+    """The model field of a product's file name: ``{model}-ens{M}-{product}`` (no ``__``, so the name still splits into its four parts)."""
+    return f"{model_name}-ens{n_members}-{product}"
+
+
+def channel_std(model) -> torch.Tensor:
+    """The per-channel sigma of ``model``'s input channels that scales the perturbation: the TimeLoop's ``channel_std``."""
+    std = getattr(model, "channel_std", None)
+    if std is None:
+        raise NotImplementedError(f"{type(model).__name__} has no channel_std: perturbed members need the model's per-channel scale")
+    return std.to(model.device, torch.float32).reshape(-1).contiguous()
+
+
+def _world_size() -> int:
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members):
+    """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised."""
+    from .core.models.utils import _PINNED_LIMIT
+    if _world_size() > 1:
+        raise NotImplementedError("ensemble_forecast runs all members on one GPU; under a process group of more than one rank use "
+                                  "skyrim_amd.pangu.ensemble.MemberParallelEnsemble (members sharded over ranks)")
+    if not 1 <= int(n_members) <= MAX_MEMBERS:
+        raise ValueError(f"n_members = {n_members}: 1 to {MAX_MEMBERS} members are supported (SKENS_MAX_MEMBERS)")
+    if n_steps < 0 or save_every < 1:
+        raise ValueError("n_steps >= 0 and save_every >= 1")
+    if not 0 <= int(seed) < 2 ** 32:
+        raise ValueError("seed is a 32-bit unsigned integer (the generator's key)")
+    products = tuple(products)
+    unknown = [p for p in products if p not in PRODUCTS]
+    if unknown:
+        raise ValueError(f"unknown products {unknown}; choose from {PRODUCTS}")
+    names = list(model.out_channel_names)
+    for what, table, cap in (("exceed", exceed, MAX_THRESHOLDS), ("quantiles", quantiles, MAX_QUANTILES)):
+        for ch, vals in (table or {}).items():
+            if ch not in names:
+                raise ValueError(f"{what}: channel {ch!r} is not an output channel of this model")
+            if not 1 <= len(vals) <= cap:
+                raise ValueError(f"{what}[{ch!r}]: 1 to {cap} values per channel, got {len(vals)}")
+    for ch, vals in (quantiles or {}).items():
+        for q in vals:
+            quantile_position(q, int(n_members))
+    missing = [c for c in (channels or []) if c not in names]
+    if missing:
+        raise ValueError(f"channels {missing} are not output channels of this model")
+    saved = list(range(0, n_steps + 1, save_every))
+    if keep_members:
+        need = int(n_members) * len(saved) * len(names) * len(model.grid.lat) * len(model.grid.lon) * 4
+        if need > _PINNED_LIMIT:
+            raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
+                             f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every")
+    return (products, {k: [float(np.float32(v)) for v in vs] for k, vs in (exceed or {}).items()},
+            {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}, saved)
+
+
+def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
+        products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
+        save: bool = False, save_config: dict | None = None) -> EnsembleForecast:
+    """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
+    from .common import generate_forecast_id, save_forecast
+    from .datasource import get_initial_condition_for_model
+    from .labeled import DataArray
+    model = gm.model
+    products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
+                                                  keep_members)
+    M = int(n_members)
+    names = list(model.out_channel_names)
+    n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
+    hw = n_lat * n_lon
+    x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
+    dev = x0.device
+    if dev.type != "cuda":
+        raise RuntimeError("ensemble_forecast makes and reduces its members with HIP kernels: the model must be on a GPU")
+    if hasattr(model, "__dict__"):
+        model._resident_state = None                       # the interleaved loops below are not a state a later rollout continues from
+    std = channel_std(model)
+    if std.numel() != x0.shape[2]:
+        raise ValueError(f"channel_std holds {std.numel()} values for {x0.shape[2]} input channels")
+    cfg = dict(save_config or {})
+    cfg.setdefault("forecast_id", generate_forecast_id())
+    if save_config is not None:
+        save_config["forecast_id"] = cfg["forecast_id"]
+    fid = cfg["forecast_id"]
+    zarr = (cfg.get("file_type") or "netcdf") == "zarr"
+
+    loops = []
+    for m in range(M):
+        xm = torch.empty_like(x0)
+        perturb(x0, std, xm, hw, float(perturb_scale), int(seed), m)
+        loops.append(model(start_time, xm))
+        del xm
+    del x0
+    n_saved, C = len(saved), len(names)
+    host = {p: np.empty((n_saved, C, n_lat, n_lon), np.float32) for p in products}
+    host_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in exceed.items()}
+    host_q = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in quantiles.items()}
+    host_members = np.empty((M, n_saved, C, n_lat, n_lon), np.float32) if keep_members else None
+    dev_out = {p: torch.empty((C, n_lat, n_lon), dtype=torch.float32, device=dev) for p in set(products) | {"mean"}}
+    dev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in exceed.items()}
+    dev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in quantiles.items()}
+    times, paths, source = [], [], gm.source_label
+    try:
+        for k in range(n_steps + 1):
+            states, time = [], None
+            for m, loop in enumerate(loops):
+                try:
+                    time, out, _ = next(loop)
+                except FloatingPointError as e:
+                    raise FloatingPointError(f"ensemble member {m}, step {k}: {e}") from e
+                states.append((out[0] if out.dim() == 4 else out).contiguous())
+            table = member_table(states)
+            keep = k in saved
+            want = {p: dev_out[p] for p in (products if keep else ())}
+            want["mean"] = dev_out["mean"]                 # every step: a non-finite member makes the mean non-finite, one flag to read
+            stats(states, table, 0, C * hw, **want)
+            if not bool(torch.isfinite(dev_out["mean"]).all().item()):
+                bad = [m for m, s in enumerate(states) if not bool(torch.isfinite(s).all().item())]
+                raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {k}")
+            if keep:
+                s = saved.index(k)
+                times.append(time)
+                for ch, thr in exceed.items():
+                    stats(states, table, names.index(ch) * hw, hw, exceed=dev_ex[ch], thresholds=thr)
+                    host_ex[ch][s] = dev_ex[ch].cpu().numpy()
+                for ch, lev in quantiles.items():
+                    stats(states, table, names.index(ch) * hw, hw, quant=dev_q[ch], levels=lev)
+                    host_q[ch][s] = dev_q[ch].cpu().numpy()
+                for p in products:
+                    host[p][s] = dev_out[p].cpu().numpy()
+                if keep_members:
+                    for m, st in enumerate(states):
+                        host_members[m, s] = st.cpu().numpy()
+                if save and s >= 1:
+                    for p in products:
+                        da = DataArray(host[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
+                                       dict(time=times[s - 1:s + 1], channel=names, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
+                        name = product_model_name(gm.model_name, M, p)
+                        pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg      # one zarr store per product, appended along time
+                        paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
+                    source = "file"
+            del states, table
+    finally:
+        for loop in loops:
+            try:
+                loop.close()
+            except FloatingPointError:
+                pass                                       # every delivered step was checked above, by member
+        if hasattr(model, "__dict__"):
+            model._resident_state = None
+            model.__dict__.pop("_state_is_own_output", None)
+
+    grid = dict(lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon))
+
+    def labelled(arr, dim, labels):
+        da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **grid))
+        return da.sel(channel=list(channels)) if channels and dim == "channel" else da
+
+    ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid)
+    for p in products:
+        setattr(ens, p, labelled(host[p], "channel", names))
+    ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
+    ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
+    if keep_members:
+        ens.members = DataArray(host_members, ["member", "time", "channel", "lat", "lon"],
+                                dict(member=np.arange(M), time=times, channel=names, **grid))
+        if channels:
+            ens.members = ens.members.sel(channel=list(channels))
+    return ens

@@ -25,6 +25,7 @@ class FcnTimeLoop(EngineTimeLoop):
         if params is None:
             params = weights.resolve("SKYRIM_FCN_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed), "fourcastnet")
         self.engine.load_params(params)
+        self.channel_std = torch.as_tensor(params["norm.std"]).float().reshape(-1)    # the scale of a perturbed ensemble member (skyrim_amd/ensemble.py)
         self._channels(CHANNELS, self.cfg.in_chans, self.cfg.out_chans)
         step = 180.0 / (self.cfg.n_lat if self.cfg.n_lat % 2 == 0 else self.cfg.n_lat - 1)
         # 90, 89.75, ..., -89.75 at full size: no south-pole row

@@ -31,6 +31,7 @@ class FuxiTimeLoop(EngineTimeLoop):
         if params is None:
             params = weights.resolve("SKYRIM_FUXI_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed, self.engine.device), "fuxi")
         self.engine.load_params(params)
+        self.channel_std = torch.as_tensor(params["norm.std"]).float().reshape(-1)    # the scale of a perturbed ensemble member (skyrim_amd/ensemble.py)
         self._channels(CHANNELS, self.cfg.channels)
         lat, lon = latlon_axes(self.cfg)
         self.grid = Grid(list(lat), list(lon))
@@ -54,11 +55,11 @@ class FuxiTimeLoop(EngineTimeLoop):
         p = self.guard.take()
         return None if p is None else (p[0], p[1], self.guard.hint)
 
-    def _yield(self, time, state, step, restart):
+    def _yield(self, time, state, step, restart, guard):
         out = state.unsqueeze(0)
         self._last = (out, step)
         if step > 0:
-            self.guard.push(state, step)
+            guard.push(state, step)
         return time, out, restart
 
     def __call__(self, time: datetime.datetime, x: torch.Tensor, restart=None):
@@ -69,13 +70,15 @@ class FuxiTimeLoop(EngineTimeLoop):
         step = self._last[1] if own else 0
         x = x.to(self.device, torch.float32)
         older, newer = x[0, 0].contiguous().clone(), x[0, 1].contiguous().clone()
-        self.guard.pending = None
+        # the deferred check belongs to THIS generator (several may be open at once: skyrim_amd/ensemble.py interleaves one per member);
+        # ``self.guard`` names the one opened last, which is the one take_pending_check's caller is draining
+        guard = self.guard = weights.FiniteGuard(self.guard.hint)
         try:
-            yield self._yield(time, newer, step, restart)
+            yield self._yield(time, newer, step, restart, guard)
             while True:
                 step += 1
                 older, newer = newer, self.engine.call(older, newer, time, self.stage_for(step))
                 time = time + self.time_step
-                yield self._yield(time, newer, step, restart)
+                yield self._yield(time, newer, step, restart, guard)
         finally:
-            self.guard.check()
+            guard.check()

@@ -14,6 +14,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     dlwp_ingest / dlwp_conv / dlwp_egress                (DLWP, include/skyrim_dlwp.h)
     fuxi_layer_norm / fuxi_window_attention / fuxi_resample   (FuXi, include/skyrim_fuxi.h)
     fengwu_layer_norm / fengwu_window_attention             (FengWu, include/skyrim_fengwu.h)
+    ens_perturb / ens_stats                              (ensemble members and statistics, include/skyrim_ens.h)
 """
 from __future__ import annotations
 
@@ -501,6 +502,18 @@ def _fengwu_window_attention(qkv, qkv_bias, table, out, geom: list[int], scale: 
         native.check(lib.skfw_window_attention(ctypes.byref(d), native.stream(dev)), "skfw_window_attention", lib)
 
 
+# ---- ensembles ----------------------------------------------------------------------------------------------------------------- #
+def _ens_perturb(x0, std, out, chan_stride: int, scale: float, seed: int, member_first: int) -> None:
+    from . import ensemble
+    ensemble.perturb(x0, std, out, chan_stride, scale, seed, member_first)
+
+
+def _ens_stats(members, table, offset: int, n: int, mean, spread, min, max, exceed, thresholds, quant, levels) -> None:
+    """``table``: ensemble.member_table(members), the device array of the members' pointers."""
+    from . import ensemble
+    ensemble.stats(list(members), table, offset, n, mean, spread, min, max, exceed, list(thresholds), quant, list(levels))
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -544,6 +557,9 @@ _SCHEMAS = [
      _fuxi_resample),
     ("fengwu_layer_norm(Tensor x, Tensor gamma, Tensor beta, Tensor(a!) out, int rows, int batch, int C, float eps) -> ()", _fengwu_layer_norm),
     ("fengwu_window_attention(Tensor qkv, Tensor qkv_bias, Tensor table, Tensor(a!) out, int[] geom, float scale) -> ()", _fengwu_window_attention),
+    ("ens_perturb(Tensor x0, Tensor std, Tensor(a!) out, int chan_stride, float scale, int seed, int member_first) -> ()", _ens_perturb),
+    ("ens_stats(Tensor[] members, Tensor table, int offset, int n, Tensor(a!)? mean, Tensor(b!)? spread, Tensor(c!)? min, Tensor(d!)? max, "
+     "Tensor(e!)? exceed, float[] thresholds, Tensor(f!)? quant, float[] levels) -> ()", _ens_stats),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 

@@ -108,6 +108,7 @@ class PanguTimeLoop(EngineTimeLoop):
         self.grid = Grid(self.geom.lat, self.geom.lon)
         self._mean = params["norm.mean"].to(self.engine.device, torch.float32).reshape(-1, 1, 1)
         self._std = params["norm.std"].to(self.engine.device, torch.float32).reshape(-1, 1, 1)
+        self.channel_std = self._std.reshape(-1)                     # the scale of a perturbed ensemble member (skyrim_amd/ensemble.py)
 
     @property
     def term_plan(self) -> int:
@@ -126,7 +127,7 @@ class PanguTimeLoop(EngineTimeLoop):
         for e in (self.engine, self.engine24):
             if e is not None:
                 e.release()
-        self._mean = self._std = None
+        self._mean = self._std = self.channel_std = None
 
     def __call__(self, time: datetime.datetime, x: torch.Tensor, restart=None):
         own = self.__dict__.pop("_state_is_own_output", False)       # run_basic_inference: ``x`` is this loop's last output, still in HBM

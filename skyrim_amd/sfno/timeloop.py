@@ -25,6 +25,7 @@ class SfnoTimeLoop(EngineTimeLoop):
         if params is None:
             params = weights.resolve("SKYRIM_SFNO_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed), "fourcastnet_v2")
         self.engine.load_params(params)
+        self.channel_std = torch.as_tensor(params["norm.std"]).float().reshape(-1)    # the scale of a perturbed ensemble member (skyrim_amd/ensemble.py)
         self._channels(CHANNELS, self.cfg.in_chans, self.cfg.out_chans)
         self.grid = Grid(list(np.linspace(90.0, -90.0, self.cfg.n_lat)), list(np.arange(self.cfg.n_lon) * (360.0 / self.cfg.n_lon)))
 

@@ -1,0 +1,168 @@
+"""``ensemble_forecast`` end to end on the MI355X: Pangu at 49 x 192 and FuXi at its toy size (two history levels, the cascade),
+the control member against ``forecast``, every product against the float64 statistic of the kept members, seeds, files and the
+``ensemble`` command."""
+from __future__ import annotations
+
+import datetime
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import _ens_reference as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+T0 = datetime.datetime(2024, 5, 13, 18, 0)
+FUXI_TOY = dict(n_lat=73, n_lon=144, channels=6, embed=128, heads=2, depth=2, window=(3, 6))
+
+
+@pytest.fixture(scope="module")
+def pangu(toy):
+    from skyrim_amd.core.models.pangu import PanguModel
+    g, params, _ = toy
+    return PanguModel(ic_source="gfs", geom=g, params=params)
+
+
+@pytest.fixture(scope="module")
+def fuxi():
+    from skyrim_amd.core.models.fuxi import FuxiModel
+    from skyrim_amd.fuxi.spec import FuxiConfig, init_synthetic
+    cfg = FuxiConfig(**FUXI_TOY, cascade_steps=(1, 2))
+    return FuxiModel(ic_source="synthetic", cfg=cfg, params=init_synthetic(cfg, 11), device=DEV)
+
+
+def _products_match_members(ens, exceed, quantiles):
+    mem = np.asarray(ens.members.values)                       # (M, T, C, H, W)
+    M, T, C = mem.shape[:3]
+    names = ens.members.channel.values.tolist()
+    for t in range(T):
+        x = mem[:, t].reshape(M, -1)
+        ref = R.stats(x)
+        assert np.array_equal(ens.min.values[t].reshape(-1), ref["min"]) and np.array_equal(ens.max.values[t].reshape(-1), ref["max"])
+        em = np.abs(ens.mean.values[t].reshape(-1).astype(np.float64) - ref["mean"]) / np.maximum(R.mean_bound(x, ref["mean"]), 1e-300)
+        es = np.abs(ens.spread.values[t].reshape(-1).astype(np.float64) - ref["spread"]) / np.maximum(R.spread_bound(x, ref["spread"]), 1e-300)
+        print(f"{ens.model_name} lead {t}: mean {em.max():.3f} of its bound, spread {es.max():.3f} of its bound")
+        assert em.max() <= 1 and es.max() <= 1
+        for ch, thr in exceed.items():
+            r = R.stats(mem[:, t, names.index(ch)].reshape(M, -1), thresholds=thr)
+            assert np.array_equal(ens.exceedance[ch].values[t].reshape(len(thr), -1), r["exceed"])
+        for ch, lev in quantiles.items():
+            r = R.stats(mem[:, t, names.index(ch)].reshape(M, -1), levels=lev)
+            for k, (q, big) in enumerate(r["quant"]):
+                got = ens.quantile[ch].values[t, k].reshape(-1).astype(np.float64)
+                assert np.all(np.abs(got - q) <= 2 * np.spacing(big.astype(np.float32)))
+
+
+def _end_to_end(m, exceed, quantiles):
+    before = m.forecast(T0, n_steps=3)
+    before_vals = np.array(before.values)
+    kw = dict(n_steps=3, n_members=5, keep_members=True, products=("mean", "spread", "min", "max"), exceed=exceed, quantiles=quantiles)
+    ens = m.ensemble_forecast(T0, seed=0, **kw)
+    assert ens.n_members == 5 and ens.seed == 0 and ens.perturb_scale == 1e-3 and ens.paths == []
+    assert ens.mean.dims == ("time", "channel", "lat", "lon") and ens.mean.shape == before.shape
+    assert ens.members.dims == ("member", "time", "channel", "lat", "lon") and ens.members.shape == (5,) + before.shape
+    assert np.array_equal(ens.mean.time.values, before.time.values)
+    for ch, v in exceed.items():
+        assert ens.exceedance[ch].dims == ("time", "threshold", "lat", "lon") and ens.exceedance[ch].shape[1] == len(v)
+    for ch, v in quantiles.items():
+        assert ens.quantile[ch].dims == ("time", "quantile", "lat", "lon") and ens.quantile[ch].shape[1] == len(v)
+    mem = np.asarray(ens.members.values)
+    assert np.array_equal(mem[0], before_vals)                               # the control member: forecast, bit for bit
+    assert all(not np.array_equal(mem[k], mem[0]) for k in range(1, 5))
+    assert float(np.asarray(ens.spread.values)[1:].max()) > 0
+    _products_match_members(ens, exceed, quantiles)
+    again = m.ensemble_forecast(T0, seed=0, **kw)
+    assert np.array_equal(np.asarray(again.members.values), mem) and np.array_equal(again.spread.values, ens.spread.values)
+    other = np.asarray(m.ensemble_forecast(T0, seed=1, **kw).members.values)
+    assert np.array_equal(other[0], mem[0]) and all(not np.array_equal(other[k], mem[k]) for k in range(1, 5))
+    one = m.ensemble_forecast(T0, n_steps=3, n_members=1)
+    assert np.array_equal(one.mean.values, before_vals) and np.all(one.spread.values == 0)
+    from skyrim_amd.core.models.base import GlobalPrediction
+    name = ens.mean.channel.values.tolist()[0]
+    assert GlobalPrediction(ens.mean).point(float(ens.mean.lat.values[3]), float(ens.mean.lon.values[5]), name, n_step=1) == ens.mean.values[1, 0, 3, 5].item()
+    after = m.forecast(T0, n_steps=3)                                        # an ordinary call on the same object: the bits it gave before
+    assert np.array_equal(np.asarray(after.values), before_vals)
+    return ens
+
+
+def test_pangu_toy_end_to_end(pangu):
+    _end_to_end(pangu, {"t2m": [273.15, 303.15]}, {"t2m": [0.1, 0.5, 0.9]})
+    pred, _ = pangu.rollout(T0, n_steps=2, save=False)
+    ref = pangu.forecast(T0, n_steps=2)
+    assert np.array_equal(np.asarray(pred.values)[-1], np.asarray(ref.values)[-1])
+
+
+def test_fuxi_toy_end_to_end_and_cascade(fuxi):
+    names = fuxi.out_channel_names
+    _end_to_end(fuxi, {names[0]: [0.0, 1.0]}, {names[-1]: [0.0, 0.5, 1.0]})
+    # every member switches stage at the same step: the step count belongs to the generator, not to the loop object
+    calls, real = [], fuxi.model.engine.call
+
+    def spy(older, newer, time, stage):
+        calls.append(stage)
+        return real(older, newer, time, stage)
+    fuxi.model.engine.call = spy
+    try:
+        fuxi.ensemble_forecast(T0, n_steps=3, n_members=4)
+    finally:
+        del fuxi.model.engine.call
+    assert calls == ["short"] * 4 + ["medium"] * 4 + ["long"] * 4
+
+
+def test_non_finite_member_is_named(fuxi):
+    real = fuxi.model.engine.call
+    count = [0]
+
+    def poison(older, newer, time, stage):
+        out = real(older, newer, time, stage)
+        count[0] += 1
+        if count[0] == 5:                                    # 3 members: the 5th call is member 1's second step
+            out = out.clone()
+            out[0, 0, 0] = float("nan")
+        return out
+    fuxi.model.engine.call = poison
+    try:
+        with pytest.raises(FloatingPointError, match=r"member(\(s\))? \[?1\]?.*step 2"):
+            fuxi.ensemble_forecast(T0, n_steps=3, n_members=3)
+    finally:
+        del fuxi.model.engine.call
+    assert np.isfinite(fuxi.forecast(T0, n_steps=1).values).all()
+
+
+@pytest.mark.parametrize("file_type", ["netcdf", "zarr"])
+def test_save_writes_product_files(pangu, tmp_path, file_type):
+    from skyrim_amd.labeled import open_dataarray
+    cfg = {"output_dir": str(tmp_path), "file_type": file_type}
+    ens = pangu.ensemble_forecast(T0, n_steps=2, n_members=3, products=("mean", "spread"), save=True, save_config=cfg)
+    fid = cfg["forecast_id"]
+    assert ens.forecast_id == fid and len(ens.paths) == 4
+    if file_type == "netcdf":
+        want = [f"pangu-ens3-{p}__{src}__{a}__{b}.nc" for (src, a, b) in (("synthetic", "20240513_18:00", "20240514_00:00"),
+                                                                          ("file", "20240514_00:00", "20240514_06:00")) for p in ("mean", "spread")]
+        assert [Path(p).name for p in ens.paths] == want
+        for p in ens.paths:
+            assert Path(p).parent == tmp_path / fid and Path(p).exists()
+            assert len(Path(p).stem.split("__")) == 4
+        for step in (1, 2):
+            back = open_dataarray(ens.paths[2 * (step - 1)])
+            assert back.shape == (2, 69, 49, 192)
+            assert np.array_equal(back.isel(time=-1).values, ens.mean.values[step])
+            assert np.array_equal(open_dataarray(ens.paths[2 * (step - 1) + 1]).isel(time=-1).values, ens.spread.values[step])
+    else:
+        assert set(ens.paths) == {str(tmp_path / fid / "pangu-ens3-mean"), str(tmp_path / fid / "pangu-ens3-spread")}
+        back = open_dataarray(tmp_path / fid / "pangu-ens3-mean")
+        assert back.shape[0] == 4                                             # two appends of two time entries each
+        assert np.array_equal(back.isel(time=-1).values, ens.mean.values[2])
+
+
+def test_ensemble_command_line(tmp_path):
+    from click.testing import CliRunner
+    from skyrim_amd.ensemble_cli import ensemble
+    res = CliRunner().invoke(ensemble, ["-m", "pangu", "-n", "3", "-l", "12", "-o", str(tmp_path), "-d", "20240513", "-t", "1800"])
+    assert res.exit_code == 0, res.output + repr(res.exception)
+    paths = [ln for ln in res.output.splitlines() if ln.endswith(".nc")]
+    assert len(paths) == 4 and all(Path(p).exists() for p in paths)
+    names = sorted(Path(p).name.split("__")[0] for p in paths)
+    assert names == ["pangu-ens3-mean"] * 2 + ["pangu-ens3-spread"] * 2
