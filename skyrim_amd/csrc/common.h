@@ -43,6 +43,12 @@ struct PrecF16x3  { typedef f16 T;  static constexpr int NA = 2, NW = 2; };
 // fc2 of the "fp16 hidden" mode: A = single fp16 plane (the GELU output), W = fp16 hi/lo planes, 2 MFMA terms
 struct PrecF16x2W { typedef f16 T;  static constexpr int NA = 1, NW = 2; };
 
+// 8 consecutive fp32 (16-byte aligned) as two float4 loads: the unit every A loader and attention operand is fetched in
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
 // ---- hi/lo split ---------------------------------------------------------- //
 // 8 fp32 -> NP planes of 8 x T packed as uint4.  lo = T(v - float(hi)).
 // The hi plane is made OPAQUE (an empty asm that "modifies" it) before the lo plane is derived from it.  Left alone, hipcc converts twice --

@@ -263,10 +263,6 @@ __global__ void __launch_bounds__(256) egress_kernel(const skdlwp_egress_desc d)
 
 using namespace skp;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
-
-static int hip_status() { return hipGetLastError() == hipSuccess ? 0 : SKDLWP_E_HIP; }
-
 extern "C" {
 
 int skdlwp_abi_version(void) { return SKDLWP_ABI_VERSION; }
@@ -281,9 +277,7 @@ const char* skdlwp_error_string(int code) {
 }
 
 int skdlwp_prepare_weight(const float* src, long long sn, long long sk, int N, int K, void* dst, long long plane, int ldw, void* stream) {
-    if (!src || !dst || N <= 0 || K <= 0 || ldw < K || (ldw & 7) || plane < (long long)N * ldw) return SKDLWP_E_ARG;
-    const hipError_t e = prep_weight<f16, 2>(src, static_cast<f16*>(dst), plane, N, K, ldw, sn, sk, 0, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : SKDLWP_E_HIP;
+    return prepare_weight_f16(src, sn, sk, N, K, dst, plane, ldw, stream, SKDLWP_E_ARG, SKDLWP_E_HIP);
 }
 
 int skdlwp_ingest(const skdlwp_ingest_desc* d, void* stream) {
@@ -292,7 +286,7 @@ int skdlwp_ingest(const skdlwp_ingest_desc* d, void* stream) {
         (d->ld_out & 7))
         return SKDLWP_E_ARG;
     hipLaunchKernelGGL(ingest_kernel, dim3((unsigned)((d->cells + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return hip_status();
+    return hip_status(SKDLWP_E_HIP);
 }
 
 int skdlwp_conv(const skdlwp_conv_desc* d, void* stream) {
@@ -324,7 +318,7 @@ int skdlwp_egress(const skdlwp_egress_desc* d, void* stream) {
         d->channels > kMaxC || d->cells <= 0 || d->points <= 0 || d->ld_y < 2 * d->channels || (d->ld_y & 3) || !aligned16(d->y))
         return SKDLWP_E_ARG;
     hipLaunchKernelGGL(egress_kernel, dim3((unsigned)((d->points + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return hip_status();
+    return hip_status(SKDLWP_E_HIP);
 }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/skyrim_fcn.h"
+#include "rownorm.h"
 #include "strided_gemm.h"
 
 namespace skp {
@@ -97,67 +98,21 @@ struct EpHead {
     }
 };
 
-template <class AL, class EP>
-hipError_t run_gemm(const AL& al, const EP& ep, const void* w, long long w_plane, int ldw, int M, int N, int K, hipStream_t s) {
-    GemmArgs<PrecF16x3, AL, EP> g;
-    g.al = al;
-    g.ep = ep;
-    g.W = static_cast<const f16*>(w);
-    g.w_plane = w_plane;
-    g.ldw = ldw;
-    g.M = M; g.N = N; g.K = K;
-    return launch_gemm<PrecF16x3, TF, AL, EP>(g, s);
-}
-
 // strided GEMM out = A W^T (+ bias, residuals) with two-level row addressing for A and out (strided_gemm.h)
 hipError_t dft_gemm(const float* a, int a_m1, long long a_sm, long long a_sm2, long long a_sk, const void* w, long long w_plane, int ldw,
                     float* out, int o_m1, long long o_sm, long long o_sm2, long long o_sn, const float* res_pre, const float* res_post,
                     int M, int N, int K, hipStream_t s) {
     const ALStrided al{a, M, K, a_m1, a_sm, a_sm2, a_sk, nullptr, nullptr, nullptr, 0, 0};
     const EpStrided ep{out, nullptr, res_pre, res_post, o_m1, 0, o_sm, o_sm2, o_sn};
-    return run_gemm(al, ep, w, w_plane, ldw, M, N, K, s);
+    return run_gemm<TF>(al, ep, w, w_plane, ldw, M, N, K, s);
 }
 
-// ---- LayerNorm over the channels of a row: one wavefront per row, two passes in registers ---- //
+// ---- LayerNorm over the channels of a row: one wavefront per row, two passes in registers (C <= 1024: 4 float4 per lane) ---- //
 __global__ void __launch_bounds__(256) layer_norm_kernel(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          float* __restrict__ out, long long rows, int C, float eps) {
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
     if (r >= rows) return;
-    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
-    const int C4 = C >> 2;
-    float4 v[4];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < C4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (lane + 64 * i < C4) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + eps);
-    float4* orow = reinterpret_cast<float4*>(out + r * C);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 gm = reinterpret_cast<const float4*>(gamma)[c], bt = reinterpret_cast<const float4*>(beta)[c];
-            orow[c] = make_float4((v[i].x - mean) * rstd * gm.x + bt.x, (v[i].y - mean) * rstd * gm.y + bt.y,
-                                  (v[i].z - mean) * rstd * gm.z + bt.z, (v[i].w - mean) * rstd * gm.w + bt.w);
-        }
-    }
+    row_layer_norm<4>(RowContig{reinterpret_cast<const float4*>(x + r * C)}, gamma, beta, nullptr, out + r * C, C, eps);
 }
 
 // ---- the fused two-layer MLP ----------------------------------------------------------------------------------------------------- //
@@ -407,8 +362,6 @@ hipError_t spectral_mlp(const skfcn_spectral_mlp_desc* d, hipStream_t s) {
 
 using namespace skp;
 
-static int hip_status() { return hipGetLastError() == hipSuccess ? 0 : SKFCN_E_HIP; }
-
 extern "C" {
 
 int skfcn_abi_version(void) { return SKFCN_ABI_VERSION; }
@@ -423,9 +376,7 @@ const char* skfcn_error_string(int code) {
 }
 
 int skfcn_prepare_weight(const float* src, long long sn, long long sk, int N, int K, void* dst, long long plane, int ldw, void* stream) {
-    if (!src || !dst || N <= 0 || K <= 0 || ldw < K || (ldw & 7) || plane < (long long)N * ldw) return SKFCN_E_ARG;
-    const hipError_t e = prep_weight<f16, 2>(src, static_cast<f16*>(dst), plane, N, K, ldw, sn, sk, 0, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : SKFCN_E_HIP;
+    return prepare_weight_f16(src, sn, sk, N, K, dst, plane, ldw, stream, SKFCN_E_ARG, SKFCN_E_HIP);
 }
 
 int skfcn_prepare_mlp_weights(const float* w1, const float* w2, int K, int H, int N, int batch, void* w1f, void* w2f, void* stream) {
@@ -434,7 +385,7 @@ int skfcn_prepare_mlp_weights(const float* w1, const float* w2, int K, int H, in
     const long long t1 = (long long)batch * H * K, t2 = (long long)batch * N * H;
     hipLaunchKernelGGL(prep_mlp_w1_kernel, dim3((unsigned)((t1 + 255) / 256)), dim3(256), 0, s, w1, static_cast<f16*>(w1f), H, K, t1);
     hipLaunchKernelGGL(prep_mlp_w2_kernel, dim3((unsigned)((t2 + 255) / 256)), dim3(256), 0, s, w2, static_cast<f16*>(w2f), N, H, t2);
-    return hip_status();
+    return hip_status(SKFCN_E_HIP);
 }
 
 int skfcn_patch_embed(const skfcn_patch_embed_desc* d, void* stream) {
@@ -446,14 +397,14 @@ int skfcn_patch_embed(const skfcn_patch_embed_desc* d, void* stream) {
     const int wt = d->wimg / d->patch, M = (d->himg / d->patch) * wt;
     const ALPatch al{d->x, M, K, wt, d->patch, d->wimg, (long long)d->himg * d->wimg, d->kscale, d->kshift};
     const EpStrided ep{d->out, d->bias, nullptr, d->pos, 1 << 30, 0, d->embed, 0, 1};
-    const hipError_t e = run_gemm(al, ep, d->w, d->w_plane, d->ldw, M, d->embed, K, static_cast<hipStream_t>(stream));
+    const hipError_t e = run_gemm<TF>(al, ep, d->w, d->w_plane, d->ldw, M, d->embed, K, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : SKFCN_E_HIP;
 }
 
 int skfcn_layer_norm(const float* x, const float* gamma, const float* beta, float* out, long long rows, int C, float eps, void* stream) {
     if (!x || !gamma || !beta || !out || rows <= 0 || C <= 0 || (C & 3) || C > 1024) return SKFCN_E_ARG;
     hipLaunchKernelGGL(layer_norm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, gamma, beta, out, rows, C, eps);
-    return hip_status();
+    return hip_status(SKFCN_E_HIP);
 }
 
 int skfcn_spectral_mlp(const skfcn_spectral_mlp_desc* d, void* stream) {
@@ -514,7 +465,7 @@ int skfcn_head_run(const skfcn_head_desc* d, void* stream) {
     if (d->ldw < d->embed || (d->ldw & 7) || d->w_plane < (long long)N * d->ldw || (long long)M * d->embed >= (1ll << 30)) return SKFCN_E_ARG;
     const ALFast<true> al{d->t, M, d->embed, 1 << 30, d->embed, 0, 1};
     const EpHead ep{d->out, d->bias, d->cout, wt, d->patch, d->wimg, (long long)d->himg * d->wimg};
-    const hipError_t e = run_gemm(al, ep, d->w, d->w_plane, d->ldw, M, N, d->embed, static_cast<hipStream_t>(stream));
+    const hipError_t e = run_gemm<TF>(al, ep, d->w, d->w_plane, d->ldw, M, N, d->embed, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? 0 : SKFCN_E_HIP;
 }
 

@@ -5,15 +5,17 @@
 //                zero rows outside the grid), ALFast rows (strided_gemm.h), ALCat (two sources along K: the skip linear).  EpFw: bias
 //                (+ GELU) (+ residual), the 2 x 2 pixel shuffle of the patch expand with its crop, the 4 x 4 scatter of the recovery
 //                with its crop and de-normalisation
-//   attention    one wave = 16 queries of one (window, head, batch entry); key tiles of 32 with an online softmax.  S^T = K Q^T and
-//                O^T = V^T P^T on v_mfma_f32_16x16x32_f16 (three hi/lo terms; head dim 32 = one k-step).  Windows of 1-, 2- or 3-D
-//                over a padded (Z, H, W) grid; the shift and the padding are token indexing (a padded token reads the qkv bias); the
-//                position bias and the shift mask come from one dense table row per query
-//   row kernels  LayerNorm over token rows, batched over modalities; the patch merge's 2 x 2 gather feeds the same kernel
+//   attention    window_attn.h's body (one wave = 16 queries of one (window, head, batch entry), online softmax over key tiles of
+//                32) with head dim 32 = one k-step.  FwAttn supplies windows of 1-, 2- or 3-D over a padded (Z, H, W) grid: the shift
+//                and the padding are token indexing (a padded token reads the qkv bias); the position bias and the shift mask come
+//                from one dense table row per query
+//   row kernels  LayerNorm over token rows (rownorm.h), batched over modalities; the patch merge's 2 x 2 gather feeds the same kernel
 #include <hip/hip_runtime.h>
 
 #include "../../include/skyrim_fengwu.h"
+#include "rownorm.h"
 #include "strided_gemm.h"
+#include "window_attn.h"
 
 namespace skp {
 
@@ -102,8 +104,7 @@ struct ALCat {
         for (int i = 0; i < 8; ++i) o.v[i] = 0.f;
         if (!r.ok || k >= K) return;
         const float* p = k < k_split ? a + r.m * lda + k : a2 + r.m * lda2 + (k - k_split);
-        const float4 x = *reinterpret_cast<const float4*>(p), y = *reinterpret_cast<const float4*>(p + 4);
-        o.v[0] = x.x; o.v[1] = x.y; o.v[2] = x.z; o.v[3] = x.w; o.v[4] = y.x; o.v[5] = y.y; o.v[6] = y.z; o.v[7] = y.w;
+        load8(p, o.v);
     }
     __device__ __forceinline__ void finish(const Raw& r, float (&v)[8]) const {
 #pragma unroll
@@ -227,219 +228,90 @@ constexpr int kLnVec = 6;                     // C <= 1536: 6 float4 per lane
 
 __global__ void __launch_bounds__(256) ln_kernel(const skfw_ln_desc d) {
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
     if (r >= d.rows * d.batch) return;
-    const int z = (int)(r / d.rows);
-    const long long rr = r - (long long)z * d.rows;
-    const int C = d.C, C4 = C >> 2;
-    float4 v[kLnVec];
+    const int z = (int)(r / d.rows), C = d.C;
+    const float *gamma = d.gamma + (long long)z * C, *beta = d.beta + (long long)z * C;
     if (!d.merge) {
-        const float4* xr = reinterpret_cast<const float4*>(d.x + r * C);
-#pragma unroll
-        for (int i = 0; i < kLnVec; ++i) {
-            const int c = lane + 64 * i;
-            v[i] = c < C4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    } else {
-        const int cs = C >> 2, cs4 = cs >> 2, w2 = d.w_src >> 1;
-        const int i = (int)(rr / w2), j = (int)(rr - (long long)i * w2);
-        const float* xb = d.x + (long long)z * d.h_src * d.w_src * cs;
-#pragma unroll
-        for (int u = 0; u < kLnVec; ++u) {
-            const int c = lane + 64 * u;
-            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < C4) {
-                const int q = c / cs4, cc = c - q * cs4;             // Swin's order: (dy, dx) = (0, 0), (1, 0), (0, 1), (1, 1)
-                const int sy = 2 * i + (q & 1) - d.front, sx = 2 * j + (q >> 1);
-                if (sy >= 0 && sy < d.h_src) v[u] = reinterpret_cast<const float4*>(xb + ((long long)sy * d.w_src + sx) * cs)[cc];
-            }
-        }
+        row_layer_norm<kLnVec>(RowContig{reinterpret_cast<const float4*>(d.x + r * C)}, gamma, beta, nullptr, d.out + r * C, C, d.eps);
+        return;
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        if (lane + 64 * i < C4) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
-            q += (a * a + b * b) + (c * c + e * e);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + d.eps);
-    float4* orow = reinterpret_cast<float4*>(d.out + r * C);
-    const float4* gp = reinterpret_cast<const float4*>(d.gamma + (long long)z * C);
-    const float4* bp = reinterpret_cast<const float4*>(d.beta + (long long)z * C);
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 gm = gp[c], bt = bp[c];
-            orow[c] = make_float4((v[i].x - mean) * rstd * gm.x + bt.x, (v[i].y - mean) * rstd * gm.y + bt.y,
-                                  (v[i].z - mean) * rstd * gm.z + bt.z, (v[i].w - mean) * rstd * gm.w + bt.w);
-        }
-    }
+    // row (i, j) of the merged grid: the 2 x 2 source tokens in Swin's order (dy, dx) = (0, 0), (1, 0), (0, 1), (1, 1); source rows cropped
+    // at the front or beyond the source are zero
+    const long long rr = r - (long long)z * d.rows;
+    const int cs = C >> 2, cs4 = cs >> 2, w2 = d.w_src >> 1;
+    const int i = (int)(rr / w2), j = (int)(rr - (long long)i * w2);
+    const float* xb = d.x + (long long)z * d.h_src * d.w_src * cs;
+    const auto gather = [&](int c) {
+        const int q = c / cs4, cc = c - q * cs4;
+        const int sy = 2 * i + (q & 1) - d.front, sx = 2 * j + (q >> 1);
+        if (sy < 0 || sy >= d.h_src) return make_float4(0.f, 0.f, 0.f, 0.f);
+        return reinterpret_cast<const float4*>(xb + ((long long)sy * d.w_src + sx) * cs)[cc];
+    };
+    row_layer_norm<kLnVec>(gather, gamma, beta, nullptr, d.out + r * C, C, d.eps);
 }
 
 // ---- window attention ---------------------------------------------------------------------------------------------------------- //
-typedef OpT<f16>::v8 v8;
 constexpr int kHd = 32;
-
-__device__ __forceinline__ void split_v8(const float (&v)[8], v8& h, v8& l) {
-    uint4 o[2];
-    split8<f16, 2>(v, o);
-    h = as_v8<f16>(o[0]);
-    l = as_v8<f16>(o[1]);
-}
-
-// P's scale before its fp16 split: p <= 1 stays below the fp16 maximum, and the lo plane of p >= 2^-18 stays normal
-constexpr float kPScale = 32768.0f;
-
-__device__ __forceinline__ f32x4 mfma3(const v8& ah, const v8& al, const v8& bh, const v8& bl, f32x4 c) {
-    c = OpT<f16>::mfma(al, bh, c);
-    c = OpT<f16>::mfma(ah, bl, c);
-    return OpT<f16>::mfma(ah, bh, c);
-}
-
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 __device__ __forceinline__ int type_of(int n_types, int n_win, int i) { return n_types == n_win ? i : (n_types == 2 ? (i == n_win - 1 ? 1 : 0) : 0); }
 
-__global__ void __launch_bounds__(256) window_attn_kernel(const skfw_attn_desc d, int nqc) {
-    const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
-    const int wave = threadIdx.x >> 6;
-    const int win = blockIdx.x, head = blockIdx.y, bt = blockIdx.z / nqc, qc = blockIdx.z - bt * nqc;
-    const int wz = d.wz, wh = d.wh, ww = d.ww, whw = wh * ww, N = wz * whw;
-    const int q0 = qc * 64 + wave * 16;
-    if (q0 >= N) return;                                          // wave-uniform; no barriers in this kernel
-    const int nwx = d.Wp / ww, nwy = d.Hp / wh, nwz = d.Zp / wz;
-    const int wx = win % nwx, wyz = win / nwx, wy = wyz % nwy, wzi = wyz / nwy;
-    const long long ld = 3ll * d.C, ntok = (long long)d.Z * d.H * d.W;
-    const float* qkv = d.qkv + bt * ntok * ld + head * kHd;
-    const float* pb = d.qkv_bias + bt * ld + head * kHd;
+struct FwAttn {
+    static constexpr int HD = kHd;
+    const skfw_attn_desc& d;
+    int bt, head, wzi, wy, wx;         // batch entry, head, the window's place in the shifted padded grid
+    const float* qkv;                  // the batch entry's tokens and the row a padding token reads, both at the head's q
+    const float* pb;
+    const float* table;                // [N][N] of the window's type and the head
+    long long tq;                      // the query: its token (-1: padding) and its table row
+    const float* trow;
+    __device__ __forceinline__ FwAttn(const skfw_attn_desc& d_, int win, int head_, int bt_) : d(d_), bt(bt_), head(head_) {
+        const int nwx = d.Wp / d.ww, nwy = d.Hp / d.wh, nwz = d.Zp / d.wz, wyz = win / nwx, N = d.wz * d.wh * d.ww;
+        wx = win % nwx;
+        wy = wyz % nwy;
+        wzi = wyz / nwy;
+        qkv = d.qkv + bt * ((long long)d.Z * d.H * d.W) * (3ll * d.C) + head * kHd;
+        pb = d.qkv_bias + bt * (3ll * d.C) + head * kHd;
+        const int type = type_of(d.types_z, nwz, wzi) * d.types_y + type_of(d.types_y, nwy, wy);
+        table = d.table + bt * d.table_sb + ((long long)type * d.heads + head) * N * N;
+    }
     // window-local index -> shifted padded-grid coordinate -> rolled back -> unpadded token (-1: a padding token)
-    auto token = [&](int i) -> long long {
-        const int iz = i / whw, rem = i - iz * whw, iy = rem / ww, ix = rem - iy * ww;
-        int zs = wzi * wz + iz + d.sz, ys = wy * wh + iy + d.sh, xs = wx * ww + ix + d.sw;
+    __device__ __forceinline__ long long token(int i) const {
+        const int whw = d.wh * d.ww, iz = i / whw, rem = i - iz * whw, iy = rem / d.ww, ix = rem - iy * d.ww;
+        int zs = wzi * d.wz + iz + d.sz, ys = wy * d.wh + iy + d.sh, xs = wx * d.ww + ix + d.sw;
         if (zs >= d.Zp) zs -= d.Zp;
         if (ys >= d.Hp) ys -= d.Hp;
         if (xs >= d.Wp) xs -= d.Wp;
         const int zr = zs - d.fz, yr = ys - d.fh, xr = xs - d.fw;
         if (zr < 0 || zr >= d.Z || yr < 0 || yr >= d.H || xr < 0 || xr >= d.W) return -1;
         return ((long long)zr * d.H + yr) * d.W + xr;
-    };
-    auto ptr = [&](long long t, int part) -> const float* { return (t < 0 ? pb : qkv + t * ld) + part * d.C; };
-
-    // queries: lane (l15, g) holds scale q[d = 8 g + j] of query q0 + l15 (the B operand of S^T = K Q^T)
-    const int qi = q0 + l15 < N ? q0 + l15 : N - 1;
-    const long long tq = token(qi);
-    v8 qh, ql;
-    {
-        float v[8];
-        load8(ptr(tq, 0) + 8 * g, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= d.scale;
-        split_v8(v, qh, ql);
     }
-    const int type = type_of(d.types_z, nwz, wzi) * d.types_y + type_of(d.types_y, nwy, wy);
-    const float* trow = d.table + bt * d.table_sb + (((long long)type * d.heads + head) * N + qi) * N;
-    float m = -INFINITY, lsum = 0.f;
-    f32x4 o[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int k0 = 0; k0 < N; k0 += 32) {
-        // S^T[key][q] for keys k0 + 16 b + (0..15): A = K[key = l15 + 16 b][d = 8 g + j]
-        f32x4 s[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int key = k0 + 16 * b + l15 < N ? k0 + 16 * b + l15 : N - 1;
-            float v[8];
-            load8(ptr(token(key), 1) + 8 * g, v);
-            v8 kh, kl;
-            split_v8(v, kh, kl);
-            s[b] = mfma3(kh, kl, qh, ql, f32x4{0.f, 0.f, 0.f, 0.f});
-        }
-        // s[b][r] = score of key k0 + 16 b + 4 g + r for query q0 + l15: + the table entry; online softmax
-        float p[8];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = k0 + 16 * b + 4 * g + r;
-                const float v = key < N ? s[b][r] + trow[key] : -INFINITY;
-                p[4 * b + r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mn = fmaxf(m, mx);                  // finite: key k0 is in every tile
-        const float alpha = expf(m - mn);
-        m = mn;
-        lsum *= alpha;
-#pragma unroll
-        for (int b = 0; b < 2; ++b) o[b] *= alpha;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            p[i] = p[i] == -INFINITY ? 0.f : expf(p[i] - mn);
-            lsum += p[i];
-        }
-        // P^T as the B operand: k-slot (g, j) <-> key k0 + (j < 4 ? 4 g + j : 16 + 4 g + j - 4), exactly this lane's p[j], scaled by
-        // kPScale before the split (1/kPScale is folded into 1/lsum): unscaled, a p below 2^-3 leaves a subnormal lo plane that keeps
-        // only multiples of 2^-24, and over a sharp softmax of many keys those losses add up
-        v8 ph, pl;
-        {
-            float ps[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ps[i] = p[i] * kPScale;
-            split_v8(ps, ph, pl);
-        }
-        const float* vp[8];
-        bool vok[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = k0 + (j < 4 ? 4 * g + j : 12 + 4 * g + j);
-            vok[j] = key < N;
-            vp[j] = ptr(token(vok[j] ? key : N - 1), 2) + l15;
-        }
-        // O^T[d][q] += V^T P^T: A = V^T[d = 16 db + l15][k-slot (g, j)]
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = vok[j] ? vp[j][16 * db] : 0.f;
-            v8 vh, vl;
-            split_v8(v, vh, vl);
-            o[db] = mfma3(vh, vl, ph, pl, o[db]);
-        }
+    __device__ __forceinline__ void query(int i) {
+        tq = token(i);
+        trow = table + (long long)i * (d.wz * d.wh * d.ww);
     }
-    lsum += __shfl_xor(lsum, 16);
-    lsum += __shfl_xor(lsum, 32);
-    if (q0 + l15 >= N || tq < 0) return;
-    const float inv = (1.0f / lsum) * (1.0f / kPScale);
-    // o[db][r] = O[q0 + l15][16 db + 4 g + r]
-    float* op = d.out + (bt * ntok + tq) * d.C + head * kHd + 4 * g;
+    __device__ __forceinline__ const float* row(int i, int part) const {
+        const long long t = token(i);
+        return (t < 0 ? pb : qkv + t * (3ll * d.C)) + part * d.C;
+    }
+    __device__ __forceinline__ void prep_q(float (&v)[1][8]) const {
 #pragma unroll
-    for (int db = 0; db < 2; ++db)
-        *reinterpret_cast<float4*>(op + 16 * db) = make_float4(o[db][0] * inv, o[db][1] * inv, o[db][2] * inv, o[db][3] * inv);
+        for (int j = 0; j < 8; ++j) v[0][j] *= d.scale;
+    }
+    __device__ __forceinline__ void prep_k(float (&)[1][8]) const {}
+    __device__ __forceinline__ float score(float s, int key) const { return s + trow[key]; }
+    __device__ __forceinline__ float* out() const {
+        return tq < 0 ? nullptr : d.out + (bt * ((long long)d.Z * d.H * d.W) + tq) * d.C + head * kHd;
+    }
+};
+
+__global__ void __launch_bounds__(256) window_attn_kernel(const skfw_attn_desc d, int nqc) {
+    const int bt = blockIdx.z / nqc;
+    window_attn_body(FwAttn(d, blockIdx.x, blockIdx.y, bt), d.wz * d.wh * d.ww, blockIdx.z - bt * nqc);
 }
 
 }  // namespace skp
 
 using namespace skp;
-
-static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
-
-static int hip_status() { return hipGetLastError() == hipSuccess ? 0 : SKFW_E_HIP; }
 
 static bool mods_ok(int mods, const int* off, const int* cnt) {
     if (mods <= 0 || mods > SKFW_MAX_MODS) return false;
@@ -463,9 +335,7 @@ const char* skfw_error_string(int code) {
 }
 
 int skfw_prepare_weight(const float* src, long long sn, long long sk, int N, int K, void* dst, long long plane, int ldw, void* stream) {
-    if (!src || !dst || N <= 0 || K <= 0 || ldw < K || (ldw & 7) || plane < (long long)N * ldw) return SKFW_E_ARG;
-    const hipError_t e = prep_weight<f16, 2>(src, static_cast<f16*>(dst), plane, N, K, ldw, sn, sk, 0, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : SKFW_E_HIP;
+    return prepare_weight_f16(src, sn, sk, N, K, dst, plane, ldw, stream, SKFW_E_ARG, SKFW_E_HIP);
 }
 
 int skfw_embed(const skfw_embed_desc* d, void* stream) {
@@ -495,7 +365,7 @@ int skfw_layer_norm(const skfw_ln_desc* d, void* stream) {
         return SKFW_E_ARG;
     const long long total = d->rows * d->batch;
     hipLaunchKernelGGL(ln_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return hip_status();
+    return hip_status(SKFW_E_HIP);
 }
 
 int skfw_linear(const skfw_linear_desc* d, void* stream) {
@@ -542,7 +412,7 @@ int skfw_window_attention(const skfw_attn_desc* d, void* stream) {
     const int nqc = (N + 63) / 64;
     if (nwin >= (1ll << 31) || (long long)d->batch * nqc > 65535) return SKFW_E_ARG;
     hipLaunchKernelGGL(window_attn_kernel, dim3((unsigned)nwin, d->heads, d->batch * nqc), dim3(256), 0, static_cast<hipStream_t>(stream), *d, nqc);
-    return hip_status();
+    return hip_status(SKFW_E_HIP);
 }
 
 int skfw_recover(const skfw_recover_desc* d, void* stream) {

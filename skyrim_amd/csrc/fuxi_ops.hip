@@ -5,14 +5,17 @@
 //   conv         gemm.h's pipeline with ALConv: 3 x 3 taps (stride 1 / 2, zero padding) or 1 x 1 over channels-last grids, the source
 //                read plain, GroupNorm-applied + SiLU, or as the concatenation of two sources; EpFuxi stores or pixel-shuffles (2 x 2)
 //   linear       gemm.h's pipeline with ALFast rows; EpFuxi: bias (+ GELU), or the head's 4 x 4 scatter into (C, 4 H, 4 W)
-//   attention    one wave = 16 queries of one (window, head); key tiles of 32 with an online softmax, so the window size is a run-time
-//                argument.  S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_f16 (three hi/lo terms): a lane ends with 8 scores
-//                of ONE query, which are -- permuted within the tile -- its B operand of the PV product, and 16 outputs of that query
-//   row kernels  LayerNorm (+ residual), GroupNorm statistics (float64, fixed order), GroupNorm + SiLU + residual, bilinear resample
+//   attention    window_attn.h's body (one wave = 16 queries of one (window, head), online softmax over key tiles of 32) with head
+//                dim 64; FxAttn supplies the 2-D roll, the cosine normalisation of q and k with the clamped logit scale, and the
+//                continuous position bias + region mask of a score
+//   row kernels  LayerNorm (+ residual: rownorm.h), GroupNorm statistics (float64, fixed order), GroupNorm + SiLU + residual, bilinear
+//                resample
 #include <hip/hip_runtime.h>
 
 #include "../../include/skyrim_fuxi.h"
+#include "rownorm.h"
 #include "strided_gemm.h"
+#include "window_attn.h"
 
 namespace skp {
 
@@ -91,8 +94,7 @@ struct ALConv {
         }
         const long long pix = (long long)iy * w_in + ix;
         const float* p = c < c0 ? src0 + pix * c0 + c : src1 + pix * c1 + (c - c0);
-        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-        o.v[0] = a.x; o.v[1] = a.y; o.v[2] = a.z; o.v[3] = a.w; o.v[4] = b.x; o.v[5] = b.y; o.v[6] = b.z; o.v[7] = b.w;
+        load8(p, o.v);
         if (gn_stats != nullptr && c < c0) o.c = c;
     }
     __device__ __forceinline__ void finish(const Raw& r, float (&v)[8]) const {
@@ -170,18 +172,6 @@ struct EpFuxi {
     }
 };
 
-template <class AL>
-hipError_t run_gemm(const AL& al, const EpFuxi& ep, const void* w, long long w_plane, int ldw, int M, int N, int K, hipStream_t s) {
-    GemmArgs<PrecF16x3, AL, EpFuxi> g;
-    g.al = al;
-    g.ep = ep;
-    g.W = static_cast<const f16*>(w);
-    g.w_plane = w_plane;
-    g.ldw = ldw;
-    g.M = M; g.N = N; g.K = K;
-    return launch_gemm<PrecF16x3, TFx, AL, EpFuxi>(g, s);
-}
-
 __global__ void __launch_bounds__(256) time_vec_kernel(const float* __restrict__ tw, const float* __restrict__ tb, skfuxi_embed_desc d) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= d.C) return;
@@ -197,48 +187,8 @@ constexpr int kLnVec = 6;
 __global__ void __launch_bounds__(256) ln_res_kernel(const float* __restrict__ x, const float* res, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, float* out, long long rows, int C, float eps) {
     const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
     if (r >= rows) return;
-    const float4* xr = reinterpret_cast<const float4*>(x + r * C);
-    const int C4 = C >> 2;
-    float4 v[kLnVec];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        const int c = lane + 64 * i;
-        v[i] = c < C4 ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    const float mean = s / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        if (lane + 64 * i < C4) {
-            const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + b * b) + (c * c + d * d);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    const float rstd = rsqrtf(q / (float)C + eps);
-    float4* orow = reinterpret_cast<float4*>(out + r * C);
-    const float4* rr = res ? reinterpret_cast<const float4*>(res + r * C) : nullptr;
-#pragma unroll
-    for (int i = 0; i < kLnVec; ++i) {
-        const int c = lane + 64 * i;
-        if (c < C4) {
-            const float4 gm = reinterpret_cast<const float4*>(gamma)[c], bt = reinterpret_cast<const float4*>(beta)[c];
-            float4 y = make_float4((v[i].x - mean) * rstd * gm.x + bt.x, (v[i].y - mean) * rstd * gm.y + bt.y,
-                                   (v[i].z - mean) * rstd * gm.z + bt.z, (v[i].w - mean) * rstd * gm.w + bt.w);
-            if (rr) {
-                const float4 t = rr[c];
-                y.x += t.x; y.y += t.y; y.z += t.z; y.w += t.w;
-            }
-            orow[c] = y;
-        }
-    }
+    row_layer_norm<kLnVec>(RowContig{reinterpret_cast<const float4*>(x + r * C)}, gamma, beta, res ? res + r * C : nullptr, out + r * C, C, eps);
 }
 
 // ---- GroupNorm: statistics (one workgroup per group, float64 partial sums in a fixed order), apply + SiLU + residual --------------- //
@@ -292,182 +242,67 @@ __global__ void __launch_bounds__(256) gn_residual_kernel(const float* x, const 
 }
 
 // ---- window attention ---------------------------------------------------------------------------------------------------------- //
-typedef OpT<f16>::v8 v8;
-
 __device__ __forceinline__ int region(int i, int n, int win, int s) { return s == 0 ? 0 : (i < n - win ? 0 : (i < n - s ? 1 : 2)); }
 
-__device__ __forceinline__ void split_v8(const float (&v)[8], v8& h, v8& l) {
-    uint4 o[2];
-    split8<f16, 2>(v, o);
-    h = as_v8<f16>(o[0]);
-    l = as_v8<f16>(o[1]);
-}
-
-// P's scale before its fp16 split: p <= 1 stays below the fp16 maximum, and the lo plane of p >= 2^-18 stays normal
-constexpr float kPScale = 32768.0f;
-
-__device__ __forceinline__ f32x4 mfma3(const v8& ah, const v8& al, const v8& bh, const v8& bl, f32x4 c) {
-    c = OpT<f16>::mfma(al, bh, c);
-    c = OpT<f16>::mfma(ah, bl, c);
-    return OpT<f16>::mfma(ah, bh, c);
-}
-
-__global__ void __launch_bounds__(256) window_attn_kernel(const skfuxi_attn_desc d) {
-    const int lane = threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
-    const int wave = threadIdx.x >> 6;
-    const int win = blockIdx.x, head = blockIdx.y;
-    const int wh = d.wh, ww = d.ww, H = d.H, W = d.W, N = wh * ww;
-    const int q0 = blockIdx.z * 64 + wave * 16;
-    if (q0 >= N) return;                                          // wave-uniform; no barriers in this kernel
-    const int wy = win / (W / ww), wx = win - wy * (W / ww);
-    const int swm = d.mask_lon ? d.sw : 0;
-    const long long ld = 3ll * d.C;
-    // token of window-local index i: shifted-grid (ys, xs), rolled back to the stored grid
-    auto token = [&](int i, int& ys, int& xs) -> long long {
-        const int r = i / ww, c = i - r * ww;
-        ys = wy * wh + r;
-        xs = wx * ww + c;
-        int yo = ys + d.sh, xo = xs + d.sw;
-        if (yo >= H) yo -= H;
-        if (xo >= W) xo -= W;
-        return (long long)yo * W + xo;
-    };
-
-    // queries: lane (l15, g) holds q[d = 32 ch + 8 g + j] of query q0 + l15 (the B operand of S^T = K Q^T)
-    const int qi = q0 + l15 < N ? q0 + l15 : N - 1;
-    int qys, qxs;
-    const long long tq = token(qi, qys, qxs);
-    const int qreg = 3 * region(qys, H, wh, d.sh) + region(qxs, W, ww, swm);
-    const int qr = qi / ww, qc = qi - qr * ww;
-    v8 qh[2], ql[2];
-    {
-        const float* p = d.qkv + tq * ld + head * 64 + 8 * g;
-        float v[2][8];
+struct FxAttn {
+    static constexpr int HD = 64;
+    const skfuxi_attn_desc& d;
+    int head, wy, wx;                  // the window's place in the shifted grid
+    int swm;                           // the longitude shift as the mask sees it (0: periodic, no mask)
+    const float* cpb;                  // the head's (2 wh - 1) x (2 ww - 1) position-bias table
+    long long tq;                      // the query: its token, window row / column and mask region
+    int qr, qc, qreg;
+    __device__ __forceinline__ FxAttn(const skfuxi_attn_desc& d_, int win, int head_)
+        : d(d_), head(head_), wy(win / (d_.W / d_.ww)), wx(win - wy * (d_.W / d_.ww)), swm(d_.mask_lon ? d_.sw : 0),
+          cpb(d_.cpb + (long long)head_ * (2 * d_.wh - 1) * (2 * d_.ww - 1)) {}
+    // token of window-local (r, c): shifted-grid position, rolled back to the stored grid
+    __device__ __forceinline__ long long token(int r, int c) const {
+        int yo = wy * d.wh + r + d.sh, xo = wx * d.ww + c + d.sw;
+        if (yo >= d.H) yo -= d.H;
+        if (xo >= d.W) xo -= d.W;
+        return (long long)yo * d.W + xo;
+    }
+    __device__ __forceinline__ int reg(int r, int c) const { return 3 * region(wy * d.wh + r, d.H, d.wh, d.sh) + region(wx * d.ww + c, d.W, d.ww, swm); }
+    __device__ __forceinline__ void query(int i) {
+        qr = i / d.ww;
+        qc = i - qr * d.ww;
+        tq = token(qr, qc);
+        qreg = reg(qr, qc);
+    }
+    __device__ __forceinline__ const float* row(int i, int part) const {
+        const int r = i / d.ww;
+        return d.qkv + token(r, i - r * d.ww) * (3ll * d.C) + part * d.C + head * HD;
+    }
+    // |v| over the 64 values of a row that the four lanes (l15, 0..3) hold, floored at norm_eps
+    __device__ __forceinline__ float norm(const float (&v)[2][8]) const {
         float ss = 0.f;
 #pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-            const float4 a = *reinterpret_cast<const float4*>(p + 32 * ch), b = *reinterpret_cast<const float4*>(p + 32 * ch + 4);
-            v[ch][0] = a.x; v[ch][1] = a.y; v[ch][2] = a.z; v[ch][3] = a.w; v[ch][4] = b.x; v[ch][5] = b.y; v[ch][6] = b.z; v[ch][7] = b.w;
+        for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
             for (int j = 0; j < 8; ++j) ss += v[ch][j] * v[ch][j];
-        }
         ss += __shfl_xor(ss, 16);
         ss += __shfl_xor(ss, 32);
-        const float f = expf(fminf(d.logit_scale[head], d.logit_max)) / fmaxf(sqrtf(ss), d.norm_eps);
+        return fmaxf(sqrtf(ss), d.norm_eps);
+    }
+    __device__ __forceinline__ void scale(float (&v)[2][8], float f) const {
 #pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
+        for (int ch = 0; ch < 2; ++ch)
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[ch][j] *= f;
-            split_v8(v[ch], qh[ch], ql[ch]);
-        }
     }
-    const int span = 2 * ww - 1;
-    const float* cpb = d.cpb + (long long)head * (2 * wh - 1) * span;
-    float m = -INFINITY, lsum = 0.f;
-    f32x4 o[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) o[b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    __device__ __forceinline__ void prep_q(float (&v)[2][8]) const { scale(v, expf(fminf(d.logit_scale[head], d.logit_max)) / norm(v)); }
+    __device__ __forceinline__ void prep_k(float (&v)[2][8]) const { scale(v, 1.0f / norm(v)); }
+    __device__ __forceinline__ float score(float s, int key) const {
+        const int kr = key / d.ww, kc = key - kr * d.ww;
+        float v = s + cpb[(qr - kr + d.wh - 1) * (2 * d.ww - 1) + (qc - kc + d.ww - 1)];
+        if (reg(kr, kc) != qreg) v += d.mask_value;
+        return v;
+    }
+    __device__ __forceinline__ float* out() const { return d.out + tq * d.C + head * HD; }
+};
 
-    for (int k0 = 0; k0 < N; k0 += 32) {
-        // S^T[key][q] for keys k0 + 16 b + (0..15): A = K[key = l15 + 16 b][d = 32 ch + 8 g + j]
-        f32x4 s[2];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int key = k0 + 16 * b + l15 < N ? k0 + 16 * b + l15 : N - 1;
-            int ys, xs;
-            const float* p = d.qkv + token(key, ys, xs) * ld + d.C + head * 64 + 8 * g;
-            float v[2][8];
-            float ss = 0.f;
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) {
-                const float4 a = *reinterpret_cast<const float4*>(p + 32 * ch), c = *reinterpret_cast<const float4*>(p + 32 * ch + 4);
-                v[ch][0] = a.x; v[ch][1] = a.y; v[ch][2] = a.z; v[ch][3] = a.w; v[ch][4] = c.x; v[ch][5] = c.y; v[ch][6] = c.z; v[ch][7] = c.w;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ss += v[ch][j] * v[ch][j];
-            }
-            ss += __shfl_xor(ss, 16);
-            ss += __shfl_xor(ss, 32);
-            const float f = 1.0f / fmaxf(sqrtf(ss), d.norm_eps);
-            s[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ch = 0; ch < 2; ++ch) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[ch][j] *= f;
-                v8 kh, kl;
-                split_v8(v[ch], kh, kl);
-                s[b] = mfma3(kh, kl, qh[ch], ql[ch], s[b]);
-            }
-        }
-        // s[b][r] = score of key k0 + 16 b + 4 g + r for query q0 + l15: + position bias + shift mask; online softmax
-        float p[8];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int key = k0 + 16 * b + 4 * g + r;
-                float v = -INFINITY;
-                if (key < N) {
-                    const int kr = key / ww, kc = key - kr * ww;
-                    v = s[b][r] + cpb[(qr - kr + wh - 1) * span + (qc - kc + ww - 1)];
-                    const int kreg = 3 * region(wy * wh + kr, H, wh, d.sh) + region(wx * ww + kc, W, ww, swm);
-                    if (kreg != qreg) v += d.mask_value;
-                }
-                p[4 * b + r] = v;
-                mx = fmaxf(mx, v);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float mn = fmaxf(m, mx);                  // finite: key k0 is in every tile
-        const float alpha = expf(m - mn);
-        m = mn;
-        lsum *= alpha;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) o[b] *= alpha;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            p[i] = p[i] == -INFINITY ? 0.f : expf(p[i] - mn);
-            lsum += p[i];
-        }
-        // P^T as the B operand: k-slot (g, j) <-> key k0 + (j < 4 ? 4 g + j : 16 + 4 g + j - 4), exactly this lane's p[j], scaled by
-        // kPScale before the split (1/kPScale is folded into 1/lsum): unscaled, a p below 2^-3 leaves a subnormal lo plane that keeps
-        // only multiples of 2^-24, and over a sharp softmax of many keys those losses add up
-        v8 ph, pl;
-        {
-            float ps[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ps[i] = p[i] * kPScale;
-            split_v8(ps, ph, pl);
-        }
-        long long vt[8];
-        bool vok[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int key = k0 + (j < 4 ? 4 * g + j : 12 + 4 * g + j);
-            vok[j] = key < N;
-            int ys, xs;
-            vt[j] = token(vok[j] ? key : N - 1, ys, xs) * ld + 2 * d.C + head * 64 + l15;
-        }
-        // O^T[d][q] += V^T P^T: A = V^T[d = 16 db + l15][k-slot (g, j)]
-#pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = vok[j] ? d.qkv[vt[j] + 16 * db] : 0.f;
-            v8 vh, vl;
-            split_v8(v, vh, vl);
-            o[db] = mfma3(vh, vl, ph, pl, o[db]);
-        }
-    }
-    lsum += __shfl_xor(lsum, 16);
-    lsum += __shfl_xor(lsum, 32);
-    if (q0 + l15 >= N) return;
-    const float inv = (1.0f / lsum) * (1.0f / kPScale);
-    // o[db][r] = O[q0 + l15][16 db + 4 g + r]
-    float* op = d.out + tq * d.C + head * 64 + 4 * g;
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-        *reinterpret_cast<float4*>(op + 16 * db) = make_float4(o[db][0] * inv, o[db][1] * inv, o[db][2] * inv, o[db][3] * inv);
+__global__ void __launch_bounds__(256) window_attn_kernel(const skfuxi_attn_desc d) {
+    window_attn_body(FxAttn(d, blockIdx.x, blockIdx.y), d.wh * d.ww, blockIdx.z);
 }
 
 // ---- bilinear resample + de-normalisation ------------------------------------------------------------------------------------- //
@@ -497,10 +332,6 @@ __global__ void __launch_bounds__(256) resample_kernel(const skfuxi_resample_des
 
 using namespace skp;
 
-static bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
-
-static int hip_status() { return hipGetLastError() == hipSuccess ? 0 : SKFUXI_E_HIP; }
-
 extern "C" {
 
 int skfuxi_abi_version(void) { return SKFUXI_ABI_VERSION; }
@@ -516,9 +347,7 @@ const char* skfuxi_error_string(int code) {
 }
 
 int skfuxi_prepare_weight(const float* src, long long sn, long long sk, int N, int K, void* dst, long long plane, int ldw, void* stream) {
-    if (!src || !dst || N <= 0 || K <= 0 || ldw < K || (ldw & 7) || plane < (long long)N * ldw) return SKFUXI_E_ARG;
-    const hipError_t e = prep_weight<f16, 2>(src, static_cast<f16*>(dst), plane, N, K, ldw, sn, sk, 0, 0, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? 0 : SKFUXI_E_HIP;
+    return prepare_weight_f16(src, sn, sk, N, K, dst, plane, ldw, stream, SKFUXI_E_ARG, SKFUXI_E_HIP);
 }
 
 int skfuxi_embed(const skfuxi_embed_desc* d, void* stream) {
@@ -532,7 +361,7 @@ int skfuxi_embed(const skfuxi_embed_desc* d, void* stream) {
     if (hipGetLastError() != hipSuccess) return SKFUXI_E_HIP;
     const ALEmbed al{d->x0, d->x1, d->mean, d->inv_std, M, K, wt, d->n_lon, (long long)d->n_lat * d->n_lon};
     const EpFuxi ep{d->out, d->bias, d->tvec, EP_STORE, 0, d->C, 0, 0, 0};
-    return run_gemm(al, ep, d->w, d->w_plane, d->ldw, M, d->C, K, s) == hipSuccess ? 0 : SKFUXI_E_HIP;
+    return run_gemm<TFx>(al, ep, d->w, d->w_plane, d->ldw, M, d->C, K, s) == hipSuccess ? 0 : SKFUXI_E_HIP;
 }
 
 int skfuxi_layer_norm(const float* x, const float* res, const float* gamma, const float* beta, float* out, long long rows, int C, float eps, void* stream) {
@@ -540,7 +369,7 @@ int skfuxi_layer_norm(const float* x, const float* res, const float* gamma, cons
         (res && !aligned16(res)))
         return SKFUXI_E_ARG;
     hipLaunchKernelGGL(ln_res_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, res, gamma, beta, out, rows, C, eps);
-    return hip_status();
+    return hip_status(SKFUXI_E_HIP);
 }
 
 int skfuxi_conv(const skfuxi_conv_desc* d, void* stream) {
@@ -559,13 +388,13 @@ int skfuxi_conv(const skfuxi_conv_desc* d, void* stream) {
     const ALConv al{d->src0, d->src1, d->gn_stats, d->gn_gamma, d->gn_beta, M, K, d->h_in, d->w_in, d->w_out, d->c0, d->c1, cin, d->taps,
                     d->stride, d->gn_stats ? d->c0 / d->groups : 1};
     const EpFuxi ep{d->out, d->bias, nullptr, d->shuffle ? EP_SHUFFLE : EP_STORE, 0, d->cout, d->w_out, 0, 0};
-    return run_gemm(al, ep, d->w, d->w_plane, d->ldw, M, N, K, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : SKFUXI_E_HIP;
+    return run_gemm<TFx>(al, ep, d->w, d->w_plane, d->ldw, M, N, K, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : SKFUXI_E_HIP;
 }
 
 int skfuxi_gn_stats(const float* x, long long rows, int C, int groups, float eps, float* stats, void* stream) {
     if (!x || !stats || rows <= 0 || C <= 0 || groups <= 0 || C % groups || groups > 65535) return SKFUXI_E_ARG;
     hipLaunchKernelGGL(gn_stats_kernel, dim3(groups), dim3(kGnThreads), 0, static_cast<hipStream_t>(stream), x, rows, C, C / groups, eps, stats);
-    return hip_status();
+    return hip_status(SKFUXI_E_HIP);
 }
 
 int skfuxi_gn_residual(const float* x, const float* a, const float* stats, const float* gamma, const float* beta, float* out, long long rows,
@@ -576,7 +405,7 @@ int skfuxi_gn_residual(const float* x, const float* a, const float* stats, const
     const long long n4 = rows * C / 4;
     hipLaunchKernelGGL(gn_residual_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, a, stats, gamma,
                        beta, out, n4, C, C / groups);
-    return hip_status();
+    return hip_status(SKFUXI_E_HIP);
 }
 
 int skfuxi_linear(const skfuxi_linear_desc* d, void* stream) {
@@ -590,7 +419,7 @@ int skfuxi_linear(const skfuxi_linear_desc* d, void* stream) {
     const ALFast<true> al{d->a, d->M, d->K, 1 << 30, d->K, 0, 1};
     EpFuxi ep{d->out, d->bias, nullptr, d->mode ? EP_HEAD : EP_STORE, d->act, d->N, d->w_tok, P, 0};
     if (d->mode == 1) ep.hw = (long long)(P * (d->M / d->w_tok)) * (P * d->w_tok);
-    return run_gemm(al, ep, d->w, d->w_plane, d->ldw, d->M, d->N, d->K, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : SKFUXI_E_HIP;
+    return run_gemm<TFx>(al, ep, d->w, d->w_plane, d->ldw, d->M, d->N, d->K, static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : SKFUXI_E_HIP;
 }
 
 int skfuxi_window_attention(const skfuxi_attn_desc* d, void* stream) {
@@ -602,7 +431,7 @@ int skfuxi_window_attention(const skfuxi_attn_desc* d, void* stream) {
     const int nwin = (d->H / d->wh) * (d->W / d->ww), N = d->wh * d->ww;
     if (d->heads > 65535 || (N + 63) / 64 > 65535) return SKFUXI_E_ARG;
     hipLaunchKernelGGL(window_attn_kernel, dim3(nwin, d->heads, (N + 63) / 64), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return hip_status();
+    return hip_status(SKFUXI_E_HIP);
 }
 
 int skfuxi_resample(const skfuxi_resample_desc* d, void* stream) {
@@ -611,7 +440,7 @@ int skfuxi_resample(const skfuxi_resample_desc* d, void* stream) {
         return SKFUXI_E_ARG;
     const long long total = (long long)d->channels * d->h_out * d->w_out;
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), *d);
-    return hip_status();
+    return hip_status(SKFUXI_E_HIP);
 }
 
 }  // extern "C"

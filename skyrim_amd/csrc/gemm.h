@@ -223,6 +223,19 @@ inline hipError_t launch_gemm(const GemmArgs<P, AL, EP>& g, hipStream_t stream) 
     return hipGetLastError();
 }
 
+// the fp16 x 3 GEMM of the per-model libraries: fp32 A through a loader, prepared fp16 hi/lo weights
+template <class TC, class AL, class EP>
+hipError_t run_gemm(const AL& al, const EP& ep, const void* w, long long w_plane, int ldw, int M, int N, int K, hipStream_t s) {
+    GemmArgs<PrecF16x3, AL, EP> g;
+    g.al = al;
+    g.ep = ep;
+    g.W = static_cast<const f16*>(w);
+    g.w_plane = w_plane;
+    g.ldw = ldw;
+    g.M = M; g.N = N; g.K = K;
+    return launch_gemm<PrecF16x3, TC, AL, EP>(g, s);
+}
+
 // element (a, b, r) of a wave's accumulator tile, swapped order:   m = m0w + a*16 + (lane&15),
 //                                                                  n = n0w + b*16 + 4*(lane>>4) + r
 //                                       un-swapped order:          n = n0w + b*16 + (lane&15),

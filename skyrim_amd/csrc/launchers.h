@@ -116,4 +116,17 @@ size_t colsum_scratch_floats(int rows, int K);
 hipError_t bias_fold(const float* w, const float* colsum, float scale, float* bias, int N, int K, hipStream_t);
 template <class T> hipError_t merge_stats(const T* x, long long plane, float2* stats, int Z, int H1, int W1, int H2, int W2, int C, float eps, hipStream_t);
 
+// ---- the C entry points of the per-model libraries (fcn, dlwp, fuxi, fengwu): each passes its own error codes ---- //
+inline bool aligned16(const void* p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
+
+inline int hip_status(int e_hip) { return hipGetLastError() == hipSuccess ? 0 : e_hip; }
+
+// the body of sk*_prepare_weight: fp32 [N][K] (strides sn, sk) -> fp16 hi / lo planes of [N][ldw]
+inline int prepare_weight_f16(const float* src, long long sn, long long sk, int N, int K, void* dst, long long plane, int ldw, void* stream,
+                              int e_arg, int e_hip) {
+    if (!src || !dst || N <= 0 || K <= 0 || ldw < K || (ldw & 7) || plane < (long long)N * ldw) return e_arg;
+    const hipError_t e = prep_weight<f16, 2>(src, static_cast<f16*>(dst), plane, N, K, ldw, sn, sk, 0, 0, static_cast<hipStream_t>(stream));
+    return e == hipSuccess ? 0 : e_hip;
+}
+
 }  // namespace skp
