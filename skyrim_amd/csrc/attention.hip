@@ -389,10 +389,15 @@ qkv_attention_kernel(const QkvAttnArgs a) {
         }
         if (wi + S::NWAVES < a.nW) load_src(wi + S::NWAVES);
         // A ROLLED loop over the query fragments: qv[qf] is then indexed at run time and lives in scratch memory (144 bytes per lane, written once
-        // and read once per window, L1-resident).  Fully unrolled the nine softmax bodies were scheduled into each other: 78-105 spilled registers
-        // and 0.28 ms per launch at C = 384 against 0.235 in this form (measured; the two-launch form: 0.29)
+        // and read once per window).  That is NOT an L1 hit: WRITE_SIZE of a launch exceeds the attention output by exactly 144 B x 64 lanes per
+        // (window, head) -- the fragments go out past the L2 and come back, so a reload is a fabric round trip.  It is therefore requested one
+        // iteration ahead (qn), under the softmax and P V of the fragment before it.  Fully unrolled the nine softmax bodies were scheduled into
+        // each other: 78-105 spilled registers and 0.28 ms per launch at C = 384 against 0.235 rolled (measured; the two-launch form: 0.29)
+        uint4 qn = qv[0];
 #pragma unroll 1
         for (int qf = 0; qf < 9; ++qf) {
+            const uint4 qc = qn;
+            if (qf < 8) qn = qv[qf + 1];                // requested a whole softmax + P V ahead of its use
             // the lane's query: the token of fragment row l15 -> (z_q, h_q, w_q); copy c = (w_q + 1) mod 4 makes every group address a multiple of 8 bytes
             const int qi = attn_key(qf, l15);
             const int zq = qi >= 72 ? 1 : 0, hq = (qi - 72 * zq) / 12, wq = qi - 72 * zq - 12 * hq;
@@ -403,7 +408,7 @@ qkv_attention_kernel(const QkvAttnArgs a) {
             for (int f = 0; f < 9; ++f) {
                 typedef f16 h4 __attribute__((ext_vector_type(4)));
                 const h4 b = __builtin_bit_cast(h4, *reinterpret_cast<const uint2*>(bqp + koff[f]));
-                s[f] = OpT<T>::mfma(as_v8<T>(kf[f]), as_v8<T>(qv[qf]), f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]});
+                s[f] = OpT<T>::mfma(as_v8<T>(kf[f]), as_v8<T>(qc), f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]});
             }
             f32x4 o[2], osum;
             attn_softmax_pv(s, vf, o, osum);

@@ -89,7 +89,10 @@ proj_mlp2_kernel(const Block2Args<T> a) {
 #pragma unroll
     for (int t = 0; t < FM; ++t) {              // consumed once here: hipcc's vmcnt waits for these loads sit BEFORE the loops (fused_mlp.hip)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) { asm volatile("" : "+v"(xh[t][ks])); asm volatile("" : "+v"(xl[t][ks])); }
+        for (int ks = 0; ks < KS; ++ks) {
+            asm volatile("" : "+v"(xh[t][ks]));
+            if constexpr (!S::ONE) asm volatile("" : "+v"(xl[t][ks]));      // (ONE: zeros nobody reads -- no registers are pinned for them)
+        }
     }
 
     f32x4 yacc[FM][CF];
@@ -164,6 +167,9 @@ proj_mlp2_kernel(const Block2Args<T> a) {
             split8<T, 2>(v, o);
             xh[t][bp] = as_v8<T>(o[0]);
             xl[t][bp] = as_v8<T>(o[1]);
+            // the planes are FINISHED here: in ONE mode the lo plane is next read in the epilogue, and the compiler would rather carry the
+            // eight floats `v` across the MLP loop (in scratch) and round them there
+            asm volatile("" : "+v"(xh[t][bp]), "+v"(xl[t][bp]));
         }
 #pragma unroll
         for (int c = 0; c < CF; ++c) yacc[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -249,9 +255,13 @@ proj_mlp2_kernel(const Block2Args<T> a) {
             const int n = 32 * bp + 8 * g;
             const float4 g0 = *reinterpret_cast<const float4*>(tab + S::T_G2 + n), g1 = *reinterpret_cast<const float4*>(tab + S::T_G2 + n + 4);
             const float4 e0 = *reinterpret_cast<const float4*>(tab + S::T_E2 + n), e1 = *reinterpret_cast<const float4*>(tab + S::T_E2 + n + 4);
+            // x_mid is converted back from the fragments HERE: left visible, the compiler reuses the floats split8 rounded in the between phase
+            // and carries them through the whole MLP loop -- in scratch (C / 2 + 1 dwords per lane and tile)
+            v8 mh = xh[t][bp], ml = xl[t][bp];
+            asm volatile("" : "+v"(mh), "+v"(ml));
             float oh[8], ol[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) { oh[i] = (float)xh[t][bp][i]; ol[i] = (float)xl[t][bp][i]; }
+            for (int i = 0; i < 8; ++i) { oh[i] = (float)mh[i]; ol[i] = (float)ml[i]; }
             const f32x4 &x = yacc[t][2 * bp], &z = yacc[t][2 * bp + 1];
             const float v[8] = {(oh[0] + ol[0]) + ((x[0] - mean) * rstd * g0.x + e0.x), (oh[1] + ol[1]) + ((x[1] - mean) * rstd * g0.y + e0.y),
                                 (oh[2] + ol[2]) + ((x[2] - mean) * rstd * g0.z + e0.z), (oh[3] + ol[3]) + ((x[3] - mean) * rstd * g0.w + e0.w),
