@@ -116,17 +116,32 @@ class GlobalModel:
     def ensemble_forecast(self, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3,
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
-                          save_config: dict | None = None):
+                          save_config: dict | None = None, truth=None, climatology=None, scores: bool = False):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
         own TimeLoop generator, and at each lead time one HIP pass over the members gives the ``products`` (any of mean, spread, min, max),
         the exceedance fractions ``exceed = {channel: [thresholds]}`` and the quantiles ``quantiles = {channel: [levels]}`` (at most 4
         values per channel).  Returns an ``ensemble.EnsembleForecast``; its time axis holds the initial condition and every
-        ``save_every``-th step.  ``save=True`` writes one file per product and saved step, model field ``{model}-ens{M}-{product}``."""
+        ``save_every``-th step.  ``save=True`` writes one file per product and saved step, model field ``{model}-ens{M}-{product}``.
+        ``scores=True`` scores every lead time against ``truth`` right after its statistics, on the members where they lie
+        (``verify`` below has the forms of ``truth`` and ``climatology``); the ``verify.Scores`` land in ``EnsembleForecast.scores``."""
         from ... import ensemble
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
-                            save=save, save_config=save_config)
+                            save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores)
+
+    def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
+               save: bool = False, save_config: dict | None = None):
+        """Scores of the deterministic forecast at every lead time 0 .. ``n_steps`` (skyrim_amd/verify.py): bias, MAE, RMSE,
+        CRPS (= MAE for one member) and, with a ``climatology``, ACC, area-weighted per channel.  The model's TimeLoop is advanced, each
+        valid time's truth is uploaded and the state is scored where it lies in HBM: no forecast state goes to the host.  ``truth``:
+        None = the model's own kind of data source at the valid times; or any object with ``channel_names`` and ``[time]``; or a
+        (time, channel, lat, lon) DataArray / saved forecast.  ``climatology``: the same forms, or one (channel, lat, lon) array for every
+        lead time.  Channels present in both forecast and truth are scored.  Returns ``verify.Scores``; ``save=True`` writes
+        ``{model}-scores.json`` under the forecast id directory."""
+        from ... import verify
+        return verify.verify_model(self, start_time, n_steps=n_steps, truth=truth, climatology=climatology, channels=channels, save=save,
+                                   save_config=save_config)
 
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):

@@ -43,6 +43,18 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.ensemble_forecast(start_time, n_steps=n_steps, n_members=n_members, **kwargs)
 
+    def verify(self, start_time: datetime.datetime, n_steps: int = 4, **kwargs):
+        """Scores of the single model's forecast against a truth at every lead time (``GlobalModel.verify`` has the arguments):
+        bias, MAE, RMSE, CRPS and ACC per channel as a ``verify.Scores``.  ``ensemble_forecast(..., scores=True)`` scores an ensemble."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.verify(start_time, n_steps=n_steps, **kwargs)
+
+    @staticmethod
+    def score_prediction(pred, truth, climatology=None, device="cuda:0", **kwargs):
+        """Scores of a forecast that is already in memory or on disk (``verify.score_prediction``)."""
+        from .. import verify
+        return verify.score_prediction(pred, truth, climatology=climatology, device=device, **kwargs)
+
     def predict(self, date: str, time: str, lead_time: int = 6, save: bool = False, save_config: dict | None = None):
         """Predict a single lead-time snapshot, optionally saving every intermediate step.
         date: YYYYMMDD, time: HHMM, lead_time in hours (clipped down to a multiple of 6, at least 6)."""

@@ -155,6 +155,7 @@ class EnsembleForecast:
     members: object = None
     paths: list = field(default_factory=list)
     forecast_id: str = ""
+    scores: object = None        # verify.Scores with ``scores=True``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -216,7 +217,7 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
 
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
-        save: bool = False, save_config: dict | None = None) -> EnsembleForecast:
+        save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from .common import generate_forecast_id, save_forecast
     from .datasource import get_initial_condition_for_model
@@ -227,6 +228,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     M = int(n_members)
     names = list(model.out_channel_names)
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
+    scorer = None
+    if scores:                                             # (refusals of the request come before anything touches the device)
+        from . import verify
+        scorer = verify.LeadScorer(gm.model_name, names, model.grid.lat, model.grid.lon, M, verify.default_truth(gm) if truth is None else truth,
+                                   climatology, channels, device=model.device)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -277,6 +283,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             if not bool(torch.isfinite(dev_out["mean"]).all().item()):
                 bad = [m for m, s in enumerate(states) if not bool(torch.isfinite(s).all().item())]
                 raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {k}")
+            if scorer is not None:
+                scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
             if keep:
                 s = saved.index(k)
                 times.append(time)
@@ -317,6 +325,12 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         return da.sel(channel=list(channels)) if channels and dim == "channel" else da
 
     ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid)
+    if scorer is not None:
+        ens.scores = scorer.result()
+        ens.scores.forecast_id = fid
+        if save:
+            from .common import OUTPUT_DIR
+            paths.append(ens.scores.save(cfg.get("output_dir") or OUTPUT_DIR))
     for p in products:
         setattr(ens, p, labelled(host[p], "channel", names))
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}

@@ -15,6 +15,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     fuxi_layer_norm / fuxi_window_attention / fuxi_resample   (FuXi, include/skyrim_fuxi.h)
     fengwu_layer_norm / fengwu_window_attention             (FengWu, include/skyrim_fengwu.h)
     ens_perturb / ens_stats                              (ensemble members and statistics, include/skyrim_ens.h)
+    score_fields                                         (forecast scores against a truth state, include/skyrim_score.h)
 """
 from __future__ import annotations
 
@@ -514,6 +515,13 @@ def _ens_stats(members, table, offset: int, n: int, mean, spread, min, max, exce
     ensemble.stats(list(members), table, offset, n, mean, spread, min, max, exceed, list(thresholds), quant, list(levels))
 
 
+# ---- verification -------------------------------------------------------------------------------------------------------------- #
+def _score_fields(members, table, truth, weights, out, workspace, flags: int, clim, counts, c0: int, nc: int) -> None:
+    """``table``: ensemble.member_table(members); ``flags``: the groups of verify.DET / VAR / CRPS / ACC / RANK."""
+    from . import verify
+    verify.score(list(members), table, truth, weights, out, workspace, flags, clim, counts, c0, nc)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -560,6 +568,8 @@ _SCHEMAS = [
     ("ens_perturb(Tensor x0, Tensor std, Tensor(a!) out, int chan_stride, float scale, int seed, int member_first) -> ()", _ens_perturb),
     ("ens_stats(Tensor[] members, Tensor table, int offset, int n, Tensor(a!)? mean, Tensor(b!)? spread, Tensor(c!)? min, Tensor(d!)? max, "
      "Tensor(e!)? exceed, float[] thresholds, Tensor(f!)? quant, float[] levels) -> ()", _ens_stats),
+    ("score_fields(Tensor[] members, Tensor table, Tensor truth, Tensor weights, Tensor(a!)? out, Tensor(b!) workspace, int flags, Tensor? clim, "
+     "Tensor(c!)? counts, int c0, int nc) -> ()", _score_fields),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 

@@ -1,0 +1,453 @@
+"""Forecast verification on the device (include/skyrim_score.h): RMSE, ACC, fair CRPS, spread / skill and the rank
+histogram of a forecast or an ensemble against a truth state, made where the states lie in HBM.
+
+Three layers:
+
+* the binding of libskyrim_score.so (``SPEC``, ``load_library``, ``score``); the same call is ``torch.ops.skyrim_hip.score_fields``;
+* ``area_weights`` and ``Scores`` -- the latitude weights and the labelled table the host forms from the kernel's per-channel sums;
+* the drivers: ``verify_model`` (``GlobalModel.verify``), ``LeadScorer`` (what ``ensemble.run`` calls at every lead time with
+  ``scores=True``) and ``score_prediction`` for forecasts that are already on disk.
+"""
+from __future__ import annotations
+
+import ctypes
+import datetime
+import json
+import math
+import os
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import native
+
+MAX_MEMBERS = 64                                                # include/skyrim_score.h SKSCORE_MAX_MEMBERS
+DET, VAR, CRPS, ACC, RANK = 1, 2, 4, 8, 16                      # SKSCORE_DET ...
+SLOTS = ("bias", "mae", "mse", "var", "crps", "abs", "pair", "fa", "ff", "aa")      # SKSCORE_BIAS ... SKSCORE_AA
+PARTIALS = 9
+METRICS = ("bias", "mae", "rmse", "acc", "crps", "spread", "ssr")
+DEFAULT_CHANNELS = ("z500", "t850", "t2m", "u10m")
+_P = ctypes.c_void_p
+
+
+class ScoreDesc(ctypes.Structure):
+    """skscore_desc."""
+    _fields_ = [("members", _P), ("M", ctypes.c_int), ("member_align", ctypes.c_int), ("truth", _P), ("clim", _P),
+                ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("c0", ctypes.c_int), ("nc", ctypes.c_int),
+                ("lat_weight", _P), ("flags", ctypes.c_int), ("out", _P), ("counts", _P), ("workspace", _P),
+                ("workspace_bytes", ctypes.c_size_t)]
+
+
+SPEC = native.Spec("skyrim_score", "SKYRIM_SCORE_LIB", "skscore", 1, {          # include/skyrim_score.h SKSCORE_ABI_VERSION
+    "skscore_abi_version": (ctypes.c_int, []),
+    "skscore_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "skscore_run": (ctypes.c_int, [ctypes.POINTER(ScoreDesc), _P]),
+}, " -- forecast scores have no torch fallback")
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+_lib = None
+
+
+def load_library() -> ctypes.CDLL:
+    """libskyrim_score.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
+    global _lib
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
+
+
+def _dev(t, what: str, dtype, dev=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
+    return t.data_ptr()
+
+
+def score(members, table: torch.Tensor, truth: torch.Tensor, weights: torch.Tensor, out, workspace: torch.Tensor, flags: int,
+          clim=None, counts=None, c0: int = 0, nc: int | None = None) -> None:
+    """One ``skscore_run``: the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors; ``table`` =
+    ``ensemble.member_table(members)``) against ``truth`` over the channels [c0, c0 + nc).  ``weights``: H float64; ``out``: float64
+    (nc, 10), slots ``SLOTS`` (only those of the groups in ``flags`` are written); ``counts``: int32 (nc, H, M + 1) with RANK;
+    ``workspace``: float64, at least C * H * 9 elements.  Queued on torch's current stream.
+
+    The members themselves are checked here; the CONTENTS of ``table`` (device memory) are not read back and are trusted to be the
+    addresses of ``members`` in order, as in ``ensemble.stats``: build it with ``member_table`` from the same list."""
+    M = len(members)
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"score_fields: {M} members; 1 to {MAX_MEMBERS} are supported")
+    if truth.dim() != 3:
+        raise ValueError("score_fields: states are (C, H, W)")
+    C, H, W = truth.shape
+    nc = C - c0 if nc is None else nc
+    dev = truth.device
+    d = ScoreDesc()
+    align = 16
+    for t in members:
+        if _dev(t, "score_fields: member", torch.float32, dev) % 16:
+            align = 4
+        if t.numel() != truth.numel():
+            raise ValueError(f"score_fields: a member holds {t.numel()} elements, the truth {truth.numel()}")
+    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
+        raise ValueError("score_fields: table must be member_table(members)")
+    if not (0 <= c0 and 0 <= nc and c0 + nc <= C) or flags <= 0 or flags & ~31:
+        raise ValueError("score_fields: a channel range inside the states and at least one group of outputs")
+    d.members, d.M, d.member_align, d.truth = table.data_ptr(), M, align, _dev(truth, "score_fields: truth", torch.float32, dev)
+    d.C, d.H, d.W, d.c0, d.nc, d.flags = C, H, W, c0, nc, flags
+    d.lat_weight = _dev(weights, "score_fields: weights", torch.float64, dev)
+    if weights.numel() != H:
+        raise ValueError(f"score_fields: {weights.numel()} latitude weights for {H} rows")
+    if flags & ACC:
+        if clim is None or clim.shape != truth.shape:
+            raise ValueError("score_fields: the ACC sums need a climatology of the truth's shape")
+        d.clim = _dev(clim, "score_fields: clim", torch.float32, dev)
+    if flags & RANK:
+        d.counts = _dev(counts, "score_fields: counts", torch.int32, dev)
+        if counts.numel() != nc * H * (M + 1):
+            raise ValueError(f"score_fields: counts must hold nc * H * (M + 1) = {nc * H * (M + 1)} int32")
+    if flags & ~RANK:
+        d.out = _dev(out, "score_fields: out", torch.float64, dev)
+        if out.numel() != nc * len(SLOTS):
+            raise ValueError(f"score_fields: out must hold nc * {len(SLOTS)} float64")
+    lib = load_library()
+    need = lib.skscore_workspace_bytes(C, H, M, flags)
+    d.workspace, d.workspace_bytes = _dev(workspace, "score_fields: workspace", torch.float64, dev), workspace.numel() * 8
+    if d.workspace_bytes < need:
+        raise ValueError(f"score_fields: the workspace holds {workspace.numel() * 8} bytes, {need} are needed")
+    with torch.cuda.device(dev):
+        native.check(lib.skscore_run(ctypes.byref(d), native.stream(dev)), "skscore_run", lib)
+
+
+# ---- weights and the table ------------------------------------------------------------------------------------------------------------ #
+def area_weights(lat) -> np.ndarray:
+    """Float64 cell-area weights of a latitude axis in degrees, as WeatherBench 2 defines them: w_j = sin(ub_j) - sin(lb_j) with the
+    cell bounds midway between neighbouring latitudes, the two outer bounds half a spacing beyond the axis and clipped to +-90.
+    Ascending and descending axes give the same weight to the same latitude; an axis from pole to pole sums to 2."""
+    lat = np.asarray(lat, np.float64)
+    if lat.ndim != 1 or lat.size == 0 or not np.all(np.isfinite(lat)) or np.any(np.abs(lat) > 90):
+        raise ValueError("area_weights: a one-dimensional latitude axis in degrees")
+    if lat.size == 1:
+        return np.ones(1)
+    step = np.diff(lat)
+    if not (np.all(step > 0) or np.all(step < 0)):
+        raise ValueError("area_weights: the latitude axis must be strictly monotonic")
+    mid = (lat[:-1] + lat[1:]) / 2
+    bounds = np.clip(np.concatenate([[lat[0] - step[0] / 2], mid, [lat[-1] + step[-1] / 2]]), -90.0, 90.0)
+    return np.abs(np.diff(np.sin(np.deg2rad(bounds))))
+
+
+def _iso(t) -> str:
+    return t.isoformat() if hasattr(t, "isoformat") else str(np.datetime_as_string(np.datetime64(t, "s")))
+
+
+class Scores:
+    """What verification returns.  ``table``: DataArray(metric, time, channel) with the metrics of ``METRICS`` that apply (ACC needs a
+    climatology; crps / spread / ssr as ensemble metrics need M > 1 -- the others are absent, not NaN-filled; at M = 1 ``crps`` is
+    present and equals ``mae``).  ``sums``: DataArray(slot, time, channel), the kernel's own per-channel sums (``SLOTS``) the table is
+    formed from.  ``rank_histogram``: (time, channel, rank) area-weighted frequencies that sum to 1, ``rank_counts`` the exact integers
+    summed over the latitude rows; both None at M = 1."""
+
+    def __init__(self, model_name, n_members, times, channels, sums, slots, rank_counts=None, rank_histogram=None, forecast_id=""):
+        from .labeled import DataArray
+        self.model_name, self.n_members, self.forecast_id = model_name, int(n_members), forecast_id
+        self.times, self.channels = list(times), list(channels)
+        slots = list(slots)
+        coords = dict(time=self.times, channel=self.channels)
+        self.sums = DataArray(np.asarray(sums, np.float64), ["slot", "time", "channel"], dict(slot=slots, **coords))
+        s = {k: np.asarray(sums, np.float64)[i] for i, k in enumerate(slots)}
+        M, rows = self.n_members, {}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            if "mse" in s:
+                rows["bias"], rows["mae"], rows["rmse"] = s["bias"], s["mae"], np.sqrt(s["mse"])
+            if "fa" in s:
+                rows["acc"] = s["fa"] / np.sqrt(s["ff"] * s["aa"])
+            if "crps" in s:
+                rows["crps"] = s["crps"]
+            if "var" in s and M > 1:
+                rows["spread"] = np.sqrt(s["var"])
+                if "mse" in s:
+                    rows["ssr"] = math.sqrt((M + 1) / M) * rows["spread"] / rows["rmse"]
+        names = [m for m in METRICS if m in rows]
+        self.table = DataArray(np.stack([rows[m] for m in names]) if names else np.zeros((0, len(self.times), len(self.channels))),
+                               ["metric", "time", "channel"], dict(metric=names, **coords))
+        self.rank_counts = self.rank_histogram = None
+        if rank_counts is not None:
+            rc = dict(rank=np.arange(M + 1), **coords)
+            self.rank_counts = DataArray(np.asarray(rank_counts, np.int64), ["time", "channel", "rank"], rc)
+            self.rank_histogram = DataArray(np.asarray(rank_histogram, np.float64), ["time", "channel", "rank"], rc)
+
+    def metric(self, name: str) -> np.ndarray:
+        """(time, channel) values of one metric."""
+        return self.table.sel(metric=name).values
+
+    def file_name(self) -> str:
+        return f"{self.model_name}-scores.json" if self.n_members == 1 else f"{self.model_name}-ens{self.n_members}-scores.json"
+
+    def to_json(self) -> str:
+        def clean(a):                                           # JSON has no NaN: non-finite scores are written as null
+            return [clean(v) for v in a] if isinstance(a, list) else (a if isinstance(a, int) or math.isfinite(a) else None)
+        doc = dict(model=self.model_name, n_members=self.n_members, forecast_id=self.forecast_id, times=[_iso(t) for t in self.times],
+                   channels=self.channels, slots=self.sums.slot.values.tolist(), sums=clean(self.sums.values.tolist()),
+                   metrics=self.table.metric.values.tolist(), table=clean(self.table.values.tolist()))
+        if self.rank_counts is not None:
+            doc["rank_counts"] = self.rank_counts.values.tolist()
+            doc["rank_histogram"] = clean(self.rank_histogram.values.tolist())
+        return json.dumps(doc)
+
+    def save(self, output_dir) -> str:
+        """``{output_dir}/{forecast id}/{model}-scores.json`` (``{model}-ens{M}-scores.json`` for an ensemble); returns the path."""
+        d = Path(output_dir) / self.forecast_id if self.forecast_id else Path(output_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        path = d / self.file_name()
+        path.write_text(self.to_json())
+        return str(path)
+
+    @classmethod
+    def from_json(cls, text: str) -> "Scores":
+        doc = json.loads(text)
+        nan = lambda a: np.array([[[np.nan if v is None else v for v in r] for r in p] for p in a], np.float64)      # noqa: E731
+        times = [datetime.datetime.fromisoformat(t) for t in doc["times"]]
+        rc = doc.get("rank_counts")
+        return cls(doc["model"], doc["n_members"], times, doc["channels"], nan(doc["sums"]).reshape(len(doc["slots"]), len(times), -1),
+                   doc["slots"], None if rc is None else np.array(rc, np.int64), None if rc is None else nan(doc["rank_histogram"]),
+                   doc.get("forecast_id", ""))
+
+    @classmethod
+    def load(cls, path) -> "Scores":
+        return cls.from_json(Path(path).read_text())
+
+
+# ---- truth and climatology ------------------------------------------------------------------------------------------------------------ #
+class _Fields:
+    """A truth or climatology in any of its accepted forms, read one valid time at a time as (channel names, (C, H, W) float32)."""
+
+    def __init__(self, src, what: str, lat, lon):
+        from .labeled import DataArray
+        self.src, self.what, self.lat, self.lon = src, what, np.asarray(lat), np.asarray(lon)
+        if isinstance(src, (str, os.PathLike)):
+            from .labeled import open_dataarray
+            self.src = src = open_dataarray(os.fspath(src))
+        self.array = isinstance(src, DataArray)
+        if self.array:
+            if tuple(src.dims) not in (("time", "channel", "lat", "lon"), ("channel", "lat", "lon")):
+                raise ValueError(f"{what}: a DataArray must have dims (time, channel, lat, lon) or (channel, lat, lon), not {tuple(src.dims)}")
+            self.names = src.channel.values.tolist()
+            self.flip = self._orientation(np.asarray(src._coords["lat"]), np.asarray(src._coords["lon"]))
+        elif hasattr(src, "channel_names") and hasattr(src, "__getitem__"):
+            self.names, self.flip = list(src.channel_names), False
+        else:
+            raise ValueError(f"{what}: expected a data source (channel_names, [time]), a DataArray or a saved forecast, not {type(src).__name__}")
+
+    def _orientation(self, lat, lon) -> bool:
+        """False: on the forecast's grid; True: the latitude axis runs the other way (compare core/models/ensemble._on_grid_of)."""
+        if lon.shape != self.lon.shape or not np.array_equal(lon, self.lon):
+            raise ValueError(f"{self.what} is on a different lon axis than the forecast")
+        if lat.shape == self.lat.shape and np.array_equal(lat, self.lat):
+            return False
+        if lat.shape == self.lat.shape and np.array_equal(lat[::-1], self.lat):
+            return True
+        raise ValueError(f"{self.what} is on a different lat axis than the forecast")
+
+    def at(self, time, names) -> np.ndarray:
+        """The (len(names), H, W) float32 state at ``time``."""
+        idx = [self.names.index(n) for n in names]
+        if self.array:
+            da = self.src
+            if "time" in da.dims:
+                times = np.asarray(da._coords["time"]).astype("datetime64[s]")
+                hit = np.nonzero(times == np.datetime64(time, "s"))[0]
+                if hit.size == 0:
+                    raise ValueError(f"{self.what} holds no entry for {time}")
+                a = np.asarray(da.values[int(hit[-1])])
+            else:
+                a = np.asarray(da.values)
+        else:
+            a = np.asarray(self.src[time])
+            if a.shape[-2] == len(self.lat) + 1 == 721:
+                a = a[..., :720, :]       # 0.25-degree source, grid without the south-pole row (datasource.get_initial_condition_for_model)
+            if a.shape[-2:] != (len(self.lat), len(self.lon)):
+                raise ValueError(f"{self.what} delivers {a.shape[-2:]} fields for a {len(self.lat)} x {len(self.lon)} forecast")
+        a = a[idx]
+        if self.flip:
+            a = a[:, ::-1]
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def default_truth(gm):
+    """The model's own kind of data source for its OUTPUT channels, built the way the model builds its own."""
+    from .datasource import get_data_source
+    return get_data_source(gm.model.out_channel_names, initial_condition_source=gm.ic_source, geom=getattr(gm.model, "geom", None),
+                           state_fn=getattr(gm.model, "synthetic_state", None))
+
+
+def _world_size() -> int:
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def check_request(n_members: int, out_names, channels=None) -> None:
+    """The refusals that need no device."""
+    if _world_size() > 1:
+        raise NotImplementedError("scores are made on one GPU from members that all lie there; members sharded over the ranks of a "
+                                  "process group are out of scope (DESIGN.md 18)")
+    if not 1 <= int(n_members) <= MAX_MEMBERS:
+        raise ValueError(f"n_members = {n_members}: 1 to {MAX_MEMBERS} members can be scored (SKSCORE_MAX_MEMBERS)")
+    missing = [c for c in (channels or []) if c not in list(out_names)]
+    if missing:
+        raise ValueError(f"channels {missing} are not output channels of this model")
+
+
+class LeadScorer:
+    """Scores one lead time after the other on the device and gathers the per-channel sums.  ``names``: the forecast's channels in
+    the order of its (C, H, W) states; the channels scored are those the truth (and the climatology) also holds, restricted to
+    ``channels`` when given."""
+
+    def __init__(self, model_name, names, lat, lon, n_members, truth, climatology=None, channels=None, device="cuda:0", forecast_id=""):
+        check_request(n_members, names, channels)
+        if truth is None:
+            raise ValueError("scores need a truth: a data source, a DataArray or a saved forecast")
+        self.model_name, self.names, self.M, self.forecast_id = model_name, list(names), int(n_members), forecast_id
+        self.lat, self.lon = np.asarray(lat, np.float64), np.asarray(lon)
+        self.truth = _Fields(truth, "truth", lat, lon)
+        self.clim = _Fields(climatology, "climatology", lat, lon) if climatology is not None else None
+        common = [n for n in self.names if n in self.truth.names and (self.clim is None or n in self.clim.names)]
+        if not common:
+            raise ValueError("the forecast and the truth share no channel")
+        self.scored = [n for n in common if not channels or n in channels]
+        if not self.scored:
+            raise ValueError(f"none of the channels {list(channels)} is in both the forecast and the truth")
+        self.flags = DET | CRPS | (ACC if self.clim is not None else 0) | ((VAR | RANK) if self.M > 1 else 0)
+        self.device = torch.device(device)
+        self.weights_host = area_weights(self.lat)
+        self.times, self.sums, self.counts = [], [], []
+        self._dev = None
+
+    def _buffers(self):
+        if self._dev is None:
+            C, H, W, dev = len(self.names), len(self.lat), len(self.lon), self.device
+            self._dev = dict(w=torch.from_numpy(self.weights_host).to(dev), truth=torch.zeros((C, H, W), dtype=torch.float32, device=dev),
+                             clim=torch.zeros((C, H, W), dtype=torch.float32, device=dev) if self.clim is not None else None,
+                             out=torch.zeros((C, len(SLOTS)), dtype=torch.float64, device=dev),
+                             counts=torch.zeros((C, H, self.M + 1), dtype=torch.int32, device=dev) if self.M > 1 else None,
+                             ws=torch.empty(C * H * PARTIALS, dtype=torch.float64, device=dev))
+            self._idx = [self.names.index(n) for n in self.scored]
+            self._idx_dev = torch.tensor(self._idx, device=dev)
+        return self._dev
+
+    def _upload(self, fields: _Fields, time, dst: torch.Tensor):
+        dst[self._idx_dev] = torch.from_numpy(fields.at(time, self.scored)).to(self.device)
+
+    def add(self, time, states, table=None) -> None:
+        """Score the M device states (C, H, W) of valid time ``time``: the truth (and climatology) of that time is uploaded into the
+        rows of the scored channels, ONE kernel pass reads members and truth, and the per-channel sums cross to the host."""
+        from .ensemble import member_table
+        if len(states) != self.M:
+            raise ValueError(f"{len(states)} states for a scorer of {self.M} members")
+        b = self._buffers()
+        self._upload(self.truth, time, b["truth"])
+        if self.clim is not None:
+            self._upload(self.clim, time, b["clim"])
+        table = member_table(states) if table is None else table
+        # one call per run of neighbouring scored channels (usually one: every channel)
+        runs, start = [], 0
+        for k in range(1, len(self._idx) + 1):
+            if k == len(self._idx) or self._idx[k] != self._idx[k - 1] + 1:
+                runs.append((self._idx[start], k - start))
+                start = k
+        H = len(self.lat)
+        for c0, nc in runs:
+            score(states, table, b["truth"], b["w"], b["out"][c0:c0 + nc], b["ws"], self.flags, clim=b["clim"],
+                  counts=None if b["counts"] is None else b["counts"][c0:c0 + nc], c0=c0, nc=nc)
+        self.times.append(time)
+        self.sums.append(b["out"][self._idx_dev].cpu().numpy())
+        if b["counts"] is not None:
+            self.counts.append(b["counts"][self._idx_dev].cpu().numpy().reshape(len(self._idx), H, self.M + 1))
+
+    def result(self) -> Scores:
+        wanted = [k for k, need in zip(SLOTS, (DET, DET, DET, VAR, CRPS, CRPS, CRPS, ACC, ACC, ACC)) if self.flags & need]
+        sums = np.stack(self.sums) if self.sums else np.zeros((0, len(self.scored), len(SLOTS)))          # (time, channel, slot)
+        sums = np.transpose(sums, (2, 0, 1))[[SLOTS.index(k) for k in wanted]]
+        rc = rh = None
+        if self.M > 1:
+            per_row = np.stack(self.counts).astype(np.int64) if self.counts else np.zeros((0, len(self.scored), len(self.lat), self.M + 1), np.int64)
+            rc = per_row.sum(axis=2)
+            w = self.weights_host
+            rh = np.einsum("j,tcjr->tcr", w, per_row.astype(np.float64)) / (len(self.lon) * w.sum())
+        return Scores(self.model_name, self.M, self.times, self.scored, sums, wanted, rc, rh, self.forecast_id)
+
+
+def _finish(scores: Scores, save: bool, save_config):
+    from .common import OUTPUT_DIR, generate_forecast_id
+    cfg = save_config if save_config is not None else {}
+    if save:
+        cfg.setdefault("forecast_id", generate_forecast_id())
+        scores.forecast_id = cfg["forecast_id"]
+        scores.path = scores.save(cfg.get("output_dir") or OUTPUT_DIR)
+    return scores
+
+
+def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels=None, save: bool = False,
+                 save_config: dict | None = None) -> Scores:
+    """``GlobalModel.verify`` (core/models/base.py has the user-facing description)."""
+    from .datasource import get_initial_condition_for_model
+    model = gm.model
+    check_request(1, model.out_channel_names, channels)
+    if n_steps < 0:
+        raise ValueError("n_steps >= 0")
+    scorer = LeadScorer(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1,
+                        default_truth(gm) if truth is None else truth, climatology, channels, device=model.device)
+    if torch.device(model.device).type != "cuda":
+        raise RuntimeError("verify scores the forecast with HIP kernels where it lies: the model must be on a GPU")
+    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
+    if hasattr(model, "__dict__"):
+        model._resident_state = None                       # the loop below is not a state a later rollout continues from
+    loop = model(start_time, x0)
+    try:
+        for k in range(n_steps + 1):
+            time, out, _ = next(loop)
+            state = (out[0] if out.dim() == 4 else out).contiguous()
+            scorer.add(time, [state])
+            del state, out
+    finally:
+        loop.close()
+        if hasattr(model, "__dict__"):
+            model._resident_state = None
+            model.__dict__.pop("_state_is_own_output", None)
+    return _finish(scorer.result(), save, save_config)
+
+
+def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=None, model_name: str = "") -> Scores:
+    """Scores of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file or
+    zarr store, or a list of such files (their time entries in order, duplicates of a valid time scored once).  Each time entry is
+    uploaded on its own and goes through the same kernel as ``verify``."""
+    from .labeled import DataArray, open_dataarray
+    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
+    arrays = []
+    for p in items:
+        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
+            model_name = model_name or (p.model if isinstance(p.model, str) else "")
+            p = p.prediction
+        elif isinstance(p, (str, os.PathLike)):
+            model_name = model_name or Path(p).name.split("__")[0].split(".")[0]
+            p = open_dataarray(os.fspath(p))
+        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
+            raise ValueError("score_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
+        arrays.append(p)
+    first = arrays[0]
+    names = first.channel.values.tolist()
+    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
+    scorer = LeadScorer(model_name or "forecast", names, lat, lon, 1, truth, climatology, channels, device=device)
+    if scorer.device.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("score_prediction scores with HIP kernels: it needs a GPU")
+    seen = set()
+    for da in arrays:
+        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
+            raise ValueError("score_prediction: the files of one forecast must share channels and grid")
+        times = np.asarray(da._coords["time"]).astype("datetime64[s]")
+        for k, t in enumerate(times):
+            if t in seen:
+                continue
+            seen.add(t)
+            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(scorer.device)
+            scorer.add(t.astype(datetime.datetime), [state])
+            del state
+    return scorer.result()

@@ -1,0 +1,91 @@
+"""``verify`` command line: the options of ``forecast`` (skyrim_amd/forecast.py: same names, short flags and defaults) plus the size of
+the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
+channels to print.  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
+``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
+from __future__ import annotations
+
+import datetime
+from pathlib import Path
+
+import click
+
+from .common import AVAILABLE_MODELS
+from .forecast import yesterday
+from .verify import DEFAULT_CHANNELS
+
+
+def run_verify(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
+               filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
+               seed: int = 0):
+    """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
+    from .core import Skyrim
+    from .core.models.base import adjust_lead_time
+    if list_models:
+        print("Available models:", Skyrim.list_available_models())
+        return None
+    model = Skyrim(model_name, ic_source=initial_conditions)
+    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
+    step_h = model.model.time_step.total_seconds() / 3600
+    n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+    if n_steps < 1:
+        raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
+    scored = filter_vars.split(",") if bool(filter_vars) else None
+    cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
+    if members == 1:
+        scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg)
+    else:
+        ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed, products=(),
+                                      channels=scored, climatology=climatology, scores=True, save_config=cfg)
+        scores = ens.scores
+        scores.path = scores.save(cfg["output_dir"])
+    return scores
+
+
+def lines(scores, channels) -> list[str]:
+    """One line per lead time and chosen channel: every metric of the table."""
+    names = [c for c in channels if c in scores.channels] or scores.channels[:4]
+    metrics = scores.table.metric.values.tolist()
+    out = []
+    for t, time in enumerate(scores.times):
+        lead = (time - scores.times[0]).total_seconds() / 3600
+        for c in names:
+            vals = scores.table.values[:, t, scores.channels.index(c)]
+            out.append(f"+{lead:g}h {c}: " + " ".join(f"{m}={v:.6g}" for m, v in zip(metrics, vals)))
+    return out
+
+
+@click.command(name="verify")
+@click.option("--model_name", "-m", type=click.Choice(AVAILABLE_MODELS, case_sensitive=False), default="pangu", help="Select model")
+@click.option("--date", "-d", type=str, default=yesterday, help="YYYYMMDD")
+@click.option("--time", "-t", type=str, default="0000", help="HHMM")
+@click.option("--lead_time", "-l", type=int, default=6, help="Lead time in hours, rounded up to whole 6-h steps; every lead time from 0 to this one is scored")
+@click.option("--list_models", "-lm", is_flag=True, help="List all available models and exit")
+@click.option("--initial_conditions", "-ic", type=click.Choice(["cds", "ifs", "gfs"], case_sensitive=False), default="gfs",
+              help="Initial conditions provider; the truth at the valid times comes from the same source.")
+@click.option("--output_dir", "-o", type=str, default="", help="Output directory (local path)")
+@click.option("--filter_vars", "-f", type=str, default="", 
+              help="Variables that enter the scores and the JSON file, such as t2m,z500 (default: every one the truth holds).  In 'forecast' "
+                   "the same flag chooses what is saved; nothing but the scores is saved here.  See --channels for what is printed.")
+@click.option("--modal", "-mo", is_flag=True, help="(reference only) run on Modal -- not available in this build")
+@click.option("--members", "-n", type=int, default=1, help="Ensemble members to score, 1-64; 1 = the deterministic forecast")
+@click.option("--climatology", type=click.Path(exists=True), default=None, help="Saved (channel, lat, lon) or (time, ...) climatology for the ACC")
+@click.option("--channels", "-c", type=str, default=",".join(DEFAULT_CHANNELS), 
+              help="Which of the scored variables to print a line for, where the model has them; does not change the JSON file")
+@click.option("--perturb_scale", type=float, default=1e-3, help="Perturbation amplitude in units of each channel's sigma (members > 1)")
+@click.option("--seed", type=int, default=0, help="Seed of the perturbations (32-bit)")
+def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
+           perturb_scale, seed):
+    if modal:
+        raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
+    scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
+                        channels, perturb_scale, seed)
+    if scores is None:
+        return None
+    for ln in lines(scores, [c for c in channels.split(",") if c]):
+        click.echo(ln)
+    click.echo(scores.path)
+    return scores.path
+
+
+if __name__ == "__main__":
+    verify()
