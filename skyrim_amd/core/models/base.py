@@ -116,7 +116,9 @@ class GlobalModel:
     def ensemble_forecast(self, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3,
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
-                          save_config: dict | None = None, truth=None, climatology=None, scores: bool = False):
+                          save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
+                          perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+                          perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
         own TimeLoop generator, and at each lead time one HIP pass over the members gives the ``products`` (any of mean, spread, min, max),
@@ -124,11 +126,18 @@ class GlobalModel:
         values per channel).  Returns an ``ensemble.EnsembleForecast``; its time axis holds the initial condition and every
         ``save_every``-th step.  ``save=True`` writes one file per product and saved step, model field ``{model}-ens{M}-{product}``.
         ``scores=True`` scores every lead time against ``truth`` right after its statistics, on the members where they lie
-        (``verify`` below has the forms of ``truth`` and ``climatology``); the ``verify.Scores`` land in ``EnsembleForecast.scores``."""
+        (``verify`` below has the forms of ``truth`` and ``climatology``); the ``verify.Scores`` land in ``EnsembleForecast.scores``.
+        ``perturbation="spherical"`` replaces the grid-point white noise z by an isotropic Gaussian random field per (history level,
+        channel) with unit pointwise variance, correlation length ``length_scale_km`` and spectrum
+        (kappa^2 + l (l + 1))^(-alpha / 2) truncated at ``lmax`` (default min(256, n_lat_full, n_lon / 2)), synthesised on the device
+        (skyrim_amd/noise.py); it needs a pole-to-pole equiangular grid or its first rows.  ``perturb_channels`` lists the
+        input channels that are perturbed, for either kind; the others get amplitude exactly 0."""
         from ... import ensemble
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
-                            save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores)
+                            save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
+                            perturbation=perturbation, length_scale_km=length_scale_km, alpha=alpha, lmax=lmax,
+                            perturb_channels=perturb_channels)
 
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
                save: bool = False, save_config: dict | None = None):

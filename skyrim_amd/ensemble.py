@@ -4,7 +4,8 @@ Three layers:
 
 * the binding of libskyrim_ens.so (``SPEC``, ``load_library``, ``perturb``, ``stats``, ``member_table``); the same calls are
   ``torch.ops.skyrim_hip.ens_perturb / ens_stats`` (skyrim_amd/ops.py);
-* ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb``, ONE TimeLoop
+* ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb`` (white noise) or
+  ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), ONE TimeLoop
   generator per member advanced step-major (all members one step, then the statistics of that lead time), so only the members'
   current states are alive on the GPU;
 * ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
@@ -156,6 +157,10 @@ class EnsembleForecast:
     paths: list = field(default_factory=list)
     forecast_id: str = ""
     scores: object = None        # verify.Scores with ``scores=True``
+    perturbation: str = "white"  # "white" (skens_perturb) or "spherical" (skyrim_amd/noise.py)
+    length_scale_km: float = 500.0
+    alpha: float = 2.0
+    lmax: object = None          # the truncation used, spherical only
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -176,8 +181,10 @@ def _world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members):
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, perturbation="white",
+             length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised."""
+    from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
         raise NotImplementedError("ensemble_forecast runs all members on one GPU; under a process group of more than one rank use "
@@ -205,6 +212,7 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     missing = [c for c in (channels or []) if c not in names]
     if missing:
         raise ValueError(f"channels {missing} are not output channels of this model")
+    noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
     saved = list(range(0, n_steps + 1, save_every))
     if keep_members:
         need = int(n_members) * len(saved) * len(names) * len(model.grid.lat) * len(model.grid.lon) * 4
@@ -217,14 +225,18 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
 
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
-        save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False) -> EnsembleForecast:
+        save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
+        perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+        perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
+    from . import noise
     from .common import generate_forecast_id, save_forecast
     from .datasource import get_initial_condition_for_model
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members)
+                                                  keep_members, perturbation, length_scale_km, alpha, lmax, perturb_channels)
+    plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
     names = list(model.out_channel_names)
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
@@ -250,13 +262,19 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     fid = cfg["forecast_id"]
     zarr = (cfg.get("file_type") or "netcdf") == "zarr"
 
+    if plan.channel_mask is not None and plan.kind == "white":
+        std = torch.where(torch.from_numpy(plan.channel_mask).to(dev), std, torch.zeros_like(std))        # amplitude exactly 0 elsewhere
+    spherical = noise.Perturber(plan, x0, std, float(perturb_scale), int(seed)) if plan.kind == "spherical" else None
     loops = []
     for m in range(M):
         xm = torch.empty_like(x0)
-        perturb(x0, std, xm, hw, float(perturb_scale), int(seed), m)
+        if spherical is not None:
+            spherical.member(m, xm)
+        else:
+            perturb(x0, std, xm, hw, float(perturb_scale), int(seed), m)
         loops.append(model(start_time, xm))
         del xm
-    del x0
+    del x0, spherical                                      # (with it the work buffers of one member's synthesis)
     n_saved, C = len(saved), len(names)
     host = {p: np.empty((n_saved, C, n_lat, n_lon), np.float32) for p in products}
     host_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in exceed.items()}
@@ -324,7 +342,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **grid))
         return da.sel(channel=list(channels)) if channels and dim == "channel" else da
 
-    ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid)
+    ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=plan.kind,
+                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None)
     if scorer is not None:
         ens.scores = scorer.result()
         ens.scores.forecast_id = fid

@@ -16,6 +16,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     fengwu_layer_norm / fengwu_window_attention             (FengWu, include/skyrim_fengwu.h)
     ens_perturb / ens_stats                              (ensemble members and statistics, include/skyrim_ens.h)
     score_fields                                         (forecast scores against a truth state, include/skyrim_score.h)
+    noise_coeffs / noise_apply                           (spherical perturbations, include/skyrim_noise.h)
 """
 from __future__ import annotations
 
@@ -522,6 +523,18 @@ def _score_fields(members, table, truth, weights, out, workspace, flags: int, cl
     verify.score(list(members), table, truth, weights, out, workspace, flags, clim, counts, c0, nc)
 
 
+# ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
+def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
+    """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
+    from . import noise
+    noise.coeffs(out, sigma, F, f_first, seed, member_first)
+
+
+def _noise_apply(x0, y, g, out, chan_stride: int) -> None:
+    from . import noise
+    noise.apply(x0, y, g, out, chan_stride)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -570,6 +583,8 @@ _SCHEMAS = [
      "Tensor(e!)? exceed, float[] thresholds, Tensor(f!)? quant, float[] levels) -> ()", _ens_stats),
     ("score_fields(Tensor[] members, Tensor table, Tensor truth, Tensor weights, Tensor(a!)? out, Tensor(b!) workspace, int flags, Tensor? clim, "
      "Tensor(c!)? counts, int c0, int nc) -> ()", _score_fields),
+    ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
+    ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 

@@ -1,6 +1,7 @@
 """``verify`` command line: the options of ``forecast`` (skyrim_amd/forecast.py: same names, short flags and defaults) plus the size of
 the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
-channels to print.  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
+channels to print, and the kind of perturbation (``--perturbation spherical --length_scale_km --lmax``: this is where spread against skill is
+tuned; the ``ensemble`` command keeps white noise).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
 ``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
 from __future__ import annotations
 
@@ -16,7 +17,7 @@ from .verify import DEFAULT_CHANNELS
 
 def run_verify(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
                filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
-               seed: int = 0):
+               seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
     from .core.models.base import adjust_lead_time
@@ -35,7 +36,8 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
         scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg)
     else:
         ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed, products=(),
-                                      channels=scored, climatology=climatology, scores=True, save_config=cfg)
+                                      channels=scored, climatology=climatology, scores=True, save_config=cfg, perturbation=perturbation,
+                                      length_scale_km=length_scale_km, lmax=lmax)
         scores = ens.scores
         scores.path = scores.save(cfg["output_dir"])
     return scores
@@ -73,12 +75,16 @@ def lines(scores, channels) -> list[str]:
               help="Which of the scored variables to print a line for, where the model has them; does not change the JSON file")
 @click.option("--perturb_scale", type=float, default=1e-3, help="Perturbation amplitude in units of each channel's sigma (members > 1)")
 @click.option("--seed", type=int, default=0, help="Seed of the perturbations (32-bit)")
+@click.option("--perturbation", type=click.Choice(["white", "spherical"]), default="white",
+              help="Perturbation kind (members > 1): grid-point white noise, or spatially correlated fields on the sphere")
+@click.option("--length_scale_km", type=float, default=500.0, help="Correlation length of the spherical perturbations in km")
+@click.option("--lmax", type=int, default=None, help="Spectral truncation of the spherical perturbations (default: min(256, n_lat, n_lon / 2))")
 def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
-           perturb_scale, seed):
+           perturb_scale, seed, perturbation, length_scale_km, lmax):
     if modal:
         raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
     scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
-                        channels, perturb_scale, seed)
+                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax)
     if scores is None:
         return None
     for ln in lines(scores, [c for c in channels.split(",") if c]):
