@@ -117,8 +117,8 @@ class GlobalModel:
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-                          perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
-                          perturb_channels: List[str] | None = None):
+                          tracks: bool = False, track_config=None, perturbation: str = "white", length_scale_km: float = 500.0,
+                          alpha: float = 2.0, lmax: int | None = None, perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
         own TimeLoop generator, and at each lead time one HIP pass over the members gives the ``products`` (any of mean, spread, min, max),
@@ -131,13 +131,27 @@ class GlobalModel:
         channel) with unit pointwise variance, correlation length ``length_scale_km`` and spectrum
         (kappa^2 + l (l + 1))^(-alpha / 2) truncated at ``lmax`` (default min(256, n_lat_full, n_lon / 2)), synthesised on the device
         (skyrim_amd/noise.py); it needs a pole-to-pole equiangular grid or its first rows.  ``perturb_channels`` lists the
-        input channels that are perturbed, for either kind; the others get amplitude exactly 0."""
+        input channels that are perturbed, for either kind; the others get amplitude exactly 0.  ``tracks=True`` detects cyclone centres in
+        every member at every lead time, right after the scores and on the same states (skyrim_amd/tracks.py, DESIGN.md 20;
+        ``track_config``: a ``tracks.TrackerConfig`` or a dict of its fields); the linked ``tracks.Tracks`` land in
+        ``EnsembleForecast.tracks``."""
         from ... import ensemble
+        extra = dict(tracks=True, track_config=track_config) if tracks else {}
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
                             perturbation=perturbation, length_scale_km=length_scale_km, alpha=alpha, lmax=lmax,
-                            perturb_channels=perturb_channels)
+                            perturb_channels=perturb_channels, **extra)
+
+    def track_cyclones(self, start_time: datetime.datetime, n_steps: int = 4, config=None, save: bool = False, save_config: dict | None = None):
+        """Cyclone tracks of the deterministic forecast over the lead times 0 .. ``n_steps`` (skyrim_amd/tracks.py).  The
+        model's TimeLoop is advanced and every state is searched where it lies in HBM -- a pressure minimum with cyclonic 850-hPa
+        vorticity, 10-m wind and (where the model has the levels) a warm core nearby -- so that only the candidates' records cross to the
+        host, which links them into tracks.  ``config``: a ``tracks.TrackerConfig`` or a dict of its fields.  Returns ``tracks.Tracks``;
+        ``save=True`` writes ``{model}-tracks.json`` under the forecast id directory.  A model without msl, u10m, v10m, u850 and v850
+        (DLWP) is refused with ValueError before the device is touched."""
+        from ... import tracks
+        return tracks.track_model(self, start_time, n_steps=n_steps, config=config, save=save, save_config=save_config)
 
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
                save: bool = False, save_config: dict | None = None):

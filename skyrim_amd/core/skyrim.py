@@ -55,6 +55,18 @@ class Skyrim:
         from .. import verify
         return verify.score_prediction(pred, truth, climatology=climatology, device=device, **kwargs)
 
+    def track_cyclones(self, start_time: datetime.datetime, n_steps: int = 4, **kwargs):
+        """Cyclone tracks of the single model's forecast (``GlobalModel.track_cyclones`` has the arguments) as a ``tracks.Tracks``.
+        ``ensemble_forecast(..., tracks=True)`` tracks every member of an ensemble."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.track_cyclones(start_time, n_steps=n_steps, **kwargs)
+
+    @staticmethod
+    def track_prediction(pred, config=None, device="cuda:0", **kwargs):
+        """Cyclone tracks of a forecast that is already in memory or on disk (``tracks.track_prediction``)."""
+        from .. import tracks
+        return tracks.track_prediction(pred, config=config, device=device, **kwargs)
+
     def predict(self, date: str, time: str, lead_time: int = 6, save: bool = False, save_config: dict | None = None):
         """Predict a single lead-time snapshot, optionally saving every intermediate step.
         date: YYYYMMDD, time: HHMM, lead_time in hours (clipped down to a multiple of 6, at least 6)."""

@@ -161,6 +161,7 @@ class EnsembleForecast:
     length_scale_km: float = 500.0
     alpha: float = 2.0
     lmax: object = None          # the truncation used, spherical only
+    tracks: object = None        # tracks.Tracks with ``tracks=True``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -226,7 +227,7 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+        tracks: bool = False, track_config=None, perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
@@ -245,6 +246,10 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         from . import verify
         scorer = verify.LeadScorer(gm.model_name, names, model.grid.lat, model.grid.lon, M, verify.default_truth(gm) if truth is None else truth,
                                    climatology, channels, device=model.device)
+    tracker = None
+    if tracks:
+        from . import tracks as tracking
+        tracker = tracking.LeadTracker(gm.model_name, names, model.grid.lat, model.grid.lon, M, track_config, device=model.device)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -303,6 +308,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {k}")
             if scorer is not None:
                 scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
+            if tracker is not None:
+                tracker.add(time, states, table)           # cyclone candidates of this lead time: only their records leave the device
             if keep:
                 s = saved.index(k)
                 times.append(time)
@@ -350,6 +357,12 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         if save:
             from .common import OUTPUT_DIR
             paths.append(ens.scores.save(cfg.get("output_dir") or OUTPUT_DIR))
+    if tracker is not None:
+        ens.tracks = tracker.result()
+        ens.tracks.forecast_id = fid
+        if save:
+            from .common import OUTPUT_DIR
+            paths.append(ens.tracks.save(cfg.get("output_dir") or OUTPUT_DIR))
     for p in products:
         setattr(ens, p, labelled(host[p], "channel", names))
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}

@@ -17,6 +17,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     ens_perturb / ens_stats                              (ensemble members and statistics, include/skyrim_ens.h)
     score_fields                                         (forecast scores against a truth state, include/skyrim_score.h)
     noise_coeffs / noise_apply                           (spherical perturbations, include/skyrim_noise.h)
+    track_detect                                         (cyclone candidates of M states, include/skyrim_track.h)
 """
 from __future__ import annotations
 
@@ -523,6 +524,14 @@ def _score_fields(members, table, truth, weights, out, workspace, flags: int, cl
     verify.score(list(members), table, truth, weights, out, workspace, flags, clim, counts, c0, nc)
 
 
+# ---- cyclone detection ---------------------------------------------------------------------------------------------------------- #
+def _track_detect(members, table, channels, band, thresholds, h_msl, h_vort, h_wind, h_core, rowc, records, count, workspace) -> None:
+    """``table``: ensemble.member_table(members); the tables and ``rowc`` are those of tracks.geometry on the device."""
+    from . import tracks
+    tracks.detect(list(members), table, list(channels), list(band), list(thresholds), h_msl, h_vort, h_wind, h_core, rowc, records, count,
+                  workspace)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -583,6 +592,8 @@ _SCHEMAS = [
      "Tensor(e!)? exceed, float[] thresholds, Tensor(f!)? quant, float[] levels) -> ()", _ens_stats),
     ("score_fields(Tensor[] members, Tensor table, Tensor truth, Tensor weights, Tensor(a!)? out, Tensor(b!) workspace, int flags, Tensor? clim, "
      "Tensor(c!)? counts, int c0, int nc) -> ()", _score_fields),
+    ("track_detect(Tensor[] members, Tensor table, int[] channels, int[] band, float[] thresholds, Tensor h_msl, Tensor h_vort, Tensor h_wind, "
+     "Tensor? h_core, Tensor rowc, Tensor(a!) records, Tensor(b!) count, Tensor(c!) workspace) -> ()", _track_detect),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]
