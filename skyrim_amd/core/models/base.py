@@ -117,7 +117,8 @@ class GlobalModel:
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-                          tracks: bool = False, track_config=None, perturbation: str = "white", length_scale_km: float = 500.0,
+                          tracks: bool = False, track_config=None, derived: List[str] | None = None, perturbation: str = "white",
+                          length_scale_km: float = 500.0,
                           alpha: float = 2.0, lmax: int | None = None, perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
@@ -134,9 +135,14 @@ class GlobalModel:
         input channels that are perturbed, for either kind; the others get amplitude exactly 0.  ``tracks=True`` detects cyclone centres in
         every member at every lead time, right after the scores and on the same states (skyrim_amd/tracks.py, DESIGN.md 20;
         ``track_config``: a ``tracks.TrackerConfig`` or a dict of its fields); the linked ``tracks.Tracks`` land in
-        ``EnsembleForecast.tracks``."""
+        ``EnsembleForecast.tracks``.  ``derived=[...]`` names derived fields (``ws10m``, ``ws100m``, ``ws<level>``, ``thk<a>_<b>``, ``vo<X>``,
+        ``div<X>``, ``ivt``, ``ivtu``, ``ivtv``, ``iwv``: skyrim_amd/derived.py) that are formed from every member on the device at
+        each lead time; the same ``products`` of them, ``exceed`` / ``quantiles`` under their names and, with ``scores=True``, their scores land
+        in ``EnsembleForecast.derived``."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
+        if derived is not None:
+            extra["derived"] = derived
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -152,6 +158,16 @@ class GlobalModel:
         (DLWP) is refused with ValueError before the device is touched."""
         from ... import tracks
         return tracks.track_model(self, start_time, n_steps=n_steps, config=config, save=save, save_config=save_config)
+
+    def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields: List[str] = (), save: bool = False,
+                      save_config: dict | None = None):
+        """Derived fields of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/derived.py): wind speed
+        (``ws10m``, ``ws100m``, ``ws<level>``), thickness (``thk<a>_<b>``), vorticity and divergence (``vo<X>``, ``div<X>``) and the column
+        integrals ``ivt``, ``ivtu``, ``ivtv``, ``iwv``.  The model's TimeLoop is advanced and every state is derived where it lies in HBM; only
+        the derived planes cross to the host.  Returns DataArray(time, channel=fields, lat, lon); ``save=True`` writes it as the forecast of
+        ``{model}-derived``.  A field whose input channels the model lacks is refused with ValueError before the device is touched."""
+        from ... import derived
+        return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config)
 
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
                save: bool = False, save_config: dict | None = None):

@@ -129,6 +129,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator track_cyclones advances: "
                                   "track its forecast with skyrim_amd.tracks.track_prediction(forecast_or_saved_files)")
 
+    def derive_fields(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
+                                  "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):
         """Final two time levels + per-step file paths; the stepper state is fed back step to step (never through a file).

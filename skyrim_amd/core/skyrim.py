@@ -61,6 +61,19 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.track_cyclones(start_time, n_steps=n_steps, **kwargs)
 
+    def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields=(), **kwargs):
+        """Derived fields (wind speed, thickness, vorticity, divergence, vapour transport) of the single model's forecast as a
+        DataArray(time, channel=fields, lat, lon) (``GlobalModel.derive_fields`` has the arguments).
+        ``ensemble_forecast(..., derived=[...])`` gives their ensemble products."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.derive_fields(start_time, n_steps=n_steps, fields=fields, **kwargs)
+
+    @staticmethod
+    def derive_prediction(pred, fields, device="cuda:0"):
+        """Derived fields of a forecast that is already in memory or on disk (``derived.derive_prediction``)."""
+        from .. import derived
+        return derived.derive_prediction(pred, fields, device=device)
+
     @staticmethod
     def track_prediction(pred, config=None, device="cuda:0", **kwargs):
         """Cyclone tracks of a forecast that is already in memory or on disk (``tracks.track_prediction``)."""

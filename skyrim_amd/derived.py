@@ -1,0 +1,546 @@
+"""Derived fields on the device (include/skyrim_derive.h): wind speed, thickness, integrated vapour transport, vorticity
+and divergence of forecast states, made where the states lie in HBM as D compact channels per member, so that the ensemble statistics
+and the scorer read them like raw channels.
+
+Layers:
+
+* the binding of libskyrim_derive.so (``SPEC``, ``load_library``, ``run``); the same call is ``torch.ops.skyrim_hip.derive_fields``.
+  Derivation has no CPU fallback;
+* the catalogue: ``plan`` resolves user-facing names (``ws10m``, ``thk500_1000``, ``vo850``, ``div850``, ``ivt`` ...) against a model's
+  channels into a program of ops, ``row_table`` makes the row coefficients of vorticity and divergence in float64;
+* the drivers: ``LeadDeriver`` (what ``ensemble.run`` calls at every lead time with ``derived=[...]``), ``TruthDeriver`` (the hook that
+  lets ``verify.LeadScorer`` score derived fields against a truth of raw channels), ``derive_model`` (``GlobalModel.derive_fields``)
+  and ``derive_prediction`` for forecasts that are already on disk.
+"""
+from __future__ import annotations
+
+import ctypes
+import datetime
+import os
+import re
+from dataclasses import dataclass, field
+from pathlib import Path
+
+import numpy as np
+
+from . import native
+
+MAX_MEMBERS, MAX_OPS, MAX_LEVELS = 64, 16, 16                   # include/skyrim_derive.h SKDERIVE_MAX_*
+SPEED, DIFF, COLUMN, VORTDIV = 1, 2, 3, 4                       # SKDERIVE_SPEED ...
+EDGE_ONESIDED, EDGE_POLE = 1, 2                                 # SKDERIVE_EDGE_*
+RESULTS = {SPEED: 1, DIFF: 1, COLUMN: 4, VORTDIV: 2}            # output slots of an op
+EARTH_RADIUS_M = 6371000.0
+GRAVITY = 9.80665
+COLUMN_FIELDS = ("ivtu", "ivtv", "ivt", "iwv")                  # in the order of a COLUMN op's slots
+_P = ctypes.c_void_p
+
+
+class OpDesc(ctypes.Structure):
+    """skderive_op."""
+    _fields_ = [("kind", ctypes.c_int32), ("n_levels", ctypes.c_int32), ("in_a", ctypes.c_int32 * MAX_LEVELS),
+                ("in_b", ctypes.c_int32 * MAX_LEVELS), ("in_c", ctypes.c_int32 * MAX_LEVELS), ("weight", ctypes.c_float * MAX_LEVELS),
+                ("out", ctypes.c_int32 * 4)]
+
+
+class DeriveDesc(ctypes.Structure):
+    """skderive_desc."""
+    _fields_ = [("members", _P), ("M", ctypes.c_int), ("member_align", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int),
+                ("W", ctypes.c_int), ("D", ctypes.c_int), ("out", _P), ("member_stride", ctypes.c_size_t), ("rowc", _P),
+                ("edge_first", ctypes.c_int), ("edge_last", ctypes.c_int), ("n_ops", ctypes.c_int), ("ops", OpDesc * MAX_OPS)]
+
+
+SPEC = native.Spec("skyrim_derive", "SKYRIM_DERIVE_LIB", "skderive", 1, {       # include/skyrim_derive.h SKDERIVE_ABI_VERSION
+    "skderive_abi_version": (ctypes.c_int, []),
+    "skderive_run": (ctypes.c_int, [ctypes.POINTER(DeriveDesc), _P]),
+}, " -- derived fields have no torch fallback")
+EXPORTS, ABI_VERSION = SPEC.exports, SPEC.abi
+
+_lib = None
+
+
+def load_library() -> ctypes.CDLL:
+    """libskyrim_derive.so (built in-tree by ``__graft_entry__.build()`` / ``make -C skyrim_amd/csrc``)."""
+    global _lib
+    if _lib is None:
+        _lib = native.load(SPEC)
+    return _lib
+
+
+# ---- the program ------------------------------------------------------------------------------------------------------------------------- #
+@dataclass(frozen=True)
+class Op:
+    """One op of a program.  ``inputs``: (u, v) for SPEED and VORTDIV, (a, b) for DIFF, (q levels, u levels, v levels) for COLUMN --
+    channel indices; ``outputs``: one slot per result (``RESULTS``), -1 = not computed; ``weights``: the fp32 level weights of COLUMN."""
+    kind: int
+    inputs: tuple
+    outputs: tuple
+    weights: tuple = ()
+
+
+def encode(ops) -> tuple:
+    """(ints, floats): the flat form ``torch.ops.skyrim_hip.derive_fields`` takes.  Per op: kind, L, four slots, then the inputs (two
+    channels, or 3 L for COLUMN: q, u, v); the floats are the COLUMN weights, op after op."""
+    ints, floats = [], []
+    for op in ops:
+        column = op.kind == COLUMN
+        L = len(op.inputs[0]) if column else 0
+        slots = list(op.outputs) + [-1] * (4 - len(op.outputs))
+        ints += [int(op.kind), L] + [int(s) for s in slots]
+        ints += [int(c) for level in op.inputs for c in level] if column else [int(op.inputs[0]), int(op.inputs[1])]
+        floats += [float(w) for w in op.weights]
+    return ints, floats
+
+
+def decode(ints, floats) -> list:
+    ops, i, f = [], 0, 0
+    ints, floats = list(ints), list(floats)
+    while i < len(ints):
+        if i + 6 > len(ints):
+            raise ValueError("derive_fields: the program ends inside an op")
+        kind, L, slots = ints[i], ints[i + 1], ints[i + 2:i + 6]
+        i += 6
+        if kind not in RESULTS:
+            raise ValueError(f"derive_fields: unknown op kind {kind}")
+        n = 3 * L if kind == COLUMN else 2
+        if i + n > len(ints) or (kind == COLUMN and f + L > len(floats)):
+            raise ValueError("derive_fields: the program ends inside an op")
+        if kind == COLUMN:
+            ops.append(Op(kind, (tuple(ints[i:i + L]), tuple(ints[i + L:i + 2 * L]), tuple(ints[i + 2 * L:i + 3 * L])), tuple(slots),
+                          tuple(floats[f:f + L])))
+            f += L
+        else:
+            ops.append(Op(kind, (ints[i], ints[i + 1]), tuple(slots[:RESULTS[kind]])))
+        i += n
+    return ops
+
+
+def _check(t, what: str, dtype, dev):
+    import torch
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
+    return t.data_ptr()
+
+
+def describe(ops, M, C, H, W, D, member_stride, member_align=16, edges=(EDGE_POLE, EDGE_POLE)) -> DeriveDesc:
+    """The descriptor of a program, its pointers still NULL."""
+    d = DeriveDesc()
+    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride = M, member_align, C, H, W, D, member_stride
+    d.edge_first, d.edge_last = int(edges[0]), int(edges[1])
+    ops = list(ops)
+    d.n_ops = len(ops)
+    for k, op in enumerate(ops[:MAX_OPS]):
+        o = d.ops[k]
+        o.kind = op.kind
+        for r in range(4):
+            o.out[r] = int(op.outputs[r]) if r < len(op.outputs) else -1
+        if op.kind == COLUMN:
+            q, u, v = op.inputs
+            o.n_levels = len(q)
+            for l in range(min(len(q), MAX_LEVELS)):
+                o.in_a[l], o.in_b[l], o.in_c[l], o.weight[l] = q[l], u[l], v[l], op.weights[l]
+        else:
+            o.in_a[0], o.in_b[0] = op.inputs
+    return d
+
+
+def run(members, table, ops, out, rowc=None, edges=(EDGE_POLE, EDGE_POLE)) -> None:
+    """One ``skderive_run``: the program ``ops`` on the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors;
+    ``table`` = ``ensemble.member_table(members)``) into ``out``, float32 (M, D, H, W).  ``rowc``: float32 (H, 4) on the device and
+    ``edges`` = (edge_first, edge_last), needed with a VORTDIV op (``row_table``).  Queued on torch's current stream.  As in
+    ``verify.score``, the contents of ``table`` are trusted to be the addresses of ``members``."""
+    import torch
+    M, ops = len(members), list(ops)
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError(f"derive_fields: {M} members; 1 to {MAX_MEMBERS} are supported")
+    if not 1 <= len(ops) <= MAX_OPS:
+        raise ValueError(f"derive_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
+    if members[0].dim() != 3:
+        raise ValueError("derive_fields: states are (C, H, W)")
+    C, H, W = members[0].shape
+    dev = members[0].device
+    align = 16
+    for t in members:
+        if _check(t, "derive_fields: member", torch.float32, dev) % 16:
+            align = 4
+        if t.shape != members[0].shape:
+            raise ValueError("derive_fields: the members differ in shape")
+    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
+        raise ValueError("derive_fields: table must be member_table(members)")
+    po = _check(out, "derive_fields: out", torch.float32, dev)
+    if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
+        raise ValueError(f"derive_fields: out must be ({M}, D, {H}, {W})")
+    for op in ops:
+        if op.kind == COLUMN and (len(set(len(x) for x in op.inputs)) != 1 or len(op.weights) != len(op.inputs[0])
+                                  or not 2 <= len(op.weights) <= MAX_LEVELS):
+            raise ValueError(f"derive_fields: a COLUMN op has 2 to {MAX_LEVELS} levels, each with q, u, v and a weight")
+        if len(op.outputs) != RESULTS.get(op.kind, 0):
+            raise ValueError("derive_fields: an op has one slot per result (SPEED, DIFF: 1; VORTDIV: 2; COLUMN: 4)")
+    D = out.shape[1]
+    d = describe(ops, M, C, H, W, D, D * H * W, align, edges)
+    d.members, d.out = table.data_ptr(), po
+    if any(op.kind == VORTDIV for op in ops):
+        if rowc is None or tuple(rowc.shape) != (H, 4):
+            raise ValueError(f"derive_fields: vorticity and divergence need rowc ({H}, 4)")
+        d.rowc = _check(rowc, "derive_fields: rowc", torch.float32, dev)
+    lib = load_library()
+    with torch.cuda.device(dev):
+        native.check(lib.skderive_run(ctypes.byref(d), native.stream(dev)), "skderive_run", lib)
+
+
+# ---- the row coefficients of vorticity and divergence ------------------------------------------------------------------------------------- #
+def _uniform_lon(lon) -> float:
+    from .tracks import _uniform_lon as check
+    if len(lon) < 4:
+        raise ValueError("vorticity and divergence need a periodic longitude axis of at least 4 points")
+    return check(lon)
+
+
+_row_cache: dict = {}
+
+
+def row_table(lat, lon) -> tuple:
+    """(rowc float32 (H, 4), edge_first, edge_last) of include/skyrim_derive.h, made in float64 and rounded once; cached per grid.
+    Interior rows: A, B+, B-, sgn(lat) as ``tracks.row_coefficients``.  A first or last row at +-90 degrees is a pole row: its entry is
+    (f, -f, 0, 0) with f = +-cos(lat_r) / (a (1 - |sin(lat_r)|)) of the neighbouring row r, + at the north pole; any other first or last
+    row is one-sided: the same A, and B+- over the latitude step between the row and its one neighbour."""
+    lat, lon = np.asarray(lat, np.float64), np.asarray(lon, np.float64)
+    key = (lat.tobytes(), lon.tobytes())
+    hit = _row_cache.get(key)
+    if hit is not None:
+        return hit
+    H = lat.size
+    step = np.diff(lat)
+    if H < 3 or not (np.all(step > 0) or np.all(step < 0)) or np.any(np.abs(lat) > 90):
+        raise ValueError("vorticity and divergence need a strictly monotonic latitude axis in degrees of at least 3 rows")
+    dlam = _uniform_lon(lon)
+    phi = np.radians(lat)
+    a = EARTH_RADIUS_M
+    rowc = np.zeros((H, 4), np.float64)
+    edges = []
+    for j in range(H):
+        jn, js = min(j + 1, H - 1), max(j - 1, 0)
+        if j in (0, H - 1) and abs(abs(lat[j]) - 90.0) < 1e-9:
+            r = 1 if j == 0 else H - 2
+            f = np.sign(lat[j]) * np.cos(phi[r]) / (a * (1.0 - abs(np.sin(phi[r]))))
+            rowc[j] = (f, -f, 0.0, 0.0)
+            edges.append(EDGE_POLE)
+            continue
+        if j in (0, H - 1):
+            edges.append(EDGE_ONESIDED)
+        c, dphi = np.cos(phi[j]), phi[jn] - phi[js]
+        rowc[j] = (1.0 / (2 * a * c * dlam), np.cos(phi[jn]) / (a * c * dphi), np.cos(phi[js]) / (a * c * dphi), np.sign(phi[j]))
+    hit = (rowc.astype(np.float32), edges[0], edges[1])
+    _row_cache[key] = hit
+    return hit
+
+
+# ---- the catalogue ----------------------------------------------------------------------------------------------------------------------- #
+@dataclass
+class Plan:
+    """A resolved request.  ``fields``: the derived names, slot d = fields[d]; ``ops``: the program; ``inputs[name]``: the raw channels a
+    derived field reads; ``rowc / edges``: the row table when vorticity or divergence is asked for; ``levels / weights``: the pressure
+    levels (hPa) and float64 trapezoid weights of the column integrals, when asked for."""
+    fields: list
+    ops: list
+    inputs: dict
+    rowc: object = None
+    edges: tuple = (EDGE_POLE, EDGE_POLE)
+    levels: list = field(default_factory=list)
+    weights: object = None
+
+
+def column_weights(levels) -> np.ndarray:
+    """Float64 trapezoid weights w_k = 100 dp_k / g of pressure levels in hPa (ascending): half the distance to both neighbours, half an
+    interval at the ends."""
+    p = np.asarray(levels, np.float64)
+    dp = np.empty_like(p)
+    dp[0], dp[-1] = (p[1] - p[0]) / 2, (p[-1] - p[-2]) / 2
+    dp[1:-1] = (p[2:] - p[:-2]) / 2
+    return 100.0 * dp / GRAVITY
+
+
+def _height(tag: str) -> bool:
+    return tag in ("10m", "100m") or tag.isdigit()
+
+
+def _parse(name: str):
+    """(kind, raw channel names it reads or None for COLUMN, slot within the op) of a derived name; None when it is not one."""
+    if name in COLUMN_FIELDS:
+        return COLUMN, None, COLUMN_FIELDS.index(name)
+    m = re.fullmatch(r"ws(\d+m?)", name)
+    if m and _height(m.group(1)):
+        return SPEED, (f"u{m.group(1)}", f"v{m.group(1)}"), 0
+    m = re.fullmatch(r"thk(\d+)_(\d+)", name)
+    if m:
+        return DIFF, (f"z{m.group(1)}", f"z{m.group(2)}"), 0
+    m = re.fullmatch(r"(vo|div)(\d+m?)", name)
+    if m and _height(m.group(2)):
+        return VORTDIV, (f"u{m.group(2)}", f"v{m.group(2)}"), 0 if m.group(1) == "vo" else 1
+    return None
+
+
+def column_levels(names, levels=None) -> list:
+    """The pressure levels (hPa, ascending) with q, u and v among ``names`` and 300 <= level <= 1000 (or those of ``levels``)."""
+    names = set(names)
+    have = sorted(int(n[1:]) for n in names if re.fullmatch(r"q\d+", n))
+    if not have:
+        raise ValueError("the column integrals (ivt, ivtu, ivtv, iwv) need specific humidity: this model has no channel q<level> "
+                         "(q from relative humidity is out of scope)")
+    if levels is not None:
+        use = sorted(int(l) for l in levels)
+    else:
+        use = [l for l in have if 300 <= l <= 1000]
+    missing = [f"{x}{l}" for l in use for x in "quv" if f"{x}{l}" not in names]
+    if missing:
+        raise ValueError(f"the column integrals need the channels {missing}, which this model lacks")
+    if not 2 <= len(use) <= MAX_LEVELS:
+        raise ValueError(f"the column integrals run over 2 to {MAX_LEVELS} levels, not {len(use)}")
+    return use
+
+
+def plan(names, fields, lat, lon, levels=None) -> Plan:
+    """Resolve the derived ``fields`` against the channels ``names`` of a (C, H, W) state on the grid (lat, lon).  Every refusal is a
+    ValueError before the device is touched: an unknown name, a name that is one of the model's channels, missing input channels (named),
+    more than ``MAX_OPS`` ops, a grid vorticity cannot be formed on.  ``vo<X>`` and ``div<X>`` of one level share an op, and so do the
+    four column integrals."""
+    names, fields = list(names), list(fields)
+    if not fields:
+        raise ValueError("derived: at least one field")
+    if len(set(fields)) != len(fields):
+        raise ValueError(f"derived: a field is named twice in {fields}")
+    ops, inputs, merged = [], {}, {}
+    out = Plan(fields, ops, inputs)
+    for slot, name in enumerate(fields):
+        if name in names:
+            raise ValueError(f"derived: {name!r} is a channel of this model, not a derived field")
+        parsed = _parse(name)
+        if parsed is None:
+            raise ValueError(f"derived: unknown field {name!r}; known are ws10m, ws100m, ws<level>, thk<a>_<b>, vo<X>, div<X> "
+                             f"(X a level, 10m or 100m), {', '.join(COLUMN_FIELDS)}")
+        kind, raw, result = parsed
+        if kind == COLUMN:
+            if not out.levels:
+                out.levels = column_levels(names, levels)
+                out.weights = column_weights(out.levels)
+            raw = tuple(f"{x}{l}" for x in ("q" if name == "iwv" else "quv") for l in out.levels)
+            key = (COLUMN,)
+        else:
+            missing = [c for c in raw if c not in names]
+            if missing:
+                raise ValueError(f"derived: {name!r} needs the channel{'s' if len(missing) > 1 else ''} "
+                                 f"{', '.join(repr(c) for c in missing)}, which this model lacks")
+            key = (kind,) + raw if kind == VORTDIV else (kind, name)
+        inputs[name] = list(raw)
+        if key not in merged:
+            merged[key] = len(ops)
+            if kind == COLUMN:
+                idx = tuple(tuple(names.index(f"{x}{l}") for l in out.levels) for x in "quv")
+                ops.append(Op(COLUMN, idx, (-1, -1, -1, -1), tuple(float(np.float32(w)) for w in out.weights)))
+            else:
+                ops.append(Op(kind, (names.index(raw[0]), names.index(raw[1])), (-1,) * RESULTS[kind]))
+        k = merged[key]
+        slots = list(ops[k].outputs)
+        slots[result] = slot
+        ops[k] = Op(ops[k].kind, ops[k].inputs, tuple(slots), ops[k].weights)
+    if len(ops) > MAX_OPS:
+        raise ValueError(f"derived: {len(ops)} ops for {fields}; one call holds {MAX_OPS}")
+    if any(op.kind == VORTDIV for op in ops):
+        out.rowc, e0, e1 = row_table(lat, lon)
+        out.edges = (e0, e1)
+    elif len(lat) < 3 or len(lon) < 4:
+        raise ValueError("derived fields need a grid of at least 3 rows and 4 columns")
+    return out
+
+
+def _world_size() -> int:
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def check_request(names, fields, lat, lon, n_members: int = 1, levels=None) -> Plan:
+    """Every refusal that needs no device; returns the plan."""
+    if _world_size() > 1:
+        raise NotImplementedError("derived fields are made on one GPU from members that all lie there; members sharded over the ranks of "
+                                  "a process group are out of scope (DESIGN.md 21)")
+    if not 1 <= int(n_members) <= MAX_MEMBERS:
+        raise ValueError(f"n_members = {n_members}: derived fields are made for 1 to {MAX_MEMBERS} members (SKDERIVE_MAX_MEMBERS)")
+    return plan(names, fields, lat, lon, levels)
+
+
+# ---- the drivers ------------------------------------------------------------------------------------------------------------------------- #
+class LeadDeriver:
+    """Derives one lead time after the other into its own (M, D, H, W) buffer.  ``names``: the forecast's channels in the order of its
+    (C, H, W) states; ``fields``: the derived names, channel d of the buffer is fields[d]."""
+
+    def __init__(self, names, lat, lon, n_members, fields, device="cuda:0", levels=None):
+        self.plan = check_request(names, fields, lat, lon, n_members, levels)
+        self.names, self.fields, self.M = list(names), list(fields), int(n_members)
+        self.lat, self.lon, self.device = np.asarray(lat, np.float64), np.asarray(lon, np.float64), device
+        self._dev = None
+
+    def _buffers(self):
+        if self._dev is None:
+            import torch
+            from .ensemble import member_table
+            dev = torch.device(self.device)
+            out = torch.empty((self.M, len(self.fields), self.lat.size, self.lon.size), dtype=torch.float32, device=dev)
+            states = [out[m] for m in range(self.M)]
+            self._dev = dict(out=out, states=states, table=member_table(states),
+                             rowc=None if self.plan.rowc is None else torch.from_numpy(self.plan.rowc).to(dev))
+        return self._dev
+
+    def add(self, states, table=None) -> tuple:
+        """ONE derive launch over the M device states (C, H, W); returns (derived_states, derived_table): M (D, H, W) views of the
+        buffer and their ``ensemble.member_table``, ready for ``ensemble.stats`` and ``LeadScorer.add``.  The next ``add`` overwrites
+        them."""
+        from .ensemble import member_table
+        if len(states) != self.M:
+            raise ValueError(f"{len(states)} states for a deriver of {self.M} members")
+        b = self._buffers()
+        run(states, member_table(states) if table is None else table, self.plan.ops, b["out"], b["rowc"], self.plan.edges)
+        return b["states"], b["table"]
+
+
+class TruthDeriver:
+    """The hook ``verify.LeadScorer(adapt=...)`` calls so that a truth (or climatology) of RAW channels scores derived fields: the raw
+    inputs of a valid time are uploaded into a (C, H, W) state and derived by the same kernel with M = 1.  A derived field whose inputs
+    the truth lacks is not offered to the scorer; ``dropped`` names it and the channels that are missing.  ``levels``: the pressure levels of
+    the forecast's column integrals, so that the truth's are the same integral (None: those the truth holds between 300 and 1000 hPa)."""
+
+    def __init__(self, fields, lat, lon, device="cuda:0", levels=None):
+        self.fields, self.lat, self.lon, self.device, self.levels = list(fields), lat, lon, device, levels
+        self.dropped: dict = {}
+        self._derivers: dict = {}
+
+    def _needs(self, name, have) -> list:
+        kind, raw, _ = _parse(name)
+        if kind == COLUMN:
+            lv = self.levels
+            if lv is None:
+                lv = [l for l in sorted(int(n[1:]) for n in have if re.fullmatch(r"q\d+", n)) if 300 <= l <= 1000]
+            raw = [f"{x}{l}" for x in ("q" if name == "iwv" else "quv") for l in lv] or ["q<level>"]
+        return list(raw)
+
+    def names(self, fields) -> list:
+        """The derived names that can be formed from the channels ``fields`` (a ``verify._Fields``) holds."""
+        have, ok = set(fields.names), []
+        for name in self.fields:
+            missing = [c for c in self._needs(name, have) if c not in have]
+            if missing:
+                self.dropped.setdefault(name, missing)
+            else:
+                ok.append(name)
+        return ok
+
+    def upload(self, fields, time, scored, dst, idx_dev) -> None:
+        """Fill the rows ``idx_dev`` of ``dst`` (the scorer's (D, H, W) truth buffer) with the fields ``scored`` at ``time``."""
+        import torch
+        key = (id(fields), tuple(scored))
+        hit = self._derivers.get(key)
+        if hit is None:
+            raw = []
+            for name in scored:
+                raw += [c for c in self._needs(name, set(fields.names)) if c not in raw]
+            hit = (raw, LeadDeriver(raw, self.lat, self.lon, 1, list(scored), self.device, self.levels), fields)
+            self._derivers[key] = hit                          # (holds ``fields``: its id stays taken while the entry lives)
+        raw, deriver, _ = hit
+        state = torch.from_numpy(fields.at(time, raw)).to(deriver.device)
+        states, _ = deriver.add([state])
+        dst[idx_dev] = states[0]
+
+
+@dataclass
+class DerivedProducts:
+    """``EnsembleForecast.derived``: the attributes of the raw products, labelled with the derived names.  ``dropped``: the derived
+    fields that could not be scored, with the truth channels that are missing."""
+    fields: list
+    mean: object = None
+    spread: object = None
+    min: object = None
+    max: object = None
+    exceedance: dict = field(default_factory=dict)
+    quantile: dict = field(default_factory=dict)
+    members: object = None
+    scores: object = None
+    dropped: dict = field(default_factory=dict)
+
+
+def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: bool = False, save_config: dict | None = None):
+    """``GlobalModel.derive_fields`` (core/models/base.py has the user-facing description)."""
+    from .labeled import DataArray
+    model = gm.model
+    if n_steps < 0:
+        raise ValueError("n_steps >= 0")
+    check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1)                 # before anything of the device
+    deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device)
+    import torch
+    from .datasource import get_initial_condition_for_model
+    if torch.device(model.device).type != "cuda":
+        raise RuntimeError("derive_fields derives with HIP kernels where the forecast lies: the model must be on a GPU")
+    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
+    if hasattr(model, "__dict__"):
+        model._resident_state = None                       # the loop below is not a state a later rollout continues from
+    loop = model(start_time, x0)
+    times, host = [], []
+    try:
+        for k in range(n_steps + 1):
+            time, out, _ = next(loop)
+            state = (out[0] if out.dim() == 4 else out).contiguous()
+            states, _ = deriver.add([state])
+            times.append(time)
+            host.append(states[0].cpu().numpy())
+            del state, out
+    finally:
+        loop.close()
+        if hasattr(model, "__dict__"):
+            model._resident_state = None
+            model.__dict__.pop("_state_is_own_output", None)
+    da = DataArray(np.stack(host), ["time", "channel", "lat", "lon"],
+                   dict(time=times, channel=list(fields), lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
+    if save:
+        from .common import generate_forecast_id, save_forecast
+        cfg = dict(save_config or {})
+        cfg.setdefault("forecast_id", generate_forecast_id())
+        if save_config is not None:
+            save_config["forecast_id"] = cfg["forecast_id"]
+        da.path = save_forecast(da, f"{gm.model_name}-derived", times[0], times[-1], gm.source_label, config=cfg)
+    return da
+
+
+def derive_prediction(pred, fields, device="cuda:0"):
+    """Derived fields of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF
+    file or zarr store, or a list of such files (their time entries in order, duplicates of a valid time derived once).  Each time
+    entry is uploaded on its own and goes through the same kernel as ``derive_fields``.  Returns DataArray(time, channel=fields, lat, lon)."""
+    import torch
+    from .labeled import DataArray, open_dataarray
+    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
+    arrays = []
+    for p in items:
+        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
+            p = p.prediction
+        elif isinstance(p, (str, os.PathLike)):
+            p = open_dataarray(os.fspath(p))
+        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
+            raise ValueError("derive_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
+        arrays.append(p)
+    first = arrays[0]
+    names = first.channel.values.tolist()
+    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
+    deriver = LeadDeriver(names, lat, lon, 1, fields, device=device)
+    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("derive_prediction derives with HIP kernels: it needs a GPU")
+    seen, times, host = set(), [], []
+    for da in arrays:
+        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
+            raise ValueError("derive_prediction: the files of one forecast must share channels and grid")
+        stamps = np.asarray(da._coords["time"]).astype("datetime64[s]")
+        for k, t in enumerate(stamps):
+            if t in seen:
+                continue
+            seen.add(t)
+            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(deriver.device)
+            states, _ = deriver.add([state])
+            times.append(t.astype(datetime.datetime))
+            host.append(states[0].cpu().numpy())
+            del state
+    return DataArray(np.stack(host), ["time", "channel", "lat", "lon"], dict(time=times, channel=list(fields), lat=lat, lon=lon))

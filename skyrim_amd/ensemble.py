@@ -162,6 +162,7 @@ class EnsembleForecast:
     alpha: float = 2.0
     lmax: object = None          # the truncation used, spherical only
     tracks: object = None        # tracks.Tracks with ``tracks=True``
+    derived: object = None       # derived.DerivedProducts with ``derived=[...]``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -182,9 +183,10 @@ def _world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, perturbation="white",
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, derived=None, perturbation="white",
              length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
-    """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised."""
+    """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
+    derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -201,10 +203,15 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     if unknown:
         raise ValueError(f"unknown products {unknown}; choose from {PRODUCTS}")
     names = list(model.out_channel_names)
+    if derived is not None:
+        from . import derived as deriving
+        deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members)
+    known = names + list(derived or [])
     for what, table, cap in (("exceed", exceed, MAX_THRESHOLDS), ("quantiles", quantiles, MAX_QUANTILES)):
         for ch, vals in (table or {}).items():
-            if ch not in names:
-                raise ValueError(f"{what}: channel {ch!r} is not an output channel of this model")
+            if ch not in known:
+                raise ValueError(f"{what}: channel {ch!r} is not an output channel of this model"
+                                 + ("" if derived is None else " or one of the derived fields"))
             if not 1 <= len(vals) <= cap:
                 raise ValueError(f"{what}[{ch!r}]: 1 to {cap} values per channel, got {len(vals)}")
     for ch, vals in (quantiles or {}).items():
@@ -216,7 +223,7 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
     saved = list(range(0, n_steps + 1, save_every))
     if keep_members:
-        need = int(n_members) * len(saved) * len(names) * len(model.grid.lat) * len(model.grid.lon) * 4
+        need = int(n_members) * len(saved) * len(known) * len(model.grid.lat) * len(model.grid.lon) * 4
         if need > _PINNED_LIMIT:
             raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
                              f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every")
@@ -227,8 +234,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        tracks: bool = False, track_config=None, perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
-        perturb_channels=None) -> EnsembleForecast:
+        tracks: bool = False, track_config=None, derived=None, perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0,
+        lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
     from .common import generate_forecast_id, save_forecast
@@ -236,7 +243,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, perturbation, length_scale_km, alpha, lmax, perturb_channels)
+                                                  keep_members, derived, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
     names = list(model.out_channel_names)
@@ -250,6 +257,17 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if tracks:
         from . import tracks as tracking
         tracker = tracking.LeadTracker(gm.model_name, names, model.grid.lat, model.grid.lon, M, track_config, device=model.device)
+    deriver = dscorer = adapt = None
+    if derived is not None:                                # derived fields (skyrim_amd/derived.py): their own products, labelled with their names
+        from . import derived as deriving
+        dnames = list(derived)
+        deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, M, dnames, device=model.device)
+        d_exceed, d_quant = ({k: v for k, v in t.items() if k in dnames} for t in (exceed, quantiles))
+        exceed, quantiles = ({k: v for k, v in t.items() if k not in dnames} for t in (exceed, quantiles))
+        if scores:
+            adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None)
+            dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
+                                        device=model.device, adapt=adapt)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -289,6 +307,15 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     dev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in exceed.items()}
     dev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in quantiles.items()}
     times, paths, source = [], [], gm.source_label
+    if deriver is not None:
+        D = len(dnames)
+        dhost = {p: np.empty((n_saved, D, n_lat, n_lon), np.float32) for p in products}
+        dhost_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in d_exceed.items()}
+        dhost_q = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in d_quant.items()}
+        dhost_members = np.empty((M, n_saved, D, n_lat, n_lon), np.float32) if keep_members else None
+        ddev_out = {p: torch.empty((D, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products}
+        ddev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_exceed.items()}
+        ddev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_quant.items()}
     try:
         for k in range(n_steps + 1):
             states, time = [], None
@@ -310,6 +337,25 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
             if tracker is not None:
                 tracker.add(time, states, table)           # cyclone candidates of this lead time: only their records leave the device
+            if deriver is not None and (keep or dscorer is not None):
+                dstates, dtable = deriver.add(states, table)      # ONE launch: D derived planes per member, read below like raw channels
+                if dscorer is not None:
+                    dscorer.add(time, dstates, dtable)
+                if keep:
+                    s = saved.index(k)
+                    if products:
+                        stats(dstates, dtable, 0, D * hw, **{p: ddev_out[p] for p in products})
+                    for p in products:
+                        dhost[p][s] = ddev_out[p].cpu().numpy()
+                    for ch, thr in d_exceed.items():
+                        stats(dstates, dtable, dnames.index(ch) * hw, hw, exceed=ddev_ex[ch], thresholds=thr)
+                        dhost_ex[ch][s] = ddev_ex[ch].cpu().numpy()
+                    for ch, lev in d_quant.items():
+                        stats(dstates, dtable, dnames.index(ch) * hw, hw, quant=ddev_q[ch], levels=lev)
+                        dhost_q[ch][s] = ddev_q[ch].cpu().numpy()
+                    if keep_members:
+                        for m, st in enumerate(dstates):
+                            dhost_members[m, s] = st.cpu().numpy()
             if keep:
                 s = saved.index(k)
                 times.append(time)
@@ -331,6 +377,13 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                         name = product_model_name(gm.model_name, M, p)
                         pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg      # one zarr store per product, appended along time
                         paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
+                    if deriver is not None:
+                        for p in products:
+                            da = DataArray(dhost[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
+                                           dict(time=times[s - 1:s + 1], channel=dnames, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
+                            name = product_model_name(gm.model_name, M, f"derived-{p}")
+                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
+                            paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
                     source = "file"
             del states, table
     finally:
@@ -365,6 +418,19 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             paths.append(ens.tracks.save(cfg.get("output_dir") or OUTPUT_DIR))
     for p in products:
         setattr(ens, p, labelled(host[p], "channel", names))
+    if deriver is not None:
+        def dlabelled(arr, dim, labels):
+            return DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **grid))
+        ens.derived = deriving.DerivedProducts(dnames, **{p: dlabelled(dhost[p], "channel", dnames) for p in products})
+        ens.derived.exceedance = {ch: dlabelled(dhost_ex[ch], "threshold", np.asarray(d_exceed[ch], np.float32)) for ch in d_exceed}
+        ens.derived.quantile = {ch: dlabelled(dhost_q[ch], "quantile", np.asarray(d_quant[ch], np.float64)) for ch in d_quant}
+        if keep_members:
+            ens.derived.members = DataArray(dhost_members, ["member", "time", "channel", "lat", "lon"],
+                                            dict(member=np.arange(M), time=times, channel=dnames, **grid))
+        if dscorer is not None:
+            ens.derived.scores = dscorer.result()
+            ens.derived.scores.forecast_id = fid
+            ens.derived.dropped = dict(adapt.dropped)
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
     ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
     if keep_members:

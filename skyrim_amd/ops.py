@@ -18,6 +18,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     score_fields                                         (forecast scores against a truth state, include/skyrim_score.h)
     noise_coeffs / noise_apply                           (spherical perturbations, include/skyrim_noise.h)
     track_detect                                         (cyclone candidates of M states, include/skyrim_track.h)
+    derive_fields                                        (derived channels of M states, include/skyrim_derive.h)
 """
 from __future__ import annotations
 
@@ -532,6 +533,13 @@ def _track_detect(members, table, channels, band, thresholds, h_msl, h_vort, h_w
                   workspace)
 
 
+# ---- derived fields ------------------------------------------------------------------------------------------------------------- #
+def _derive_fields(members, table, program, weights, out, rowc, edges) -> None:
+    """``program`` / ``weights``: derived.encode(ops); ``rowc`` and ``edges``: derived.row_table on the device (vorticity, divergence)."""
+    from . import derived
+    derived.run(list(members), table, derived.decode(program, weights), out, rowc, tuple(edges) if len(edges) else (derived.EDGE_POLE,) * 2)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -594,6 +602,7 @@ _SCHEMAS = [
      "Tensor(c!)? counts, int c0, int nc) -> ()", _score_fields),
     ("track_detect(Tensor[] members, Tensor table, int[] channels, int[] band, float[] thresholds, Tensor h_msl, Tensor h_vort, Tensor h_wind, "
      "Tensor? h_core, Tensor rowc, Tensor(a!) records, Tensor(b!) count, Tensor(c!) workspace) -> ()", _track_detect),
+    ("derive_fields(Tensor[] members, Tensor table, int[] program, float[] weights, Tensor(a!) out, Tensor? rowc, int[] edges) -> ()", _derive_fields),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]

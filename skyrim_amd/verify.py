@@ -299,9 +299,11 @@ def check_request(n_members: int, out_names, channels=None) -> None:
 class LeadScorer:
     """Scores one lead time after the other on the device and gathers the per-channel sums.  ``names``: the forecast's channels in
     the order of its (C, H, W) states; the channels scored are those the truth (and the climatology) also holds, restricted to
-    ``channels`` when given."""
+    ``channels`` when given.  ``adapt``: an object with ``names(fields)`` and ``upload(fields, time, scored, dst, idx)`` that stands between the
+    truth's own channels and the forecast's (``derived.TruthDeriver``: the truth of a derived field is derived from raw channels)."""
 
-    def __init__(self, model_name, names, lat, lon, n_members, truth, climatology=None, channels=None, device="cuda:0", forecast_id=""):
+    def __init__(self, model_name, names, lat, lon, n_members, truth, climatology=None, channels=None, device="cuda:0", forecast_id="",
+                 adapt=None):
         check_request(n_members, names, channels)
         if truth is None:
             raise ValueError("scores need a truth: a data source, a DataArray or a saved forecast")
@@ -309,7 +311,10 @@ class LeadScorer:
         self.lat, self.lon = np.asarray(lat, np.float64), np.asarray(lon)
         self.truth = _Fields(truth, "truth", lat, lon)
         self.clim = _Fields(climatology, "climatology", lat, lon) if climatology is not None else None
-        common = [n for n in self.names if n in self.truth.names and (self.clim is None or n in self.clim.names)]
+        self.adapt = adapt
+        truth_names = self.truth.names if adapt is None else adapt.names(self.truth)
+        clim_names = None if self.clim is None else (self.clim.names if adapt is None else adapt.names(self.clim))
+        common = [n for n in self.names if n in truth_names and (clim_names is None or n in clim_names)]
         if not common:
             raise ValueError("the forecast and the truth share no channel")
         self.scored = [n for n in common if not channels or n in channels]
@@ -334,6 +339,8 @@ class LeadScorer:
         return self._dev
 
     def _upload(self, fields: _Fields, time, dst: torch.Tensor):
+        if self.adapt is not None:
+            return self.adapt.upload(fields, time, self.scored, dst, self._idx_dev)
         dst[self._idx_dev] = torch.from_numpy(fields.at(time, self.scored)).to(self.device)
 
     def add(self, time, states, table=None) -> None:
