@@ -117,8 +117,8 @@ class GlobalModel:
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-                          tracks: bool = False, track_config=None, derived: List[str] | None = None, perturbation: str = "white",
-                          length_scale_km: float = 500.0,
+                          tracks: bool = False, track_config=None, derived: List[str] | None = None, grid=None,
+                          regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0,
                           alpha: float = 2.0, lmax: int | None = None, perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
@@ -138,11 +138,18 @@ class GlobalModel:
         ``EnsembleForecast.tracks``.  ``derived=[...]`` names derived fields (``ws10m``, ``ws100m``, ``ws<level>``, ``thk<a>_<b>``, ``vo<X>``,
         ``div<X>``, ``ivt``, ``ivtu``, ``ivtv``, ``iwv``: skyrim_amd/derived.py) that are formed from every member on the device at
         each lead time; the same ``products`` of them, ``exceed`` / ``quantiles`` under their names and, with ``scores=True``, their scores land
-        in ``EnsembleForecast.derived``."""
+        in ``EnsembleForecast.derived``.  ``grid=`` names a target grid (``"1.5deg"`` or a float, ``(lat, lon)`` arrays, or
+        ``dict(region=(lat_s, lat_n, lon_w, lon_e), res=...)``: skyrim_amd/regrid.py) every member is also put on at each lead
+        time, on the device, by ``regrid_method`` (conservative, bilinear, nearest); the same ``products``, ``exceed`` and ``quantiles`` on it
+        and, with ``scores=True``, the scores against the truth regridded likewise land in ``EnsembleForecast.regridded``.  With a grid,
+        ``keep_members=True`` also returns the regridded members and ``keep_members="regridded"`` only those, so that the host limit is
+        checked against their size."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if derived is not None:
             extra["derived"] = derived
+        if grid is not None:
+            extra.update(grid=grid, regrid_method=regrid_method)
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -169,18 +176,32 @@ class GlobalModel:
         from ... import derived
         return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config)
 
+    def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative",
+                        channels: List[str] | None = None, save: bool = False, save_config: dict | None = None):
+        """The deterministic forecast at the lead times 0 .. ``n_steps`` on another latitude-longitude grid (skyrim_amd/regrid.py,
+        DESIGN.md 22).  ``grid``: a resolution (``"1.5deg"`` or a float; 180 / res an integer), ``(lat, lon)`` arrays, or
+        ``dict(region=(lat_s, lat_n, lon_w, lon_e), res=...)``; ``method``: conservative (first order), bilinear or nearest.  The model's
+        TimeLoop is advanced and every state is regridded where it lies in HBM; only the regridded states cross to the host.  Returns
+        DataArray(time, channel, lat, lon) on the target grid; ``save=True`` writes it as the forecast of ``{model}-regrid``.  A target
+        the method cannot serve is refused with ValueError before the device is touched."""
+        from ... import regrid
+        return regrid.regrid_model(self, start_time, n_steps, grid, method, channels, save=save, save_config=save_config)
+
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
-               save: bool = False, save_config: dict | None = None):
+               save: bool = False, save_config: dict | None = None, grid=None, regrid_method: str = "conservative"):
         """Scores of the deterministic forecast at every lead time 0 .. ``n_steps`` (skyrim_amd/verify.py): bias, MAE, RMSE,
         CRPS (= MAE for one member) and, with a ``climatology``, ACC, area-weighted per channel.  The model's TimeLoop is advanced, each
         valid time's truth is uploaded and the state is scored where it lies in HBM: no forecast state goes to the host.  ``truth``:
         None = the model's own kind of data source at the valid times; or any object with ``channel_names`` and ``[time]``; or a
         (time, channel, lat, lon) DataArray / saved forecast.  ``climatology``: the same forms, or one (channel, lat, lon) array for every
         lead time.  Channels present in both forecast and truth are scored.  Returns ``verify.Scores``; ``save=True`` writes
-        ``{model}-scores.json`` under the forecast id directory."""
+        ``{model}-scores.json`` under the forecast id directory.  ``grid=`` (the forms of ``regrid_forecast``) scores on that target
+        grid: forecast and truth, both on the model's grid, are regridded by ``regrid_method`` on the device and scored with the target's
+        area weights; the scores' JSON then carries the grid's label."""
         from ... import verify
+        extra = {} if grid is None else dict(grid=grid, regrid_method=regrid_method)
         return verify.verify_model(self, start_time, n_steps=n_steps, truth=truth, climatology=climatology, channels=channels, save=save,
-                                   save_config=save_config)
+                                   save_config=save_config, **extra)
 
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):

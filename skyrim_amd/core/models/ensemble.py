@@ -36,9 +36,17 @@ def _on_grid_of(first, p):
 
 
 class GlobalEnsemble:
-    def __init__(self, model_names, ic_source: str = "cds", model_kwargs: "dict | None" = None):
+    def __init__(self, model_names, ic_source: str = "cds", model_kwargs: "dict | None" = None, grid=None,
+                 regrid_method: str = "conservative"):
         """``model_kwargs`` (beyond the reference's signature): ``{model name: constructor keywords}`` for members that are not built with
-        their defaults (grid geometry, parameters, device ...)."""
+        their defaults (grid geometry, parameters, device ...).  ``grid`` (beyond it too): a target grid of skyrim_amd/regrid.py ("1.5deg",
+        (lat, lon) arrays or a region) every member's prediction and per-step file is put on, by ``regrid_method`` on the device, before the
+        members are averaged -- so members on different native grids can be combined; without it such members are refused."""
+        if grid is not None:
+            from ... import regrid
+            if regrid_method not in regrid.METHODS:
+                raise ValueError(f"regrid: unknown method {regrid_method!r}; choose from {regrid.METHODS}")
+        self.grid, self.regrid_method = grid, regrid_method
         from . import MODELS
         missing = [n for n in model_names if n not in MODELS]
         if missing:
@@ -83,7 +91,18 @@ class GlobalEnsemble:
         if not common:
             raise ValueError("No predictions to average or no common channels available.")
         self.common_channels = common
+        if self.grid is not None:
+            predictions = [self._on_target(p.sel(channel=common)) for p in predictions]
         return concat([_on_grid_of(predictions[0], p.sel(channel=common)) for p in predictions], dim="model").mean(dim="model")
+
+    def _on_target(self, p):
+        """A member's prediction on ``self.grid``: a specification that depends on the source (a resolution, a region) is resolved against
+        the FIRST member regridded and the later members are put on the very same points."""
+        from ... import regrid
+        grid = self.grid if getattr(self, "_target", None) is None else self._target
+        out = regrid.regrid_prediction(p, grid, self.regrid_method)
+        self._target = (out._coords["lat"], out._coords["lon"])
+        return out
 
     def predict_one_step(self, start_time: datetime.datetime, save: bool = False):
         """Subclasses should implement this method."""

@@ -133,6 +133,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
                                   "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")
 
+    def regrid_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator regrid_forecast advances: "
+                                  "regrid its forecast with skyrim_amd.regrid.regrid_prediction(forecast_or_saved_files, grid, method)")
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None,
                 initial_condition=None):
         """Final two time levels + per-step file paths; the stepper state is fed back step to step (never through a file).

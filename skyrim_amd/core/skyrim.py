@@ -68,6 +68,19 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.derive_fields(start_time, n_steps=n_steps, fields=fields, **kwargs)
 
+    def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative", **kwargs):
+        """The single model's forecast on another latitude-longitude grid -- "1.5deg", (lat, lon) arrays or a region -- as a
+        DataArray(time, channel, lat, lon) (``GlobalModel.regrid_forecast`` has the arguments).
+        ``ensemble_forecast(..., grid=...)`` gives the ensemble products on it, ``verify(..., grid=...)`` the scores."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.regrid_forecast(start_time, n_steps=n_steps, grid=grid, method=method, **kwargs)
+
+    @staticmethod
+    def regrid_prediction(pred, grid, method="conservative", device="cuda:0", **kwargs):
+        """A forecast that is already in memory or on disk, on another grid (``regrid.regrid_prediction``)."""
+        from .. import regrid
+        return regrid.regrid_prediction(pred, grid, method, device=device, **kwargs)
+
     @staticmethod
     def derive_prediction(pred, fields, device="cuda:0"):
         """Derived fields of a forecast that is already in memory or on disk (``derived.derive_prediction``)."""

@@ -163,6 +163,7 @@ class EnsembleForecast:
     lmax: object = None          # the truncation used, spherical only
     tracks: object = None        # tracks.Tracks with ``tracks=True``
     derived: object = None       # derived.DerivedProducts with ``derived=[...]``
+    regridded: object = None     # regrid.RegriddedProducts with ``grid=...``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -183,10 +184,11 @@ def _world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, derived=None, perturbation="white",
-             length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, derived=None, grid=None,
+             regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
-    derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels."""
+    derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
+    ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -207,6 +209,13 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         from . import derived as deriving
         deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members)
     known = names + list(derived or [])
+    tabs = None
+    if grid is not None:
+        from . import regrid
+        if derived is not None:
+            raise ValueError("grid= together with derived= is not supported: derived fields are made on the model's own grid only "
+                             "(DESIGN.md 22, out of scope)")
+        tabs = regrid.check_request(names, model.grid.lat, model.grid.lon, n_members, grid, regrid_method)
     for what, table, cap in (("exceed", exceed, MAX_THRESHOLDS), ("quantiles", quantiles, MAX_QUANTILES)):
         for ch, vals in (table or {}).items():
             if ch not in known:
@@ -222,8 +231,12 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         raise ValueError(f"channels {missing} are not output channels of this model")
     noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
     saved = list(range(0, n_steps + 1, save_every))
+    if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
+        raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
-        need = int(n_members) * len(saved) * len(known) * len(model.grid.lat) * len(model.grid.lon) * 4
+        need = 0 if keep_members == "regridded" else int(n_members) * len(saved) * len(known) * len(model.grid.lat) * len(model.grid.lon) * 4
+        if tabs is not None:                                # the regridded members are checked at the size they have
+            need += int(n_members) * len(saved) * len(names) * tabs.lat.size * tabs.lon.size * 4
         if need > _PINNED_LIMIT:
             raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
                              f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every")
@@ -234,8 +247,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        tracks: bool = False, track_config=None, derived=None, perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0,
-        lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
+        tracks: bool = False, track_config=None, derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
+        length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
     from .common import generate_forecast_id, save_forecast
@@ -243,7 +256,9 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, derived, perturbation, length_scale_km, alpha, lmax, perturb_channels)
+                                                  keep_members, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
+                                                  perturb_channels)
+    keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
     names = list(model.out_channel_names)
@@ -268,6 +283,15 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None)
             dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
                                         device=model.device, adapt=adapt)
+    regridder = rscorer = None
+    if grid is not None:                                   # the same products on the target grid (skyrim_amd/regrid.py)
+        from . import regrid
+        regridder = regrid.LeadRegridder(names, model.grid.lat, model.grid.lon, M, grid, regrid_method, device=model.device)
+        grid_label = regrid.grid_label(grid)                # (``grid`` names the coordinates of the raw products further down)
+        if scores:
+            rscorer = verify.LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, M, scorer.truth.src, climatology, channels,
+                                        device=model.device,
+                                        adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device))
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -316,6 +340,16 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         ddev_out = {p: torch.empty((D, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products}
         ddev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_exceed.items()}
         ddev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_quant.items()}
+    if regridder is not None:
+        r_lat, r_lon = regridder.lat_out.size, regridder.lon_out.size
+        rhw = r_lat * r_lon
+        rhost = {p: np.empty((n_saved, C, r_lat, r_lon), np.float32) for p in products}
+        rhost_ex = {ch: np.empty((n_saved, len(v), r_lat, r_lon), np.float32) for ch, v in exceed.items()}
+        rhost_q = {ch: np.empty((n_saved, len(v), r_lat, r_lon), np.float32) for ch, v in quantiles.items()}
+        rhost_members = np.empty((M, n_saved, C, r_lat, r_lon), np.float32) if keep_regridded else None
+        rdev_out = {p: torch.empty((C, r_lat, r_lon), dtype=torch.float32, device=dev) for p in products}
+        rdev_ex = {ch: torch.empty((len(v), r_lat, r_lon), dtype=torch.float32, device=dev) for ch, v in exceed.items()}
+        rdev_q = {ch: torch.empty((len(v), r_lat, r_lon), dtype=torch.float32, device=dev) for ch, v in quantiles.items()}
     try:
         for k in range(n_steps + 1):
             states, time = [], None
@@ -356,6 +390,25 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     if keep_members:
                         for m, st in enumerate(dstates):
                             dhost_members[m, s] = st.cpu().numpy()
+            if regridder is not None and (keep or rscorer is not None):
+                rstates, rtable = regridder.add(states, table)    # ONE launch: every channel of every member on the target grid
+                if rscorer is not None:
+                    rscorer.add(time, rstates, rtable)
+                if keep:
+                    s = saved.index(k)
+                    if products:
+                        stats(rstates, rtable, 0, C * rhw, **{p: rdev_out[p] for p in products})
+                    for p in products:
+                        rhost[p][s] = rdev_out[p].cpu().numpy()
+                    for ch, thr in exceed.items():
+                        stats(rstates, rtable, names.index(ch) * rhw, rhw, exceed=rdev_ex[ch], thresholds=thr)
+                        rhost_ex[ch][s] = rdev_ex[ch].cpu().numpy()
+                    for ch, lev in quantiles.items():
+                        stats(rstates, rtable, names.index(ch) * rhw, rhw, quant=rdev_q[ch], levels=lev)
+                        rhost_q[ch][s] = rdev_q[ch].cpu().numpy()
+                    if keep_regridded:
+                        for m, st in enumerate(rstates):
+                            rhost_members[m, s] = st.cpu().numpy()
             if keep:
                 s = saved.index(k)
                 times.append(time)
@@ -382,6 +435,13 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                             da = DataArray(dhost[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
                                            dict(time=times[s - 1:s + 1], channel=dnames, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
                             name = product_model_name(gm.model_name, M, f"derived-{p}")
+                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
+                            paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
+                    if regridder is not None:
+                        for p in products:
+                            da = DataArray(rhost[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
+                                           dict(time=times[s - 1:s + 1], channel=names, lat=regridder.lat_out, lon=regridder.lon_out))
+                            name = product_model_name(gm.model_name, M, f"regrid-{p}")
                             pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
                             paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
                     source = "file"
@@ -431,6 +491,25 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             ens.derived.scores = dscorer.result()
             ens.derived.scores.forecast_id = fid
             ens.derived.dropped = dict(adapt.dropped)
+    if regridder is not None:
+        rgrid = dict(lat=regridder.lat_out, lon=regridder.lon_out)
+
+        def rlabelled(arr, dim, labels):
+            da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **rgrid))
+            return da.sel(channel=list(channels)) if channels and dim == "channel" else da
+        ens.regridded = regrid.RegriddedProducts(rgrid["lat"], rgrid["lon"], regrid_method,
+                                                 **{p: rlabelled(rhost[p], "channel", names) for p in products})
+        ens.regridded.exceedance = {ch: rlabelled(rhost_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
+        ens.regridded.quantile = {ch: rlabelled(rhost_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
+        if keep_regridded:
+            ens.regridded.members = DataArray(rhost_members, ["member", "time", "channel", "lat", "lon"],
+                                              dict(member=np.arange(M), time=times, channel=names, **rgrid))
+            if channels:
+                ens.regridded.members = ens.regridded.members.sel(channel=list(channels))
+        if rscorer is not None:
+            ens.regridded.scores = rscorer.result()
+            ens.regridded.scores.forecast_id = fid
+            ens.regridded.scores.grid = grid_label
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
     ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
     if keep_members:

@@ -19,6 +19,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     noise_coeffs / noise_apply                           (spherical perturbations, include/skyrim_noise.h)
     track_detect                                         (cyclone candidates of M states, include/skyrim_track.h)
     derive_fields                                        (derived channels of M states, include/skyrim_derive.h)
+    regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
 """
 from __future__ import annotations
 
@@ -540,6 +541,13 @@ def _derive_fields(members, table, program, weights, out, rowc, edges) -> None:
     derived.run(list(members), table, derived.decode(program, weights), out, rowc, tuple(edges) if len(edges) else (derived.EDGE_POLE,) * 2)
 
 
+# ---- regridding ------------------------------------------------------------------------------------------------------------------- #
+def _regrid(members, table, channels, row_start, row_count, row_weight, col_start, col_count, col_weight, out) -> None:
+    """The two tables: ``regrid.Tables.on(device)``; ``out``: (M, len(channels), Ho, Wo)."""
+    from . import regrid
+    regrid.run(list(members), table, list(channels), (row_start, row_count, row_weight), (col_start, col_count, col_weight), out)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -603,6 +611,8 @@ _SCHEMAS = [
     ("track_detect(Tensor[] members, Tensor table, int[] channels, int[] band, float[] thresholds, Tensor h_msl, Tensor h_vort, Tensor h_wind, "
      "Tensor? h_core, Tensor rowc, Tensor(a!) records, Tensor(b!) count, Tensor(c!) workspace) -> ()", _track_detect),
     ("derive_fields(Tensor[] members, Tensor table, int[] program, float[] weights, Tensor(a!) out, Tensor? rowc, int[] edges) -> ()", _derive_fields),
+    ("regrid(Tensor[] members, Tensor table, int[] channels, Tensor row_start, Tensor row_count, Tensor row_weight, Tensor col_start, "
+     "Tensor col_count, Tensor col_weight, Tensor(a!) out) -> ()", _regrid),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]

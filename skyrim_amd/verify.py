@@ -123,16 +123,23 @@ def area_weights(lat) -> np.ndarray:
     cell bounds midway between neighbouring latitudes, the two outer bounds half a spacing beyond the axis and clipped to +-90.
     Ascending and descending axes give the same weight to the same latitude; an axis from pole to pole sums to 2."""
     lat = np.asarray(lat, np.float64)
-    if lat.ndim != 1 or lat.size == 0 or not np.all(np.isfinite(lat)) or np.any(np.abs(lat) > 90):
-        raise ValueError("area_weights: a one-dimensional latitude axis in degrees")
-    if lat.size == 1:
+    if lat.ndim == 1 and lat.size == 1 and np.isfinite(lat[0]) and abs(lat[0]) <= 90:
         return np.ones(1)
+    return np.abs(np.diff(np.sin(np.deg2rad(cell_bounds(lat, "area_weights")))))
+
+
+def cell_bounds(lat, what: str = "cell_bounds") -> np.ndarray:
+    """The H + 1 float64 cell bounds, in degrees and in the order of the axis, of a latitude axis of H >= 2 rows: midway between
+    neighbouring latitudes, the two outer bounds half a spacing beyond the axis and clipped to +-90.  ``area_weights`` and the
+    conservative weights of skyrim_amd/regrid.py are both made from these."""
+    lat = np.asarray(lat, np.float64)
+    if lat.ndim != 1 or lat.size < 2 or not np.all(np.isfinite(lat)) or np.any(np.abs(lat) > 90):
+        raise ValueError(f"{what}: a one-dimensional latitude axis in degrees")
     step = np.diff(lat)
     if not (np.all(step > 0) or np.all(step < 0)):
-        raise ValueError("area_weights: the latitude axis must be strictly monotonic")
+        raise ValueError(f"{what}: the latitude axis must be strictly monotonic")
     mid = (lat[:-1] + lat[1:]) / 2
-    bounds = np.clip(np.concatenate([[lat[0] - step[0] / 2], mid, [lat[-1] + step[-1] / 2]]), -90.0, 90.0)
-    return np.abs(np.diff(np.sin(np.deg2rad(bounds))))
+    return np.clip(np.concatenate([[lat[0] - step[0] / 2], mid, [lat[-1] + step[-1] / 2]]), -90.0, 90.0)
 
 
 def _iso(t) -> str:
@@ -169,6 +176,7 @@ class Scores:
         names = [m for m in METRICS if m in rows]
         self.table = DataArray(np.stack([rows[m] for m in names]) if names else np.zeros((0, len(self.times), len(self.channels))),
                                ["metric", "time", "channel"], dict(metric=names, **coords))
+        self.grid = ""                                          # the label of the target grid when the scores were made on one (regrid.py)
         self.rank_counts = self.rank_histogram = None
         if rank_counts is not None:
             rc = dict(rank=np.arange(M + 1), **coords)
@@ -188,6 +196,8 @@ class Scores:
         doc = dict(model=self.model_name, n_members=self.n_members, forecast_id=self.forecast_id, times=[_iso(t) for t in self.times],
                    channels=self.channels, slots=self.sums.slot.values.tolist(), sums=clean(self.sums.values.tolist()),
                    metrics=self.table.metric.values.tolist(), table=clean(self.table.values.tolist()))
+        if self.grid:
+            doc["grid"] = self.grid
         if self.rank_counts is not None:
             doc["rank_counts"] = self.rank_counts.values.tolist()
             doc["rank_histogram"] = clean(self.rank_histogram.values.tolist())
@@ -207,9 +217,11 @@ class Scores:
         nan = lambda a: np.array([[[np.nan if v is None else v for v in r] for r in p] for p in a], np.float64)      # noqa: E731
         times = [datetime.datetime.fromisoformat(t) for t in doc["times"]]
         rc = doc.get("rank_counts")
-        return cls(doc["model"], doc["n_members"], times, doc["channels"], nan(doc["sums"]).reshape(len(doc["slots"]), len(times), -1),
-                   doc["slots"], None if rc is None else np.array(rc, np.int64), None if rc is None else nan(doc["rank_histogram"]),
-                   doc.get("forecast_id", ""))
+        out = cls(doc["model"], doc["n_members"], times, doc["channels"], nan(doc["sums"]).reshape(len(doc["slots"]), len(times), -1),
+                  doc["slots"], None if rc is None else np.array(rc, np.int64), None if rc is None else nan(doc["rank_histogram"]),
+                  doc.get("forecast_id", ""))
+        out.grid = doc.get("grid", "")
+        return out
 
     @classmethod
     def load(cls, path) -> "Scores":
@@ -300,7 +312,8 @@ class LeadScorer:
     """Scores one lead time after the other on the device and gathers the per-channel sums.  ``names``: the forecast's channels in
     the order of its (C, H, W) states; the channels scored are those the truth (and the climatology) also holds, restricted to
     ``channels`` when given.  ``adapt``: an object with ``names(fields)`` and ``upload(fields, time, scored, dst, idx)`` that stands between the
-    truth's own channels and the forecast's (``derived.TruthDeriver``: the truth of a derived field is derived from raw channels)."""
+    truth's own channels and the forecast's (``derived.TruthDeriver``: the truth of a derived field is derived from raw channels;
+    ``regrid.TruthRegridder``: the truth is on another grid, named by its ``truth_grid``, and regridded to the scorer's)."""
 
     def __init__(self, model_name, names, lat, lon, n_members, truth, climatology=None, channels=None, device="cuda:0", forecast_id="",
                  adapt=None):
@@ -309,9 +322,10 @@ class LeadScorer:
             raise ValueError("scores need a truth: a data source, a DataArray or a saved forecast")
         self.model_name, self.names, self.M, self.forecast_id = model_name, list(names), int(n_members), forecast_id
         self.lat, self.lon = np.asarray(lat, np.float64), np.asarray(lon)
-        self.truth = _Fields(truth, "truth", lat, lon)
-        self.clim = _Fields(climatology, "climatology", lat, lon) if climatology is not None else None
         self.adapt = adapt
+        tlat, tlon = getattr(adapt, "truth_grid", (lat, lon))          # (regrid.TruthRegridder reads the truth on the forecast's SOURCE grid)
+        self.truth = _Fields(truth, "truth", tlat, tlon)
+        self.clim = _Fields(climatology, "climatology", tlat, tlon) if climatology is not None else None
         truth_names = self.truth.names if adapt is None else adapt.names(self.truth)
         clim_names = None if self.clim is None else (self.clim.names if adapt is None else adapt.names(self.clim))
         common = [n for n in self.names if n in truth_names and (clim_names is None or n in clim_names)]
@@ -393,15 +407,24 @@ def _finish(scores: Scores, save: bool, save_config):
 
 
 def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels=None, save: bool = False,
-                 save_config: dict | None = None) -> Scores:
+                 save_config: dict | None = None, grid=None, regrid_method: str = "conservative") -> Scores:
     """``GlobalModel.verify`` (core/models/base.py has the user-facing description)."""
     from .datasource import get_initial_condition_for_model
     model = gm.model
     check_request(1, model.out_channel_names, channels)
     if n_steps < 0:
         raise ValueError("n_steps >= 0")
-    scorer = LeadScorer(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1,
-                        default_truth(gm) if truth is None else truth, climatology, channels, device=model.device)
+    regridder = None
+    if grid is not None:                                   # score on the target grid: forecast and truth go through the same regrid kernel
+        from . import regrid
+        names = list(model.out_channel_names)
+        regridder = regrid.LeadRegridder(names, model.grid.lat, model.grid.lon, 1, grid, regrid_method, device=model.device)
+        scorer = LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, 1, default_truth(gm) if truth is None else truth,
+                            climatology, channels, device=model.device,
+                            adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device))
+    else:
+        scorer = LeadScorer(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1,
+                            default_truth(gm) if truth is None else truth, climatology, channels, device=model.device)
     if torch.device(model.device).type != "cuda":
         raise RuntimeError("verify scores the forecast with HIP kernels where it lies: the model must be on a GPU")
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
@@ -412,14 +435,20 @@ def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None
         for k in range(n_steps + 1):
             time, out, _ = next(loop)
             state = (out[0] if out.dim() == 4 else out).contiguous()
-            scorer.add(time, [state])
+            if regridder is None:
+                scorer.add(time, [state])
+            else:
+                scorer.add(time, *regridder.add([state]))
             del state, out
     finally:
         loop.close()
         if hasattr(model, "__dict__"):
             model._resident_state = None
             model.__dict__.pop("_state_is_own_output", None)
-    return _finish(scorer.result(), save, save_config)
+    result = scorer.result()
+    if regridder is not None:
+        result.grid = regrid.grid_label(grid)
+    return _finish(result, save, save_config)
 
 
 def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=None, model_name: str = "") -> Scores:

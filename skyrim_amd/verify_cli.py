@@ -1,7 +1,8 @@
 """``verify`` command line: the options of ``forecast`` (skyrim_amd/forecast.py: same names, short flags and defaults) plus the size of
 the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
 channels to print, and the kind of perturbation (``--perturbation spherical --length_scale_km --lmax``: this is where spread against skill is
-tuned; the ``ensemble`` command keeps white noise).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
+tuned; the ``ensemble`` command keeps white noise), and the grid to score on (``--grid 1.5deg --regrid_method conservative``: forecast and
+truth are regridded on the device, skyrim_amd/regrid.py; the default scores on the model's own grid).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
 ``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ from .verify import DEFAULT_CHANNELS
 
 def run_verify(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
                filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
-               seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None):
+               seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None,
+               grid: str | None = None, regrid_method: str = "conservative"):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
     from .core.models.base import adjust_lead_time
@@ -32,13 +34,14 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
         raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
     scored = filter_vars.split(",") if bool(filter_vars) else None
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
+    on_grid = {} if not grid else dict(grid=grid, regrid_method=regrid_method)
     if members == 1:
-        scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg)
+        scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg, **on_grid)
     else:
         ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed, products=(),
                                       channels=scored, climatology=climatology, scores=True, save_config=cfg, perturbation=perturbation,
-                                      length_scale_km=length_scale_km, lmax=lmax)
-        scores = ens.scores
+                                      length_scale_km=length_scale_km, lmax=lmax, **on_grid)
+        scores = ens.regridded.scores if grid else ens.scores
         scores.path = scores.save(cfg["output_dir"])
     return scores
 
@@ -79,12 +82,16 @@ def lines(scores, channels) -> list[str]:
               help="Perturbation kind (members > 1): grid-point white noise, or spatially correlated fields on the sphere")
 @click.option("--length_scale_km", type=float, default=500.0, help="Correlation length of the spherical perturbations in km")
 @click.option("--lmax", type=int, default=None, help="Spectral truncation of the spherical perturbations (default: min(256, n_lat, n_lon / 2))")
+@click.option("--grid", type=str, default=None, help="Score on this grid instead of the model's own: a resolution that divides 180 degrees, "
+              "such as 1.5deg; forecast and truth are regridded on the device")
+@click.option("--regrid_method", type=click.Choice(["conservative", "bilinear", "nearest"]), default="conservative",
+              help="How --grid is reached (first-order conservative is what WeatherBench 2 uses)")
 def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
-           perturb_scale, seed, perturbation, length_scale_km, lmax):
+           perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method):
     if modal:
         raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
     scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
-                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax)
+                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method)
     if scores is None:
         return None
     for ln in lines(scores, [c for c in channels.split(",") if c]):
