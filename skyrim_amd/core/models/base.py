@@ -117,9 +117,10 @@ class GlobalModel:
                           seed: int = 0, products=("mean", "spread"), exceed: dict | None = None, quantiles: dict | None = None,
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-                          tracks: bool = False, track_config=None, derived: List[str] | None = None, grid=None,
-                          regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0,
-                          alpha: float = 2.0, lmax: int | None = None, perturb_channels: List[str] | None = None):
+                          tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
+                          derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
+                          length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+                          perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
         starts from ``x0 + perturb_scale * sigma_channel * z(seed, m)`` (member 0 is the unperturbed control), every member runs through its
         own TimeLoop generator, and at each lead time one HIP pass over the members gives the ``products`` (any of mean, spread, min, max),
@@ -143,9 +144,14 @@ class GlobalModel:
         time, on the device, by ``regrid_method`` (conservative, bilinear, nearest); the same ``products``, ``exceed`` and ``quantiles`` on it
         and, with ``scores=True``, the scores against the truth regridded likewise land in ``EnsembleForecast.regridded``.  With a grid,
         ``keep_members=True`` also returns the regridded members and ``keep_members="regridded"`` only those, so that the host limit is
-        checked against their size."""
+        checked against their size.  ``events={channel: [thresholds]}`` (``True``: the thresholds of ``exceed``), with ``scores=True``,
+        verifies the events "above the threshold" at each lead time (skyrim_amd/events.py): Brier score and decomposition,
+        reliability curve, ROC and, over the radii ``neighbourhoods_km``, the fractions skill score land in ``scores.events`` of the raw,
+        derived and regridded scores."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
+        if events is not None:
+            extra.update(events=events, neighbourhoods_km=neighbourhoods_km)
         if derived is not None:
             extra["derived"] = derived
         if grid is not None:
@@ -188,7 +194,8 @@ class GlobalModel:
         return regrid.regrid_model(self, start_time, n_steps, grid, method, channels, save=save, save_config=save_config)
 
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
-               save: bool = False, save_config: dict | None = None, grid=None, regrid_method: str = "conservative"):
+               save: bool = False, save_config: dict | None = None, grid=None, regrid_method: str = "conservative", events=None,
+               neighbourhoods_km=()):
         """Scores of the deterministic forecast at every lead time 0 .. ``n_steps`` (skyrim_amd/verify.py): bias, MAE, RMSE,
         CRPS (= MAE for one member) and, with a ``climatology``, ACC, area-weighted per channel.  The model's TimeLoop is advanced, each
         valid time's truth is uploaded and the state is scored where it lies in HBM: no forecast state goes to the host.  ``truth``:
@@ -197,9 +204,13 @@ class GlobalModel:
         lead time.  Channels present in both forecast and truth are scored.  Returns ``verify.Scores``; ``save=True`` writes
         ``{model}-scores.json`` under the forecast id directory.  ``grid=`` (the forms of ``regrid_forecast``) scores on that target
         grid: forecast and truth, both on the model's grid, are regridded by ``regrid_method`` on the device and scored with the target's
-        area weights; the scores' JSON then carries the grid's label."""
+        area weights; the scores' JSON then carries the grid's label.  ``events={channel: [thresholds]}`` also verifies the events "above
+        the threshold" (skyrim_amd/events.py): the 2 x 2 table with POD, FAR, CSI, ETS and frequency bias, the Brier score
+        and, over the radii ``neighbourhoods_km``, the fractions skill score, in ``Scores.events``."""
         from ... import verify
         extra = {} if grid is None else dict(grid=grid, regrid_method=regrid_method)
+        if events is not None:
+            extra.update(events=events, neighbourhoods_km=neighbourhoods_km)
         return verify.verify_model(self, start_time, n_steps=n_steps, truth=truth, climatology=climatology, channels=channels, save=save,
                                    save_config=save_config, **extra)
 

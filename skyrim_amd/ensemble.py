@@ -184,11 +184,13 @@ def _world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, derived=None, grid=None,
-             regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
+             neighbourhoods_km=(), scores=False, derived=None, grid=None, regrid_method="conservative", perturbation="white",
+             length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
-    ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on."""
+    ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
+    ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them)."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -226,6 +228,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     for ch, vals in (quantiles or {}).items():
         for q in vals:
             quantile_position(q, int(n_members))
+    if events is not None:
+        event_request(events, neighbourhoods_km, exceed, known, n_members, scores)
     missing = [c for c in (channels or []) if c not in names]
     if missing:
         raise ValueError(f"channels {missing} are not output channels of this model")
@@ -244,11 +248,25 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
             {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}, saved)
 
 
+def event_request(events, neighbourhoods_km, exceed, known, n_members, scores) -> tuple[dict, list]:
+    """({channel: [thresholds]}, [radii in km]) of ``ensemble_forecast(events=, neighbourhoods_km=)``; ``events=True`` means the
+    thresholds of ``exceed``.  Events are verified against a truth, so they need ``scores=True``."""
+    from . import events as eventing
+    if not scores:
+        raise ValueError("events= verifies the exceedance events against a truth: it needs scores=True")
+    if events is True:
+        if not exceed:
+            raise ValueError("events=True means the thresholds of exceed=, which is empty")
+        events = dict(exceed)
+    return eventing.check_request(known, events, neighbourhoods_km, n_members, "an output channel of this model or one of the derived fields")
+
+
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        tracks: bool = False, track_config=None, derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
-        length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
+        tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), derived=None, grid=None,
+        regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0,
+        lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
     from .common import generate_forecast_id, save_forecast
@@ -256,18 +274,24 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
-                                                  perturb_channels)
+                                                  keep_members, events, neighbourhoods_km, scores, derived, grid, regrid_method, perturbation,
+                                                  length_scale_km, alpha, lmax, perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
     names = list(model.out_channel_names)
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
     scorer = None
+    ev = d_ev = {}                                         # keyword arguments of the raw / regridded and of the derived scorer
+    if events is not None:                                 # names of derived fields go to the derived scorer, as those of ``exceed`` do
+        events, radii = event_request(events, neighbourhoods_km, exceed, names + list(derived or []), M, scores)
+        raw, der = ({k: v for k, v in events.items() if (k in names) == own} for own in (True, False))
+        ev = dict(events=raw, neighbourhoods_km=radii) if raw else {}
+        d_ev = dict(events=der, neighbourhoods_km=radii) if der else {}
     if scores:                                             # (refusals of the request come before anything touches the device)
         from . import verify
         scorer = verify.LeadScorer(gm.model_name, names, model.grid.lat, model.grid.lon, M, verify.default_truth(gm) if truth is None else truth,
-                                   climatology, channels, device=model.device)
+                                   climatology, channels, device=model.device, **ev)
     tracker = None
     if tracks:
         from . import tracks as tracking
@@ -282,7 +306,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         if scores:
             adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None)
             dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
-                                        device=model.device, adapt=adapt)
+                                        device=model.device, adapt=adapt, **d_ev)
     regridder = rscorer = None
     if grid is not None:                                   # the same products on the target grid (skyrim_amd/regrid.py)
         from . import regrid
@@ -291,7 +315,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         if scores:
             rscorer = verify.LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, M, scorer.truth.src, climatology, channels,
                                         device=model.device,
-                                        adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device))
+                                        adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device),
+                                        **ev)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device

@@ -20,6 +20,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     track_detect                                         (cyclone candidates of M states, include/skyrim_track.h)
     derive_fields                                        (derived channels of M states, include/skyrim_derive.h)
     regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
+    event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
 """
 from __future__ import annotations
 
@@ -548,6 +549,19 @@ def _regrid(members, table, channels, row_start, row_count, row_weight, col_star
     regrid.run(list(members), table, list(channels), (row_start, row_count, row_weight), (col_start, col_count, col_weight), out)
 
 
+# ---- event verification ----------------------------------------------------------------------------------------------------------- #
+def _event_counts(members, table, truth, channels, n_thr, thresholds, counts, hy, hx, sums, workspace) -> None:
+    """``thresholds``: the thresholds of all event channels one after the other, ``n_thr[e]`` of them for channel e."""
+    from . import events
+    if sum(n_thr) != len(thresholds) or len(n_thr) != len(channels):
+        raise ValueError("event_counts: n_thr holds one count per channel and sums to len(thresholds)")
+    split, at = [], 0
+    for n in n_thr:
+        split.append(list(thresholds[at:at + n]))
+        at += n
+    events.run(list(members), table, truth, list(channels), split, counts, list(hy), hx, sums, workspace)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -613,6 +627,8 @@ _SCHEMAS = [
     ("derive_fields(Tensor[] members, Tensor table, int[] program, float[] weights, Tensor(a!) out, Tensor? rowc, int[] edges) -> ()", _derive_fields),
     ("regrid(Tensor[] members, Tensor table, int[] channels, Tensor row_start, Tensor row_count, Tensor row_weight, Tensor col_start, "
      "Tensor col_count, Tensor col_weight, Tensor(a!) out) -> ()", _regrid),
+    ("event_counts(Tensor[] members, Tensor table, Tensor truth, int[] channels, int[] n_thr, float[] thresholds, Tensor(a!) counts, int[] hy, "
+     "Tensor? hx, Tensor(b!)? sums, Tensor(c!)? workspace) -> ()", _event_counts),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]

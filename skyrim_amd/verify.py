@@ -5,6 +5,7 @@ Three layers:
 
 * the binding of libskyrim_score.so (``SPEC``, ``load_library``, ``score``); the same call is ``torch.ops.skyrim_hip.score_fields``;
 * ``area_weights`` and ``Scores`` -- the latitude weights and the labelled table the host forms from the kernel's per-channel sums;
+* threshold events (Brier, reliability, ROC, contingency scores, FSS) are skyrim_amd/events.py; ``LeadScorer(events=...)`` runs them;
 * the drivers: ``verify_model`` (``GlobalModel.verify``), ``LeadScorer`` (what ``ensemble.run`` calls at every lead time with
   ``scores=True``) and ``score_prediction`` for forecasts that are already on disk.
 """
@@ -151,7 +152,8 @@ class Scores:
     climatology; crps / spread / ssr as ensemble metrics need M > 1 -- the others are absent, not NaN-filled; at M = 1 ``crps`` is
     present and equals ``mae``).  ``sums``: DataArray(slot, time, channel), the kernel's own per-channel sums (``SLOTS``) the table is
     formed from.  ``rank_histogram``: (time, channel, rank) area-weighted frequencies that sum to 1, ``rank_counts`` the exact integers
-    summed over the latitude rows; both None at M = 1."""
+    summed over the latitude rows; both None at M = 1.  ``events``: the ``events.EventScores`` of threshold events when they were asked
+    for (``events=``), else None."""
 
     def __init__(self, model_name, n_members, times, channels, sums, slots, rank_counts=None, rank_histogram=None, forecast_id=""):
         from .labeled import DataArray
@@ -177,6 +179,7 @@ class Scores:
         self.table = DataArray(np.stack([rows[m] for m in names]) if names else np.zeros((0, len(self.times), len(self.channels))),
                                ["metric", "time", "channel"], dict(metric=names, **coords))
         self.grid = ""                                          # the label of the target grid when the scores were made on one (regrid.py)
+        self.events = None                                      # events.EventScores (skyrim_amd/events.py)
         self.rank_counts = self.rank_histogram = None
         if rank_counts is not None:
             rc = dict(rank=np.arange(M + 1), **coords)
@@ -201,6 +204,8 @@ class Scores:
         if self.rank_counts is not None:
             doc["rank_counts"] = self.rank_counts.values.tolist()
             doc["rank_histogram"] = clean(self.rank_histogram.values.tolist())
+        if self.events is not None:
+            doc["events"] = self.events.to_doc()
         return json.dumps(doc)
 
     def save(self, output_dir) -> str:
@@ -221,6 +226,9 @@ class Scores:
                   doc["slots"], None if rc is None else np.array(rc, np.int64), None if rc is None else nan(doc["rank_histogram"]),
                   doc.get("forecast_id", ""))
         out.grid = doc.get("grid", "")
+        if "events" in doc:
+            from .events import EventScores
+            out.events = EventScores.from_doc(doc["events"], doc["n_members"], times)
         return out
 
     @classmethod
@@ -313,11 +321,16 @@ class LeadScorer:
     the order of its (C, H, W) states; the channels scored are those the truth (and the climatology) also holds, restricted to
     ``channels`` when given.  ``adapt``: an object with ``names(fields)`` and ``upload(fields, time, scored, dst, idx)`` that stands between the
     truth's own channels and the forecast's (``derived.TruthDeriver``: the truth of a derived field is derived from raw channels;
-    ``regrid.TruthRegridder``: the truth is on another grid, named by its ``truth_grid``, and regridded to the scorer's)."""
+    ``regrid.TruthRegridder``: the truth is on another grid, named by its ``truth_grid``, and regridded to the scorer's).
+    ``events``: {channel: [thresholds]} among the scored channels, and ``neighbourhoods_km``: after the scores of a lead time the events
+    "above the threshold" are counted on the same states and truth (skyrim_amd/events.py) and land in ``Scores.events``."""
 
     def __init__(self, model_name, names, lat, lon, n_members, truth, climatology=None, channels=None, device="cuda:0", forecast_id="",
-                 adapt=None):
+                 adapt=None, events=None, neighbourhoods_km=()):
         check_request(n_members, names, channels)
+        if events is not None:
+            from . import events as eventing
+            events, neighbourhoods_km = eventing.check_request(names, events, neighbourhoods_km, n_members, "a channel of the forecast")
         if truth is None:
             raise ValueError("scores need a truth: a data source, a DataArray or a saved forecast")
         self.model_name, self.names, self.M, self.forecast_id = model_name, list(names), int(n_members), forecast_id
@@ -339,6 +352,12 @@ class LeadScorer:
         self.weights_host = area_weights(self.lat)
         self.times, self.sums, self.counts = [], [], []
         self._dev = None
+        self.events = None
+        if events is not None:
+            unscored = [c for c in events if c not in self.scored]
+            if unscored:
+                raise ValueError(f"events: the channels {unscored} are not among the scored channels (the truth must hold them too)")
+            self.events = eventing.LeadEvents(self.names, self.lat, self.lon, self.M, events, neighbourhoods_km, device=self.device)
 
     def _buffers(self):
         if self._dev is None:
@@ -382,6 +401,8 @@ class LeadScorer:
         self.sums.append(b["out"][self._idx_dev].cpu().numpy())
         if b["counts"] is not None:
             self.counts.append(b["counts"][self._idx_dev].cpu().numpy().reshape(len(self._idx), H, self.M + 1))
+        if self.events is not None:
+            self.events.add(states, table, b["truth"])         # one more read of the event channels of members and truth
 
     def result(self) -> Scores:
         wanted = [k for k, need in zip(SLOTS, (DET, DET, DET, VAR, CRPS, CRPS, CRPS, ACC, ACC, ACC)) if self.flags & need]
@@ -393,7 +414,10 @@ class LeadScorer:
             rc = per_row.sum(axis=2)
             w = self.weights_host
             rh = np.einsum("j,tcjr->tcr", w, per_row.astype(np.float64)) / (len(self.lon) * w.sum())
-        return Scores(self.model_name, self.M, self.times, self.scored, sums, wanted, rc, rh, self.forecast_id)
+        scores = Scores(self.model_name, self.M, self.times, self.scored, sums, wanted, rc, rh, self.forecast_id)
+        if self.events is not None:
+            scores.events = self.events.result(self.times, self.weights_host)
+        return scores
 
 
 def _finish(scores: Scores, save: bool, save_config):
@@ -407,11 +431,16 @@ def _finish(scores: Scores, save: bool, save_config):
 
 
 def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels=None, save: bool = False,
-                 save_config: dict | None = None, grid=None, regrid_method: str = "conservative") -> Scores:
+                 save_config: dict | None = None, grid=None, regrid_method: str = "conservative", events=None,
+                 neighbourhoods_km=()) -> Scores:
     """``GlobalModel.verify`` (core/models/base.py has the user-facing description)."""
     from .datasource import get_initial_condition_for_model
     model = gm.model
     check_request(1, model.out_channel_names, channels)
+    ev = {} if events is None else dict(events=events, neighbourhoods_km=neighbourhoods_km)
+    if events is not None:
+        from . import events as eventing
+        eventing.check_request(model.out_channel_names, events, neighbourhoods_km, 1)
     if n_steps < 0:
         raise ValueError("n_steps >= 0")
     regridder = None
@@ -421,10 +450,10 @@ def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None
         regridder = regrid.LeadRegridder(names, model.grid.lat, model.grid.lon, 1, grid, regrid_method, device=model.device)
         scorer = LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, 1, default_truth(gm) if truth is None else truth,
                             climatology, channels, device=model.device,
-                            adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device))
+                            adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device), **ev)
     else:
         scorer = LeadScorer(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1,
-                            default_truth(gm) if truth is None else truth, climatology, channels, device=model.device)
+                            default_truth(gm) if truth is None else truth, climatology, channels, device=model.device, **ev)
     if torch.device(model.device).type != "cuda":
         raise RuntimeError("verify scores the forecast with HIP kernels where it lies: the model must be on a GPU")
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
@@ -451,10 +480,11 @@ def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None
     return _finish(result, save, save_config)
 
 
-def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=None, model_name: str = "") -> Scores:
+def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=None, model_name: str = "", events=None,
+                     neighbourhoods_km=()) -> Scores:
     """Scores of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file or
     zarr store, or a list of such files (their time entries in order, duplicates of a valid time scored once).  Each time entry is
-    uploaded on its own and goes through the same kernel as ``verify``."""
+    uploaded on its own and goes through the same kernel as ``verify``; ``events`` / ``neighbourhoods_km`` as there."""
     from .labeled import DataArray, open_dataarray
     items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
     arrays = []
@@ -471,7 +501,8 @@ def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=No
     first = arrays[0]
     names = first.channel.values.tolist()
     lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    scorer = LeadScorer(model_name or "forecast", names, lat, lon, 1, truth, climatology, channels, device=device)
+    scorer = LeadScorer(model_name or "forecast", names, lat, lon, 1, truth, climatology, channels, device=device,
+                        **({} if events is None else dict(events=events, neighbourhoods_km=neighbourhoods_km)))
     if scorer.device.type != "cuda" or not torch.cuda.is_available():
         raise RuntimeError("score_prediction scores with HIP kernels: it needs a GPU")
     seen = set()

@@ -2,7 +2,8 @@
 the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
 channels to print, and the kind of perturbation (``--perturbation spherical --length_scale_km --lmax``: this is where spread against skill is
 tuned; the ``ensemble`` command keeps white noise), and the grid to score on (``--grid 1.5deg --regrid_method conservative``: forecast and
-truth are regridded on the device, skyrim_amd/regrid.py; the default scores on the model's own grid).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
+truth are regridded on the device, skyrim_amd/regrid.py; the default scores on the model's own grid), and the threshold events to verify
+(``--event ws10m:15,25 --neighbourhood_km 100``, both repeatable: skyrim_amd/events.py).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
 ``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
 from __future__ import annotations
 
@@ -19,13 +20,19 @@ from .verify import DEFAULT_CHANNELS
 def run_verify(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
                filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
                seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None,
-               grid: str | None = None, regrid_method: str = "conservative"):
+               grid: str | None = None, regrid_method: str = "conservative", event=(), neighbourhood_km=()):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
     from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None
+    asked = {}
+    if event:                                              # --event ws10m:15,25 (repeatable): threshold events, skyrim_amd/events.py
+        from .events import parse_event
+        asked = dict(events=dict(parse_event(e) for e in event), neighbourhoods_km=tuple(neighbourhood_km))
+    elif neighbourhood_km:
+        raise ValueError("--neighbourhood_km gives the scales of the events' fractions skill score: it needs --event")
     model = Skyrim(model_name, ic_source=initial_conditions)
     start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
     step_h = model.model.time_step.total_seconds() / 3600
@@ -35,6 +42,7 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
     scored = filter_vars.split(",") if bool(filter_vars) else None
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
     on_grid = {} if not grid else dict(grid=grid, regrid_method=regrid_method)
+    on_grid.update(asked)
     if members == 1:
         scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg, **on_grid)
     else:
@@ -56,6 +64,20 @@ def lines(scores, channels) -> list[str]:
         for c in names:
             vals = scores.table.values[:, t, scores.channels.index(c)]
             out.append(f"+{lead:g}h {c}: " + " ".join(f"{m}={v:.6g}" for m, v in zip(metrics, vals)))
+    return out
+
+
+def event_lines(scores) -> list[str]:
+    """One line per lead time, event channel and threshold: the event scores that are single numbers."""
+    ev = getattr(scores, "events", None)
+    out = []
+    for t, time in enumerate(ev.times if ev is not None else []):
+        lead = (time - ev.times[0]).total_seconds() / 3600
+        for e, c in enumerate(ev.channels):
+            for k, thr in enumerate(ev.thresholds[c]):
+                vals = " ".join(f"{m}={float(getattr(ev, m).values[t, e, k]):.6g}" for m in ev.names if m != "fss")
+                fss = "" if ev.fss is None else " fss=" + ",".join(f"{v:.6g}" for v in ev.fss.values[t, e, k])
+                out.append(f"+{lead:g}h {c}>{thr:g}: {vals}{fss}")
     return out
 
 
@@ -86,15 +108,21 @@ def lines(scores, channels) -> list[str]:
               "such as 1.5deg; forecast and truth are regridded on the device")
 @click.option("--regrid_method", type=click.Choice(["conservative", "bilinear", "nearest"]), default="conservative",
               help="How --grid is reached (first-order conservative is what WeatherBench 2 uses)")
+@click.option("--event", type=str, multiple=True, help="Verify the event NAME above each threshold, NAME:THRESHOLD[,THRESHOLD...] such as "
+              "t2m:273.15,300 (repeatable; at most 4 thresholds each): Brier score, reliability, ROC, contingency scores in the JSON file")
+@click.option("--neighbourhood_km", type=float, multiple=True, help="Radius in km of a neighbourhood of the events' fractions skill score "
+              "(repeatable, at most 4; 0 = point-wise)")
 def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
-           perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method):
+           perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km):
     if modal:
         raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
     scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
-                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method)
+                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km)
     if scores is None:
         return None
     for ln in lines(scores, [c for c in channels.split(",") if c]):
+        click.echo(ln)
+    for ln in event_lines(scores):
         click.echo(ln)
     click.echo(scores.path)
     return scores.path
