@@ -118,6 +118,7 @@ class GlobalModel:
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
+                          aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -147,7 +148,11 @@ class GlobalModel:
         checked against their size.  ``events={channel: [thresholds]}`` (``True``: the thresholds of ``exceed``), with ``scores=True``,
         verifies the events "above the threshold" at each lead time (skyrim_amd/events.py): Brier score and decomposition,
         reliability curve, ROC and, over the radii ``neighbourhoods_km``, the fractions skill score land in ``scores.events`` of the raw,
-        derived and regridded scores."""
+        derived and regridded scores.  ``aggregates=["ws10m:max:24h", "t2m:mean:24h", "ws10m:hours_above@15:all", "msl:when_min:all"]``
+        asks for time-window aggregates ``channel:stat:window`` (skyrim_amd/aggregate.py) of raw channels and of the fields in
+        ``derived``: every member is reduced over the lead times of each window on the device, and the same ``products``, ``exceed`` /
+        ``quantiles`` / ``events`` under the aggregates' names (``ws10m_max_24h``), the members with ``keep_members`` and the scores with
+        ``scores=True`` land in ``EnsembleForecast.aggregated[window label]``, with the window ends as time axis."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -156,6 +161,8 @@ class GlobalModel:
             extra["derived"] = derived
         if grid is not None:
             extra.update(grid=grid, regrid_method=regrid_method)
+        if aggregates is not None:
+            extra["aggregates"] = aggregates
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -181,6 +188,18 @@ class GlobalModel:
         ``{model}-derived``.  A field whose input channels the model lacks is refused with ValueError before the device is touched."""
         from ... import derived
         return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config)
+
+    def aggregate_forecast(self, start_time: datetime.datetime, n_steps: int = 4, aggregates: List[str] = (), derived: List[str] | None = None,
+                           save: bool = False, save_config: dict | None = None):
+        """Time-window aggregates of the deterministic forecast over the lead times 1 .. ``n_steps`` (skyrim_amd/aggregate.py).
+        ``aggregates``: requests ``channel:stat:window`` -- ``stat`` one of max, min, mean, sum, hours_above@<threshold>, when_max, when_min
+        (hours since ``start_time``); ``window`` ``<N>h`` (consecutive windows (w N, (w + 1) N] hours after ``start_time``; N a multiple of
+        the model's step) or ``all``; ``derived``: derived fields the requests may name.  The model's TimeLoop is advanced and every state is
+        folded into the windows where it lies in HBM; only the closed windows cross to the host.  Returns {window label:
+        DataArray(time = window ends, channel = aggregates, lat, lon)} with the coordinate ``window_start``; ``save=True`` writes each as the
+        forecast of ``{model}-agg<label>``.  A request that cannot be served is refused with ValueError before the device is touched."""
+        from ... import aggregate
+        return aggregate.aggregate_model(self, start_time, n_steps, list(aggregates), derived=derived, save=save, save_config=save_config)
 
     def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative",
                         channels: List[str] | None = None, save: bool = False, save_config: dict | None = None):

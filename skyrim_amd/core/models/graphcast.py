@@ -133,6 +133,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
                                   "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")
 
+    def aggregate_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator aggregate_forecast advances: "
+                                  "aggregate its forecast with skyrim_amd.aggregate.aggregate_prediction(forecast_or_saved_files, aggregates)")
+
     def regrid_forecast(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator regrid_forecast advances: "
                                   "regrid its forecast with skyrim_amd.regrid.regrid_prediction(forecast_or_saved_files, grid, method)")

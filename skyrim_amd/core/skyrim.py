@@ -68,6 +68,19 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.derive_fields(start_time, n_steps=n_steps, fields=fields, **kwargs)
 
+    def aggregate_forecast(self, start_time: datetime.datetime, n_steps: int = 4, aggregates=(), **kwargs):
+        """Time-window aggregates (daily maximum, mean, hours above a threshold, time of the peak ...) of the single model's forecast as
+        {window label: DataArray(time = window ends, channel = aggregates, lat, lon)} (``GlobalModel.aggregate_forecast`` has the
+        arguments).  ``ensemble_forecast(..., aggregates=[...])`` gives their ensemble products."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.aggregate_forecast(start_time, n_steps=n_steps, aggregates=aggregates, **kwargs)
+
+    @staticmethod
+    def aggregate_prediction(pred, aggregates, derived=None, device="cuda:0"):
+        """Time-window aggregates of a forecast that is already in memory or on disk (``aggregate.aggregate_prediction``)."""
+        from .. import aggregate
+        return aggregate.aggregate_prediction(pred, aggregates, derived=derived, device=device)
+
     def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative", **kwargs):
         """The single model's forecast on another latitude-longitude grid -- "1.5deg", (lat, lon) arrays or a region -- as a
         DataArray(time, channel, lat, lon) (``GlobalModel.regrid_forecast`` has the arguments).

@@ -164,6 +164,7 @@ class EnsembleForecast:
     tracks: object = None        # tracks.Tracks with ``tracks=True``
     derived: object = None       # derived.DerivedProducts with ``derived=[...]``
     regridded: object = None     # regrid.RegriddedProducts with ``grid=...``
+    aggregated: dict = field(default_factory=dict)      # {window label: aggregate.AggregatedProducts} with ``aggregates=[...]``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -185,11 +186,12 @@ def _world_size() -> int:
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, derived=None, grid=None, regrid_method="conservative", perturbation="white",
-             length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
+             neighbourhoods_km=(), scores=False, aggregates=None, derived=None, grid=None, regrid_method="conservative",
+             perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
-    ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
+    ``aggregates``: the time-window aggregates asked for (skyrim_amd/aggregate.py), of raw channels and derived fields on the model's own
+    grid; ``exceed``, ``quantiles`` and ``events`` may name them (``ws10m_max_24h``) as well.  ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
     ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them)."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
@@ -211,6 +213,14 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         from . import derived as deriving
         deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members)
     known = names + list(derived or [])
+    aplan = None
+    if aggregates is not None:
+        from . import aggregate
+        aplan = aggregate.check_request(known, aggregates, model.time_step, n_steps, model.grid.lat, model.grid.lon, n_members)
+        clash = [f for g in aplan.groups for f in g.fields if f in known]
+        if clash:
+            raise ValueError(f"aggregates: {clash} are already channels of this forecast")
+        known = known + [f for g in aplan.groups for f in g.fields]
     tabs = None
     if grid is not None:
         from . import regrid
@@ -222,7 +232,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         for ch, vals in (table or {}).items():
             if ch not in known:
                 raise ValueError(f"{what}: channel {ch!r} is not an output channel of this model"
-                                 + ("" if derived is None else " or one of the derived fields"))
+                                 + ("" if derived is None else " or one of the derived fields")
+                                 + ("" if aplan is None else " or one of the aggregates"))
             if not 1 <= len(vals) <= cap:
                 raise ValueError(f"{what}[{ch!r}]: 1 to {cap} values per channel, got {len(vals)}")
     for ch, vals in (quantiles or {}).items():
@@ -238,7 +249,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
-        need = 0 if keep_members == "regridded" else int(n_members) * len(saved) * len(known) * len(model.grid.lat) * len(model.grid.lon) * 4
+        planes = len(saved) * (len(names) + len(derived or [])) + (0 if aplan is None else sum(g.n_windows * len(g.fields) for g in aplan.groups))
+        need = 0 if keep_members == "regridded" else int(n_members) * planes * len(model.grid.lat) * len(model.grid.lon) * 4
         if tabs is not None:                                # the regridded members are checked at the size they have
             need += int(n_members) * len(saved) * len(names) * tabs.lat.size * tabs.lon.size * 4
         if need > _PINNED_LIMIT:
@@ -264,7 +276,7 @@ def event_request(events, neighbourhoods_km, exceed, known, n_members, scores) -
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), derived=None, grid=None,
+        tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), aggregates=None, derived=None, grid=None,
         regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0,
         lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
@@ -274,8 +286,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, events, neighbourhoods_km, scores, derived, grid, regrid_method, perturbation,
-                                                  length_scale_km, alpha, lmax, perturb_channels)
+                                                  keep_members, events, neighbourhoods_km, scores, aggregates, derived, grid, regrid_method,
+                                                  perturbation, length_scale_km, alpha, lmax, perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
@@ -283,8 +295,20 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
     scorer = None
     ev = d_ev = {}                                         # keyword arguments of the raw / regridded and of the derived scorer
+    aggregator, a_events, a_radii = None, {}, []
+    if aggregates is not None:                             # time-window aggregates (skyrim_amd/aggregate.py): names of aggregates in
+        from . import aggregate                            # ``exceed``, ``quantiles`` and ``events`` go to their window group
+        aggregator = aggregate.LeadAggregator(names, model.grid.lat, model.grid.lon, M, aggregates, start_time, model.time_step,
+                                              device=model.device, n_steps=n_steps, derived=list(derived or []))
+        a_fields = [f for g in aggregator.plan.groups for f in g.fields]
+        a_exceed, a_quant = ({k: v for k, v in t.items() if k in a_fields} for t in (exceed, quantiles))
+        exceed, quantiles = ({k: v for k, v in t.items() if k not in a_fields} for t in (exceed, quantiles))
     if events is not None:                                 # names of derived fields go to the derived scorer, as those of ``exceed`` do
-        events, radii = event_request(events, neighbourhoods_km, exceed, names + list(derived or []), M, scores)
+        known = names + list(derived or []) + (a_fields if aggregator is not None else [])
+        events, radii = event_request(events, neighbourhoods_km, dict(exceed, **a_exceed) if aggregator is not None else exceed, known, M, scores)
+        if aggregator is not None:
+            a_events, a_radii = {k: v for k, v in events.items() if k in a_fields}, radii
+            events = {k: v for k, v in events.items() if k not in a_fields}
         raw, der = ({k: v for k, v in events.items() if (k in names) == own} for own in (True, False))
         ev = dict(events=raw, neighbourhoods_km=radii) if raw else {}
         d_ev = dict(events=der, neighbourhoods_km=radii) if der else {}
@@ -307,6 +331,17 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None)
             dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
                                         device=model.device, adapt=adapt, **d_ev)
+    ascorers = {}
+    if aggregator is not None and scores:                  # one scorer per window group, against the same aggregates of the truth
+        for g in aggregator.plan.groups:
+            inner = None if derived is None else deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device,
+                                                                       levels=deriver.plan.levels or None)
+            hook = aggregate.TruthAggregator(g.requests, model.grid.lat, model.grid.lon, start_time, model.time_step, device=model.device,
+                                             inner=inner)
+            g_ev = {k: v for k, v in a_events.items() if k in g.fields}
+            ascorers[g.label] = (hook, verify.LeadScorer(gm.model_name, g.fields, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology,
+                                                         None, device=model.device, adapt=hook,
+                                                         **(dict(events=g_ev, neighbourhoods_km=a_radii) if g_ev else {})))
     regridder = rscorer = None
     if grid is not None:                                   # the same products on the target grid (skyrim_amd/regrid.py)
         from . import regrid
@@ -365,6 +400,22 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         ddev_out = {p: torch.empty((D, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products}
         ddev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_exceed.items()}
         ddev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_quant.items()}
+    if aggregator is not None:                             # per window group: one entry per complete window
+        ahost = {}
+        for g in aggregator.plan.groups:
+            nf, nw = len(g.fields), g.n_windows
+            ex = {ch: v for ch, v in a_exceed.items() if ch in g.fields}
+            qu = {ch: v for ch, v in a_quant.items() if ch in g.fields}
+            ahost[g.label] = dict(
+                ends=[], starts=[], ex=ex, qu=qu,
+                host={p: np.empty((nw, nf, n_lat, n_lon), np.float32) for p in products},
+                host_ex={ch: np.empty((nw, len(v), n_lat, n_lon), np.float32) for ch, v in ex.items()},
+                host_q={ch: np.empty((nw, len(v), n_lat, n_lon), np.float32) for ch, v in qu.items()},
+                members=np.empty((M, nw, nf, n_lat, n_lon), np.float32) if keep_members else None,
+                dev={p: torch.empty((nf, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products},
+                dev_ex={ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in ex.items()},
+                dev_q={ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in qu.items()})
+        agg_derived = any(r.channel in (derived or []) for r in aggregator.plan.requests)
     if regridder is not None:
         r_lat, r_lon = regridder.lat_out.size, regridder.lon_out.size
         rhw = r_lat * r_lon
@@ -396,7 +447,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
             if tracker is not None:
                 tracker.add(time, states, table)           # cyclone candidates of this lead time: only their records leave the device
-            if deriver is not None and (keep or dscorer is not None):
+            fold_derived = aggregator is not None and agg_derived and k >= 1
+            if deriver is not None and (keep or dscorer is not None or fold_derived):
                 dstates, dtable = deriver.add(states, table)      # ONE launch: D derived planes per member, read below like raw channels
                 if dscorer is not None:
                     dscorer.add(time, dstates, dtable)
@@ -415,6 +467,35 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     if keep_members:
                         for m, st in enumerate(dstates):
                             dhost_members[m, s] = st.cpu().numpy()
+            if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
+                for c in aggregator.add(k, time, states, table, (dstates, dtable) if fold_derived else None):
+                    a, w, nf = ahost[c.label], c.window, len(c.fields)
+                    a["ends"].append(c.end)                # windows close independently of ``save_every``
+                    a["starts"].append(c.start)
+                    if products:
+                        stats(c.states, c.table, 0, nf * hw, **{p: a["dev"][p] for p in products})
+                    for p in products:
+                        a["host"][p][w] = a["dev"][p].cpu().numpy()
+                    for ch, thr in a["ex"].items():
+                        stats(c.states, c.table, c.fields.index(ch) * hw, hw, exceed=a["dev_ex"][ch], thresholds=thr)
+                        a["host_ex"][ch][w] = a["dev_ex"][ch].cpu().numpy()
+                    for ch, lev in a["qu"].items():
+                        stats(c.states, c.table, c.fields.index(ch) * hw, hw, quant=a["dev_q"][ch], levels=lev)
+                        a["host_q"][ch][w] = a["dev_q"][ch].cpu().numpy()
+                    if keep_members:
+                        for m, st in enumerate(c.states):
+                            a["members"][m, w] = st.cpu().numpy()
+                    if c.label in ascorers:
+                        hook, asc = ascorers[c.label]
+                        hook.window(c.times)               # the truth is aggregated over the same valid times
+                        asc.add(c.end, c.states, c.table)
+                    if save:
+                        for p in products:
+                            da = DataArray(a["host"][p][w:w + 1], ["time", "channel", "lat", "lon"],
+                                           dict(time=[c.end], channel=c.fields, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
+                            name = product_model_name(gm.model_name, M, f"agg{c.label}-{p}")
+                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
+                            paths.append(save_forecast(da, name, c.start, c.end, gm.source_label, config=pcfg))
             if regridder is not None and (keep or rscorer is not None):
                 rstates, rtable = regridder.add(states, table)    # ONE launch: every channel of every member on the target grid
                 if rscorer is not None:
@@ -535,6 +616,25 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             ens.regridded.scores = rscorer.result()
             ens.regridded.scores.forecast_id = fid
             ens.regridded.scores.grid = grid_label
+    if aggregator is not None:
+        for g in aggregator.plan.groups:
+            a = ahost[g.label]
+
+            def alabelled(arr, dim, labels):
+                return DataArray(arr, ["time", dim, "lat", "lon"], dict(time=a["ends"], **{dim: labels}, window_start=a["starts"], **grid))
+            prod = aggregate.AggregatedProducts(g.label, list(g.fields), **{p: alabelled(a["host"][p], "channel", g.fields) for p in products})
+            prod.exceedance = {ch: alabelled(a["host_ex"][ch], "threshold", np.asarray(a["ex"][ch], np.float32)) for ch in a["ex"]}
+            prod.quantile = {ch: alabelled(a["host_q"][ch], "quantile", np.asarray(a["qu"][ch], np.float64)) for ch in a["qu"]}
+            prod.incomplete = aggregator.incomplete.get(g.label)
+            if keep_members:
+                prod.members = DataArray(a["members"], ["member", "time", "channel", "lat", "lon"],
+                                         dict(member=np.arange(M), time=a["ends"], channel=g.fields, window_start=a["starts"], **grid))
+            if g.label in ascorers:
+                hook, asc = ascorers[g.label]
+                prod.scores = asc.result()
+                prod.scores.forecast_id = fid
+                prod.dropped = dict(hook.dropped)
+            ens.aggregated[g.label] = prod
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
     ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
     if keep_members:

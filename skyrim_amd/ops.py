@@ -21,6 +21,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     derive_fields                                        (derived channels of M states, include/skyrim_derive.h)
     regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
     event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
+    agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
 """
 from __future__ import annotations
 
@@ -562,6 +563,13 @@ def _event_counts(members, table, truth, channels, n_thr, thresholds, counts, hy
     events.run(list(members), table, truth, list(channels), split, counts, list(hy), hx, sums, workspace)
 
 
+# ---- time-window aggregates --------------------------------------------------------------------------------------------------------- #
+def _agg_update(members, table, program, params, stamp: float, acc) -> None:
+    """``program`` / ``params``: aggregate.encode(ops); ``stamp``: the lead time in hours; ``acc``: (M, D, H, W)."""
+    from . import aggregate
+    aggregate.run(list(members), table, aggregate.decode(program, params), acc, stamp)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -629,6 +637,7 @@ _SCHEMAS = [
      "Tensor col_count, Tensor col_weight, Tensor(a!) out) -> ()", _regrid),
     ("event_counts(Tensor[] members, Tensor table, Tensor truth, int[] channels, int[] n_thr, float[] thresholds, Tensor(a!) counts, int[] hy, "
      "Tensor? hx, Tensor(b!)? sums, Tensor(c!)? workspace) -> ()", _event_counts),
+    ("agg_update(Tensor[] members, Tensor table, int[] program, float[] params, float stamp, Tensor(a!) acc) -> ()", _agg_update),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]
