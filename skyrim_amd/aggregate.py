@@ -516,6 +516,7 @@ class AggregatedProducts:
     scores: object = None
     dropped: dict = field(default_factory=dict)
     incomplete: object = None
+    points: object = None        # points.PointForecast of the group's fields with ``points=...``
 
 
 def _labelled(arr, fields, ends, starts, lat, lon):

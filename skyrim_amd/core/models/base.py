@@ -118,6 +118,7 @@ class GlobalModel:
                           channels: List[str] | None = None, save_every: int = 1, keep_members: bool = False, save: bool = False,
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
+                          points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
                           aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
@@ -152,7 +153,12 @@ class GlobalModel:
         asks for time-window aggregates ``channel:stat:window`` (skyrim_amd/aggregate.py) of raw channels and of the fields in
         ``derived``: every member is reduced over the lead times of each window on the device, and the same ``products``, ``exceed`` /
         ``quantiles`` / ``events`` under the aggregates' names (``ws10m_max_24h``), the members with ``keep_members`` and the scores with
-        ``scores=True`` land in ``EnsembleForecast.aggregated[window label]``, with the window ends as time axis."""
+        ``scores=True`` land in ``EnsembleForecast.aggregated[window label]``, with the window ends as time axis.  ``points=`` names places
+        -- ``{name: (lat, lon)}``, a list of ``(name, lat, lon)`` or a CSV file ``name,lat,lon`` (skyrim_amd/points.py) -- at
+        which every member is sampled on the device at each saved lead time, by ``point_method`` (bilinear, nearest), for the channels
+        ``point_channels`` (raw channels and fields of ``derived``; default ``channels``, or every raw and derived channel): the
+        ``points.PointForecast`` (member, time, channel, point) lands in ``EnsembleForecast.points``, and each aggregate group's fields at
+        the points, sampled when a window closes, in ``EnsembleForecast.aggregated[label].points``."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -163,6 +169,8 @@ class GlobalModel:
             extra.update(grid=grid, regrid_method=regrid_method)
         if aggregates is not None:
             extra["aggregates"] = aggregates
+        if points is not None:
+            extra.update(points=points, point_channels=point_channels, point_method=point_method)
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -200,6 +208,21 @@ class GlobalModel:
         forecast of ``{model}-agg<label>``.  A request that cannot be served is refused with ValueError before the device is touched."""
         from ... import aggregate
         return aggregate.aggregate_model(self, start_time, n_steps, list(aggregates), derived=derived, save=save, save_config=save_config)
+
+    def point_forecast(self, start_time: datetime.datetime, n_steps: int = 4, points=None, channels: List[str] | None = None,
+                       derived: List[str] | None = None, method: str = "bilinear", save: bool = False, save_config: dict | None = None):
+        """The deterministic forecast at the lead times 0 .. ``n_steps`` at scattered places (skyrim_amd/points.py).
+        ``points``: ``{name: (lat, lon)}``, a list of ``(name, lat, lon)`` or a CSV file ``name,lat,lon``; ``channels``: raw channels and
+        fields of ``derived`` (default: all of both); ``method``: bilinear (two taps per axis, the longitude periodic; a point outside the
+        model's latitudes is refused) or nearest.  The model's TimeLoop is advanced and every state is sampled where it lies in HBM; only
+        the sampled values cross to the host.  Returns a ``points.PointForecast`` with one member; ``save=True`` writes
+        ``{model}-points.json`` under the forecast id directory.  A request that cannot be served is refused with ValueError before the
+        device is touched."""
+        from ... import points as pointing
+        if points is None:
+            raise ValueError("point_forecast needs points: {name: (lat, lon)}, a list of (name, lat, lon) or a CSV file name,lat,lon")
+        return pointing.point_model(self, start_time, n_steps, points, channels=channels, derived=derived, method=method, save=save,
+                                    save_config=save_config)
 
     def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative",
                         channels: List[str] | None = None, save: bool = False, save_config: dict | None = None):

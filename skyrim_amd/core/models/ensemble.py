@@ -128,6 +128,10 @@ class GlobalEnsemble:
         raise ValueError(f"aggregate_forecast aggregates the forecast of ONE model; {self!r} is a multi-model ensemble -- aggregate its saved "
                          "ensemble-mean files with skyrim_amd.aggregate.aggregate_prediction, or build Skyrim(<one model name>)")
 
+    def point_forecast(self, *args, **kwargs):
+        raise ValueError(f"point_forecast samples the forecast of ONE model; {self!r} is a multi-model ensemble -- sample its saved "
+                         "ensemble-mean files with skyrim_amd.points.extract_prediction, or build Skyrim(<one model name>)")
+
     def rollout(self, start_time: datetime.datetime, n_steps: int = 3, save: bool = True, save_config: dict | None = None):
         """Roll every member out, one at a time; returns (mean of the members' final predictions over the shared channels, paths of the per-step
         ensemble-mean files -- ``[]`` with ``save=False``).  The members' own per-step files stay where ``GlobalModel.rollout`` wrote them

@@ -137,6 +137,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator aggregate_forecast advances: "
                                   "aggregate its forecast with skyrim_amd.aggregate.aggregate_prediction(forecast_or_saved_files, aggregates)")
 
+    def point_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator point_forecast advances: "
+                                  "sample its forecast with skyrim_amd.points.extract_prediction(forecast_or_saved_files, points)")
+
     def regrid_forecast(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator regrid_forecast advances: "
                                   "regrid its forecast with skyrim_amd.regrid.regrid_prediction(forecast_or_saved_files, grid, method)")

@@ -81,6 +81,12 @@ class Skyrim:
         from .. import aggregate
         return aggregate.aggregate_prediction(pred, aggregates, derived=derived, device=device)
 
+    def point_forecast(self, start_time: datetime.datetime, n_steps: int = 4, points=None, **kwargs):
+        """The single model's forecast at scattered places -- stations, cities, wind farms -- as a ``points.PointForecast``
+        (``GlobalModel.point_forecast`` has the arguments).  ``ensemble_forecast(..., points=...)`` gives every member there."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.point_forecast(start_time, n_steps=n_steps, points=points, **kwargs)
+
     def regrid_forecast(self, start_time: datetime.datetime, n_steps: int = 4, grid="1.5deg", method: str = "conservative", **kwargs):
         """The single model's forecast on another latitude-longitude grid -- "1.5deg", (lat, lon) arrays or a region -- as a
         DataArray(time, channel, lat, lon) (``GlobalModel.regrid_forecast`` has the arguments).

@@ -165,6 +165,7 @@ class EnsembleForecast:
     derived: object = None       # derived.DerivedProducts with ``derived=[...]``
     regridded: object = None     # regrid.RegriddedProducts with ``grid=...``
     aggregated: dict = field(default_factory=dict)      # {window label: aggregate.AggregatedProducts} with ``aggregates=[...]``
+    points: object = None        # points.PointForecast with ``points=...``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -186,13 +187,16 @@ def _world_size() -> int:
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, aggregates=None, derived=None, grid=None, regrid_method="conservative",
-             perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None):
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", aggregates=None, derived=None,
+             grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
     ``aggregates``: the time-window aggregates asked for (skyrim_amd/aggregate.py), of raw channels and derived fields on the model's own
     grid; ``exceed``, ``quantiles`` and ``events`` may name them (``ws10m_max_24h``) as well.  ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
-    ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them)."""
+    ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them).
+    ``points`` / ``point_channels`` / ``point_method``: the places every member is sampled at (skyrim_amd/points.py), the raw channels and
+    derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -246,6 +250,16 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         raise ValueError(f"channels {missing} are not output channels of this model")
     noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
     saved = list(range(0, n_steps + 1, save_every))
+    if points is not None:                                  # the points, their channels, a bilinear point outside the source rows, the host limit
+        from . import points as pointing
+        pts = pointing.Points(points)
+        picked, raw, der = pointing._sources(names, derived, point_channels if point_channels is not None else (list(channels) if channels else None))
+        for nm, ch in ((names, raw), (list(derived or []), der)):
+            if ch:
+                pointing.check_request(nm, model.grid.lat, model.grid.lon, n_members, pts, ch, point_method, len(saved))
+        pointing.host_limit(n_members, len(saved), len(picked), len(pts))
+        for g in (aplan.groups if aplan is not None else []):
+            pointing.check_request(g.fields, model.grid.lat, model.grid.lon, n_members, pts, None, point_method, max(g.n_windows, 1))
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
@@ -276,9 +290,10 @@ def event_request(events, neighbourhoods_km, exceed, known, n_members, scores) -
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
-        tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), aggregates=None, derived=None, grid=None,
-        regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0,
-        lmax: int | None = None, perturb_channels=None) -> EnsembleForecast:
+        tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
+        point_method: str = "bilinear", aggregates=None, derived=None, grid=None, regrid_method: str = "conservative",
+        perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+        perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
     from .common import generate_forecast_id, save_forecast
@@ -286,8 +301,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, events, neighbourhoods_km, scores, aggregates, derived, grid, regrid_method,
-                                                  perturbation, length_scale_km, alpha, lmax, perturb_channels)
+                                                  keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, aggregates,
+                                                  derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
@@ -352,6 +367,15 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                                         device=model.device,
                                         adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device),
                                         **ev)
+    pointer, apointers = None, {}
+    if points is not None:                                 # every member at the points (skyrim_amd/points.py): raw channels and derived fields
+        from . import points as pointing                   # at each saved lead time, each aggregate group when a window closes
+        pts = pointing.Points(points)
+        pointer = pointing.LeadPoints(names, model.grid.lat, model.grid.lon, M, pts, point_channels if point_channels is not None else
+                                      (list(channels) if channels else None), point_method, model.device, list(derived or []), len(saved))
+        if aggregator is not None:
+            apointers = {g.label: pointing.LeadPoints(g.fields, model.grid.lat, model.grid.lon, M, pts, None, point_method, model.device, (),
+                                                      max(g.n_windows, 1)) for g in aggregator.plan.groups}
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -467,6 +491,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     if keep_members:
                         for m, st in enumerate(dstates):
                             dhost_members[m, s] = st.cpu().numpy()
+            if pointer is not None and keep:               # the members where they lie: one launch per source buffer, only the values leave
+                pointer.add(time, states, table, (dstates, dtable) if pointer.needs_derived else None)
             if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
                 for c in aggregator.add(k, time, states, table, (dstates, dtable) if fold_derived else None):
                     a, w, nf = ahost[c.label], c.window, len(c.fields)
@@ -485,6 +511,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     if keep_members:
                         for m, st in enumerate(c.states):
                             a["members"][m, w] = st.cpu().numpy()
+                    if c.label in apointers:
+                        apointers[c.label].add(c.end, c.states, c.table)
                     if c.label in ascorers:
                         hook, asc = ascorers[c.label]
                         hook.window(c.times)               # the truth is aggregated over the same valid times
@@ -626,6 +654,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             prod.exceedance = {ch: alabelled(a["host_ex"][ch], "threshold", np.asarray(a["ex"][ch], np.float32)) for ch in a["ex"]}
             prod.quantile = {ch: alabelled(a["host_q"][ch], "quantile", np.asarray(a["qu"][ch], np.float64)) for ch in a["qu"]}
             prod.incomplete = aggregator.incomplete.get(g.label)
+            if g.label in apointers:
+                prod.points = apointers[g.label].result(f"{gm.model_name}-ens{M}-agg{g.label}", fid, window_start=a["starts"])
             if keep_members:
                 prod.members = DataArray(a["members"], ["member", "time", "channel", "lat", "lon"],
                                          dict(member=np.arange(M), time=a["ends"], channel=g.fields, window_start=a["starts"], **grid))
@@ -635,6 +665,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 prod.scores.forecast_id = fid
                 prod.dropped = dict(hook.dropped)
             ens.aggregated[g.label] = prod
+    if pointer is not None:
+        ens.points = pointer.result(f"{gm.model_name}-ens{M}", fid)
+        if save:
+            from .common import OUTPUT_DIR
+            paths.append(ens.points.save(cfg.get("output_dir") or OUTPUT_DIR))
     ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
     ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
     if keep_members:

@@ -22,6 +22,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
     event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
+    point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
 """
 from __future__ import annotations
 
@@ -570,6 +571,13 @@ def _agg_update(members, table, program, params, stamp: float, acc) -> None:
     aggregate.run(list(members), table, aggregate.decode(program, params), acc, stamp)
 
 
+# ---- point extraction ------------------------------------------------------------------------------------------------------------------- #
+def _point_gather(members, table, channels, records, out) -> None:
+    """``records``: points.device_records(...), int32 (P, 8); ``out``: (M, len(channels), P) or (M, stride >= len(channels) P)."""
+    from . import points
+    points.run(list(members), table, list(channels), records, out)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -638,6 +646,7 @@ _SCHEMAS = [
     ("event_counts(Tensor[] members, Tensor table, Tensor truth, int[] channels, int[] n_thr, float[] thresholds, Tensor(a!) counts, int[] hy, "
      "Tensor? hx, Tensor(b!)? sums, Tensor(c!)? workspace) -> ()", _event_counts),
     ("agg_update(Tensor[] members, Tensor table, int[] program, float[] params, float stamp, Tensor(a!) acc) -> ()", _agg_update),
+    ("point_gather(Tensor[] members, Tensor table, int[] channels, Tensor records, Tensor(a!) out) -> ()", _point_gather),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]
