@@ -119,7 +119,7 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          aggregates: List[str] | None = None,
+                          scenarios: dict | None = None, aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -158,7 +158,15 @@ class GlobalModel:
         which every member is sampled on the device at each saved lead time, by ``point_method`` (bilinear, nearest), for the channels
         ``point_channels`` (raw channels and fields of ``derived``; default ``channels``, or every raw and derived channel): the
         ``points.PointForecast`` (member, time, channel, point) lands in ``EnsembleForecast.points``, and each aggregate group's fields at
-        the points, sampled when a window closes, in ``EnsembleForecast.aggregated[label].points``."""
+        the points, sampled when a window closes, in ``EnsembleForecast.aggregated[label].points``.
+        ``scenarios={"channels": ["z500"], "region": (lat_s, lat_n, lon_w, lon_e), "n_clusters": 3, "n_eofs": 3, "normalise": "spread"}``
+        relates the members to each other as patterns (skyrim_amd/scenarios.py): at each saved lead time ONE device pass
+        makes the member Gram matrix of the named raw channels over the region (None: the globe; a box may cross the date line), and from
+        it the host makes the clusters by Ward's method (labels, sizes, probabilities, representative members), the leading EOFs of the
+        spread and, with ``scores=True``, the fair energy score; the clusters' mean fields and the EOF patterns are made on the device.
+        ``normalise``: how channels are weighed against each other (``"spread"``: by their mean member variance, ``"std"``: by the
+        model's ``channel_std``, ``"none"``).  This version takes raw channels on the model's own grid only; 2 <= n_members <= 64 (63
+        with ``scores=True``: the truth is one more column).  The ``scenarios.Scenarios`` land in ``EnsembleForecast.scenarios``."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -171,6 +179,8 @@ class GlobalModel:
             extra["aggregates"] = aggregates
         if points is not None:
             extra.update(points=points, point_channels=point_channels, point_method=point_method)
+        if scenarios is not None:
+            extra["scenarios"] = scenarios
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,

@@ -166,6 +166,7 @@ class EnsembleForecast:
     regridded: object = None     # regrid.RegriddedProducts with ``grid=...``
     aggregated: dict = field(default_factory=dict)      # {window label: aggregate.AggregatedProducts} with ``aggregates=[...]``
     points: object = None        # points.PointForecast with ``points=...``
+    scenarios: object = None     # scenarios.Scenarios with ``scenarios={...}``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -181,14 +182,24 @@ def channel_std(model) -> torch.Tensor:
     return std.to(model.device, torch.float32).reshape(-1).contiguous()
 
 
+def scenario_std(model, names) -> np.ndarray:
+    """The sigma of each OUTPUT channel for ``scenarios={"normalise": "std"}``: ``channel_std`` when the model's output channels are its
+    input channels (one sigma each), refused otherwise."""
+    std = channel_std(model).cpu().numpy().astype(np.float64)
+    if std.size != len(names):
+        raise NotImplementedError(f"{type(model).__name__}: channel_std holds {std.size} values for {len(names)} output channels; "
+                                  "normalise='std' needs one per output channel")
+    return std
+
+
 def _world_size() -> int:
     import torch.distributed as dist
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", aggregates=None, derived=None,
-             grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, aggregates=None,
+             derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
@@ -196,7 +207,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     grid; ``exceed``, ``quantiles`` and ``events`` may name them (``ws10m_max_24h``) as well.  ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
     ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them).
     ``points`` / ``point_channels`` / ``point_method``: the places every member is sampled at (skyrim_amd/points.py), the raw channels and
-    derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation."""
+    derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation.  ``scenarios``: the dict of
+    skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -260,6 +272,12 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         pointing.host_limit(n_members, len(saved), len(picked), len(pts))
         for g in (aplan.groups if aplan is not None else []):
             pointing.check_request(g.fields, model.grid.lat, model.grid.lon, n_members, pts, None, point_method, max(g.n_windows, 1))
+    if scenarios is not None:                               # raw channels of the model's grid only; names of other products are refused by name
+        from . import scenarios as scen
+        other = list(derived or []) + ([f for g in aplan.groups for f in g.fields] if aplan is not None else [])
+        req = scen.check_request(names, model.grid.lat, model.grid.lon, n_members, scenarios, scores, other)
+        if req["normalise"] == "std":
+            channel_std(model)                              # NotImplementedError for a model without per-channel sigmas
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
@@ -291,7 +309,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", aggregates=None, derived=None, grid=None, regrid_method: str = "conservative",
+        point_method: str = "bilinear", scenarios=None, aggregates=None, derived=None, grid=None, regrid_method: str = "conservative",
         perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
@@ -301,8 +319,9 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, aggregates,
-                                                  derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax, perturb_channels)
+                                                  keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, scenarios,
+                                                  aggregates, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
+                                                  perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     M = int(n_members)
@@ -331,6 +350,9 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         from . import verify
         scorer = verify.LeadScorer(gm.model_name, names, model.grid.lat, model.grid.lon, M, verify.default_truth(gm) if truth is None else truth,
                                    climatology, channels, device=model.device, **ev)
+        if scenarios is not None:                          # the truth is a column of the Gram matrix: it must hold the scenario channels
+            from . import scenarios as scen
+            scen.check_scored(scenarios.get("channels") or [], scorer.scored)
     tracker = None
     if tracks:
         from . import tracks as tracking
@@ -376,6 +398,14 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         if aggregator is not None:
             apointers = {g.label: pointing.LeadPoints(g.fields, model.grid.lat, model.grid.lon, M, pts, None, point_method, model.device, (),
                                                       max(g.n_windows, 1)) for g in aggregator.plan.groups}
+    scenarist = None
+    if scenarios is not None:                              # clusters, EOFs and the energy score of the members (skyrim_amd/scenarios.py)
+        from . import scenarios as scen
+        sigma = None
+        if scenarios.get("normalise") == "std":
+            sigma = scenario_std(model, names)
+        scenarist = scen.LeadScenarios(names, model.grid.lat, model.grid.lon, M, scenarios, device=model.device, truth=scorer is not None,
+                                       std=sigma)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -491,6 +521,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     if keep_members:
                         for m, st in enumerate(dstates):
                             dhost_members[m, s] = st.cpu().numpy()
+            if scenarist is not None and keep:             # one Gram launch, its M' x M' doubles to the host, cluster means, EOF patterns
+                scenarist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
             if pointer is not None and keep:               # the members where they lie: one launch per source buffer, only the values leave
                 pointer.add(time, states, table, (dstates, dtable) if pointer.needs_derived else None)
             if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
@@ -665,6 +697,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 prod.scores.forecast_id = fid
                 prod.dropped = dict(hook.dropped)
             ens.aggregated[g.label] = prod
+    if scenarist is not None:
+        ens.scenarios = scenarist.result(f"{gm.model_name}-ens{M}", fid)
     if pointer is not None:
         ens.points = pointer.result(f"{gm.model_name}-ens{M}", fid)
         if save:

@@ -23,6 +23,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
     point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
+    gram / member_combine                                (member Gram matrices and linear combinations of M states, include/skyrim_gram.h)
 """
 from __future__ import annotations
 
@@ -578,6 +579,20 @@ def _point_gather(members, table, channels, records, out) -> None:
     points.run(list(members), table, list(channels), records, out)
 
 
+# ---- ensemble scenarios ----------------------------------------------------------------------------------------------------------------- #
+def _gram(members, table, truth, channels, region, lat_weight, out, workspace) -> None:
+    """``region``: (j0, nj, i0, ni); ``out``: float64 (len(channels), M', M') or (len(channels), stride >= M'^2) with M' = M + (truth is not None); ``workspace``:
+    scenarios.workspace_bytes(M', nc, nj, ni) bytes."""
+    from . import scenarios
+    scenarios.gram(list(members), table, truth, list(channels), list(region), lat_weight, out, workspace)
+
+
+def _member_combine(members, table, channels, coef, b, out) -> None:
+    """``coef``: float32 (K, M); ``b``: float32 (K,); ``out``: float32 (K, len(channels), H, W)."""
+    from . import scenarios
+    scenarios.combine(list(members), table, list(channels), coef, b, out)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -647,6 +662,9 @@ _SCHEMAS = [
      "Tensor? hx, Tensor(b!)? sums, Tensor(c!)? workspace) -> ()", _event_counts),
     ("agg_update(Tensor[] members, Tensor table, int[] program, float[] params, float stamp, Tensor(a!) acc) -> ()", _agg_update),
     ("point_gather(Tensor[] members, Tensor table, int[] channels, Tensor records, Tensor(a!) out) -> ()", _point_gather),
+    ("gram(Tensor[] members, Tensor table, Tensor? truth, int[] channels, int[] region, Tensor lat_weight, Tensor(a!) out, "
+     "Tensor(b!) workspace) -> ()", _gram),
+    ("member_combine(Tensor[] members, Tensor table, int[] channels, Tensor coef, Tensor b, Tensor(a!) out) -> ()", _member_combine),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]

@@ -371,6 +371,10 @@ class LeadScorer:
             self._idx_dev = torch.tensor(self._idx, device=dev)
         return self._dev
 
+    def truth_state(self) -> torch.Tensor:
+        """The (C, H, W) device state that holds the truth of the last ``add`` in the rows of the scored channels (zeros elsewhere)."""
+        return self._buffers()["truth"]
+
     def _upload(self, fields: _Fields, time, dst: torch.Tensor):
         if self.adapt is not None:
             return self.adapt.upload(fields, time, self.scored, dst, self._idx_dev)
