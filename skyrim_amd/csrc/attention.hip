@@ -292,7 +292,9 @@ qkv_attention_kernel(const QkvAttnArgs a) {
         int src[9];
 #pragma unroll
         for (int f = 0; f < 9; ++f) src[f] = srcn[f];
-        uint4 qv[9], kf[9];
+        typedef unsigned u32x9 __attribute__((ext_vector_type(9)));
+        u32x9 qx, qy, qz, qw;                           // Q fragment f = (qx[f], qy[f], qz[f], qw[f]): see the query loop
+        uint4 kf[9];
         uint2 vh[9][2];
         const T* xp[3];
         int xstep[3];
@@ -366,7 +368,8 @@ qkv_attention_kernel(const QkvAttnArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { v[r] = (qa[i][0][r] + bq[r]) * a.scale; v[4 + r] = (qa[i][1][r] + bq[4 + r]) * a.scale; }
                 split8<T, 1>(v, o);
-                qv[f] = o[0];
+                asm volatile("" : "+v"(o[0].x), "+v"(o[0].y), "+v"(o[0].z), "+v"(o[0].w));
+                qx[f] = o[0].x; qy[f] = o[0].y; qz[f] = o[0].z; qw[f] = o[0].w;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { v[r] = ka[i][0][r] + bk[r]; v[4 + r] = ka[i][1][r] + bk[4 + r]; }
                 split8<T, 1>(v, o);
@@ -378,6 +381,10 @@ qkv_attention_kernel(const QkvAttnArgs a) {
                     split4<T, 1>(u, h);
                     vh[f][df] = h[0];
                 }
+                // (converted HERE: left to the compiler the conversions sink to where the fragments are first used, below the QKV loops of the
+                // later triples, and every triple's 24 accumulators stay alive until then: 252-256 registers in use, none for Q; pinned, 208-210
+                // WITH the 36 of Q)
+                asm volatile("" : "+v"(kf[f].x), "+v"(kf[f].y), "+v"(kf[f].z), "+v"(kf[f].w), "+v"(vh[f][0].x), "+v"(vh[f][0].y), "+v"(vh[f][1].x), "+v"(vh[f][1].y));
             }
         }
         uint4 vf[2][5];
@@ -388,16 +395,15 @@ qkv_attention_kernel(const QkvAttnArgs a) {
             vf[df][4] = make_uint4(vh[8][df].x, vh[8][df].y, 0, 0);
         }
         if (wi + S::NWAVES < a.nW) load_src(wi + S::NWAVES);
-        // A ROLLED loop over the query fragments: qv[qf] is then indexed at run time and lives in scratch memory (144 bytes per lane, written once
-        // and read once per window).  That is NOT an L1 hit: WRITE_SIZE of a launch exceeds the attention output by exactly 144 B x 64 lanes per
-        // (window, head) -- the fragments go out past the L2 and come back, so a reload is a fabric round trip.  It is therefore requested one
-        // iteration ahead (qn), under the softmax and P V of the fragment before it.  Fully unrolled the nine softmax bodies were scheduled into
-        // each other: 78-105 spilled registers and 0.28 ms per launch at C = 384 against 0.235 rolled (measured; the two-launch form: 0.29)
-        uint4 qn = qv[0];
+        // A ROLLED loop over the query fragments (fully unrolled the nine softmax bodies were scheduled into each other: 78-105 spilled registers
+        // and 0.28 ms per launch at C = 384 against 0.235 rolled).  The nine Q fragments are then indexed at run time.  As nine uint4 that put
+        // them into scratch memory, 144 bytes per lane that went out past the L2 and came back (WRITE_SIZE of a launch was the attention output
+        // plus exactly those bytes).  As four 9-element vectors -- component c of every fragment in one -- they stay in 36 registers: qf is the
+        // same for the whole wave, so an element is read with the hardware's register index (s_set_gpr_idx_on / v_mov_b32 / s_set_gpr_idx_off:
+        // twelve instructions per iteration, no memory).  tests/test_pangu_attention_scratch.py holds ScratchSize at 0.
 #pragma unroll 1
         for (int qf = 0; qf < 9; ++qf) {
-            const uint4 qc = qn;
-            if (qf < 8) qn = qv[qf + 1];                // requested a whole softmax + P V ahead of its use
+            const uint4 qc = make_uint4(qx[qf], qy[qf], qz[qf], qw[qf]);
             // the lane's query: the token of fragment row l15 -> (z_q, h_q, w_q); copy c = (w_q + 1) mod 4 makes every group address a multiple of 8 bytes
             const int qi = attn_key(qf, l15);
             const int zq = qi >= 72 ? 1 : 0, hq = (qi - 72 * zq) / 12, wq = qi - 72 * zq - 12 * hq;
