@@ -119,7 +119,7 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          scenarios: dict | None = None, aggregates: List[str] | None = None,
+                          scenarios: dict | None = None, breeding: dict | None = None, aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -166,7 +166,14 @@ class GlobalModel:
         spread and, with ``scores=True``, the fair energy score; the clusters' mean fields and the EOF patterns are made on the device.
         ``normalise``: how channels are weighed against each other (``"spread"``: by their mean member variance, ``"std"``: by the
         model's ``channel_std``, ``"none"``).  This version takes raw channels on the model's own grid only; 2 <= n_members <= 64 (63
-        with ``scores=True``: the truth is one more column).  The ``scenarios.Scenarios`` land in ``EnsembleForecast.scenarios``."""
+        with ``scores=True``: the truth is one more column).  The ``scenarios.Scenarios`` land in ``EnsembleForecast.scenarios``.
+        ``breeding={"cycles": 3, "norm": "total", "paired": False}`` breeds the initial perturbations through the model itself
+        (skyrim_amd/breeding.py): ``perturbation`` then names the SEED; each cycle steps every member once, takes the
+        difference from the control forecast, scales it back to ``perturb_scale`` (``norm="total"``: one factor per member over the
+        perturbed channels, which keeps the balance between variables the model produced; ``"channel"``: every channel to its own
+        amplitude) and puts it on the analysis again -- two device launches per cycle for all members.  ``paired=True`` makes the members
+        2j - 1 and 2j the two signs of one bred vector.  Models with one history level and the same channels in and out (pangu,
+        fourcastnet, fourcastnet_v2); ``EnsembleForecast.breeding_growth`` holds the growth record (cycle, member, channel)."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -181,6 +188,8 @@ class GlobalModel:
             extra.update(points=points, point_channels=point_channels, point_method=point_method)
         if scenarios is not None:
             extra["scenarios"] = scenarios
+        if breeding is not None:
+            extra["breeding"] = breeding
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,

@@ -5,7 +5,8 @@ Three layers:
 * the binding of libskyrim_ens.so (``SPEC``, ``load_library``, ``perturb``, ``stats``, ``member_table``); the same calls are
   ``torch.ops.skyrim_hip.ens_perturb / ens_stats`` (skyrim_amd/ops.py);
 * ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb`` (white noise) or
-  ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), ONE TimeLoop
+  ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), with ``breeding=`` bred from those seeds
+  through the model itself (skyrim_amd/breeding.py), ONE TimeLoop
   generator per member advanced step-major (all members one step, then the statistics of that lead time), so only the members'
   current states are alive on the GPU;
 * ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
@@ -167,6 +168,8 @@ class EnsembleForecast:
     aggregated: dict = field(default_factory=dict)      # {window label: aggregate.AggregatedProducts} with ``aggregates=[...]``
     points: object = None        # points.PointForecast with ``points=...``
     scenarios: object = None     # scenarios.Scenarios with ``scenarios={...}``
+    breeding: object = None      # the normalised ``breeding=`` request (cycles, norm, paired) or None
+    breeding_growth: object = None      # (cycles, member, channel) float64 with ``breeding=``: breeding.Breeder.growth
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -198,8 +201,8 @@ def _world_size() -> int:
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, aggregates=None,
-             derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, breeding=None,
+             aggregates=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
@@ -208,7 +211,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them).
     ``points`` / ``point_channels`` / ``point_method``: the places every member is sampled at (skyrim_amd/points.py), the raw channels and
     derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation.  ``scenarios``: the dict of
-    skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only."""
+    skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only.  ``breeding``:
+    the dict of skyrim_amd/breeding.py (cycles, norm, paired); ``perturbation`` then names the seed."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -261,6 +265,9 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     if missing:
         raise ValueError(f"channels {missing} are not output channels of this model")
     noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
+    if breeding is not None:                                # cycles, norm, keys; one history level, the same channels in and out
+        from . import breeding as breed
+        breed.plan(model, breeding)
     saved = list(range(0, n_steps + 1, save_every))
     if points is not None:                                  # the points, their channels, a bilinear point outside the source rows, the host limit
         from . import points as pointing
@@ -309,8 +316,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, aggregates=None, derived=None, grid=None, regrid_method: str = "conservative",
-        perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+        point_method: str = "bilinear", scenarios=None, breeding=None, aggregates=None, derived=None, grid=None,
+        regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
@@ -320,10 +327,14 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
                                                   keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, scenarios,
-                                                  aggregates, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
+                                                  breeding, aggregates, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
                                                   perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
+    bplan = None
+    if breeding is not None:
+        from . import breeding as breed
+        bplan = breed.plan(model, breeding)
     M = int(n_members)
     names = list(model.out_channel_names)
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
@@ -423,19 +434,34 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     fid = cfg["forecast_id"]
     zarr = (cfg.get("file_type") or "netcdf") == "zarr"
 
+    sigma_all = std                                        # (breeding normalises with every channel's own sigma)
     if plan.channel_mask is not None and plan.kind == "white":
         std = torch.where(torch.from_numpy(plan.channel_mask).to(dev), std, torch.zeros_like(std))        # amplitude exactly 0 elsewhere
     spherical = noise.Perturber(plan, x0, std, float(perturb_scale), int(seed)) if plan.kind == "spherical" else None
-    loops = []
-    for m in range(M):
-        xm = torch.empty_like(x0)
+
+    def seed_member(m, xm):
         if spherical is not None:
             spherical.member(m, xm)
         else:
             perturb(x0, std, xm, hw, float(perturb_scale), int(seed), m)
+
+    breeder = None
+    if bplan is not None:                                  # the seeds bred through the model (skyrim_amd/breeding.py): they replace the seeds
+        breeder = breed.Breeder(model, bplan, x0, sigma_all, float(perturb_scale), int(seed), start_time, seed_member, mask=plan.channel_mask)
+        breeder.run(M)
+        if hasattr(model, "__dict__"):
+            model._resident_state = None
+    loops = []
+    for m in range(M):
+        if breeder is not None:
+            xm = breeder.member(m)
+        else:
+            xm = torch.empty_like(x0)
+            seed_member(m, xm)
         loops.append(model(start_time, xm))
         del xm
-    del x0, spherical                                      # (with it the work buffers of one member's synthesis)
+    breeding_growth = None if breeder is None else breeder.growth
+    del x0, spherical, breeder, sigma_all                  # (with them the work buffers of one member's synthesis and of the cycle)
     n_saved, C = len(saved), len(names)
     host = {p: np.empty((n_saved, C, n_lat, n_lon), np.float32) for p in products}
     host_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in exceed.items()}
@@ -629,7 +655,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         return da.sel(channel=list(channels)) if channels and dim == "channel" else da
 
     ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=plan.kind,
-                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None)
+                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None,
+                           breeding=None if bplan is None else bplan.as_dict(), breeding_growth=breeding_growth)
     if scorer is not None:
         ens.scores = scorer.result()
         ens.scores.forecast_id = fid

@@ -24,6 +24,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
     point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
     gram / member_combine                                (member Gram matrices and linear combinations of M states, include/skyrim_gram.h)
+    breed_norms / breed_apply                            (the two passes of a breeding cycle over M states, include/skyrim_breed.h)
 """
 from __future__ import annotations
 
@@ -593,6 +594,19 @@ def _member_combine(members, table, channels, coef, b, out) -> None:
     scenarios.combine(list(members), table, list(channels), coef, b, out)
 
 
+# ---- breeding cycles ---------------------------------------------------------------------------------------------------------------------- #
+def _breed_norms(y0, members, table, lat_weight, S, workspace) -> None:
+    """``S``: float64 (M, C); ``workspace``: breeding.workspace_bytes(M, C, H, W) bytes."""
+    from . import breeding
+    breeding.norms(y0, list(members), table, lat_weight, S, workspace)
+
+
+def _breed_apply(x0, y0, members, table, f, out, out_table) -> None:
+    """``f``: float32 (M, C); ``out``: M states, ``out[m]`` may be ``members[m]``; ``out_table``: ensemble.member_table(out)."""
+    from . import breeding
+    breeding.apply(x0, y0, list(members), table, f, list(out), out_table)
+
+
 # ---- spherical perturbations --------------------------------------------------------------------------------------------------- #
 def _noise_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``sigma``: the device table sigma_l 2^e, lmax floats; ``out``: [members][lmax][lmax][2][F]."""
@@ -665,6 +679,8 @@ _SCHEMAS = [
     ("gram(Tensor[] members, Tensor table, Tensor? truth, int[] channels, int[] region, Tensor lat_weight, Tensor(a!) out, "
      "Tensor(b!) workspace) -> ()", _gram),
     ("member_combine(Tensor[] members, Tensor table, int[] channels, Tensor coef, Tensor b, Tensor(a!) out) -> ()", _member_combine),
+    ("breed_norms(Tensor y0, Tensor[] members, Tensor table, Tensor lat_weight, Tensor(a!) S, Tensor(b!) workspace) -> ()", _breed_norms),
+    ("breed_apply(Tensor x0, Tensor y0, Tensor[] members, Tensor table, Tensor f, Tensor(a!)[] out, Tensor out_table) -> ()", _breed_apply),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
 ]

@@ -1,7 +1,8 @@
 """``verify`` command line: the options of ``forecast`` (skyrim_amd/forecast.py: same names, short flags and defaults) plus the size of
 the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
 channels to print, and the kind of perturbation (``--perturbation spherical --length_scale_km --lmax``: this is where spread against skill is
-tuned; the ``ensemble`` command keeps white noise), and the grid to score on (``--grid 1.5deg --regrid_method conservative``: forecast and
+tuned; ``--breed_cycles 3 --breed_norm total --breed_paired`` breeds those perturbations through the model, skyrim_amd/breeding.py;
+the ``ensemble`` command keeps white noise), and the grid to score on (``--grid 1.5deg --regrid_method conservative``: forecast and
 truth are regridded on the device, skyrim_amd/regrid.py; the default scores on the model's own grid), and the threshold events to verify
 (``--event ws10m:15,25 --neighbourhood_km 100``, both repeatable: skyrim_amd/events.py).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
 ``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
@@ -20,7 +21,8 @@ from .verify import DEFAULT_CHANNELS
 def run_verify(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
                filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
                seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None,
-               grid: str | None = None, regrid_method: str = "conservative", event=(), neighbourhood_km=()):
+               grid: str | None = None, regrid_method: str = "conservative", event=(), neighbourhood_km=(), breed_cycles: int = 0,
+               breed_norm: str = "total", breed_paired: bool = False):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
     from .core.models.base import adjust_lead_time
@@ -43,12 +45,13 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
     on_grid = {} if not grid else dict(grid=grid, regrid_method=regrid_method)
     on_grid.update(asked)
+    bred = {} if not breed_cycles else dict(breeding=dict(cycles=breed_cycles, norm=breed_norm, paired=breed_paired))
     if members == 1:
         scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg, **on_grid)
     else:
         ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed, products=(),
                                       channels=scored, climatology=climatology, scores=True, save_config=cfg, perturbation=perturbation,
-                                      length_scale_km=length_scale_km, lmax=lmax, **on_grid)
+                                      length_scale_km=length_scale_km, lmax=lmax, **bred, **on_grid)
         scores = ens.regridded.scores if grid else ens.scores
         scores.path = scores.save(cfg["output_dir"])
     return scores
@@ -104,6 +107,11 @@ def event_lines(scores) -> list[str]:
               help="Perturbation kind (members > 1): grid-point white noise, or spatially correlated fields on the sphere")
 @click.option("--length_scale_km", type=float, default=500.0, help="Correlation length of the spherical perturbations in km")
 @click.option("--lmax", type=int, default=None, help="Spectral truncation of the spherical perturbations (default: min(256, n_lat, n_lon / 2))")
+@click.option("--breed_cycles", type=int, default=0, help="Breed the perturbations through the model for this many cycles, 1-50 "
+              "(members > 1; 0 = the seed perturbations as they are)")
+@click.option("--breed_norm", type=click.Choice(["total", "channel"]), default="total",
+              help="Rescaling of a bred vector: one factor per member, or every channel to its own amplitude")
+@click.option("--breed_paired", is_flag=True, help="Members 2j-1 and 2j are the two signs of one bred vector")
 @click.option("--grid", type=str, default=None, help="Score on this grid instead of the model's own: a resolution that divides 180 degrees, "
               "such as 1.5deg; forecast and truth are regridded on the device")
 @click.option("--regrid_method", type=click.Choice(["conservative", "bilinear", "nearest"]), default="conservative",
@@ -113,11 +121,13 @@ def event_lines(scores) -> list[str]:
 @click.option("--neighbourhood_km", type=float, multiple=True, help="Radius in km of a neighbourhood of the events' fractions skill score "
               "(repeatable, at most 4; 0 = point-wise)")
 def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
-           perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km):
+           perturb_scale, seed, perturbation, length_scale_km, lmax, breed_cycles, breed_norm, breed_paired, grid, regrid_method, event,
+           neighbourhood_km):
     if modal:
         raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
     scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
-                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km)
+                        channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km,
+                        breed_cycles, breed_norm, breed_paired)
     if scores is None:
         return None
     for ln in lines(scores, [c for c in channels.split(",") if c]):
