@@ -94,7 +94,8 @@ int skgc_sum_linear_layer_norm(const skgc_sum_desc* desc, void* stream);
 /* ---- ABI v4: an interaction-network update as ONE kernel (csrc/graphcast_fused.hip; layouts: skyrim_amd/graphcast/fused.py) ----------
  *
  * Edge update + receiver sum, latent 512, on PACKED rows (multiples of 128; a receiver's run of rows never crosses a 128-row tile unless
- * it is longer than a tile; padding rows have recv < 0 and idx < 0):
+ * it is longer than a tile; padding rows have recv < 0 and idx < 0; the CONTENTS of a padding row of e_in are inert -- any value, 6e4 or NaN
+ * included, reaches no bit of agg, heads or the other rows of e_out, and the padding rows of e_out are not written):
  *     pre  = (has_fc1 ? e_in W_e^T : e_in) + sum_s term[s][ idx[s][row] ]            first Linear by distributivity (b1 folded into a term)
  *     y    = LayerNorm( swish(pre) W2^T + b2 ) * gamma + beta
  *     e_out[row] = e_in[row] + y   (has_fc1 only, nullable)          agg[ recv[row] ] = sum of y over the receiver's run of rows

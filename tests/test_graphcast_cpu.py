@@ -200,3 +200,106 @@ def test_identity_case_catches_swapped_columns_of_an_octet():
         perm = torch.arange(512)
         perm[i], perm[j] = j, i
         _trips(R.linear_fp32(c, col_map=perm), ref, R.BAR_LN, f"(g) columns {i} and {j} swapped")
+
+
+# ---- the fused kernels (tests/test_graphcast_fused_edges_gpu.py): the cases are well formed and the bounds bite ---------------------------- #
+def test_run_structures_obey_the_header_and_hit_their_edges():
+    """Every structure keeps the header's rule (a run crosses a tile boundary only if it is longer than a tile, its receivers are not
+    met again later) within 12 tiles; the seams structure ends runs at rows 62, 63, 64, 126 and 127 of its first tile."""
+    for name in R.RUN_STRUCTURES + ["mixed"]:
+        recv, n_nodes = R.mixed_runs() if name == "mixed" else R.run_structure(name)
+        assert len(recv) % R.TILE == 0 and len(recv) <= 12 * R.TILE and int(recv.max()) < n_nodes
+        ends = [i for i in range(len(recv)) if recv[i] >= 0 and (i + 1 == len(recv) or recv[i + 1] != recv[i])]
+        starts = [i for i in range(len(recv)) if recv[i] >= 0 and (i == 0 or recv[i - 1] != recv[i])]
+        assert len({int(recv[i]) for i in starts}) == len(starts), name
+        for i0, i1 in zip(starts, ends):
+            assert i0 // R.TILE == i1 // R.TILE or i1 - i0 + 1 > R.TILE, (name, i0, i1)
+        if name == "seams":
+            assert [i for i in ends if i < R.TILE] == [62, 63, 64, 126, 127]
+    lens = {int(n) for name in ("long_a", "long_b") for r in [R.run_structure(name)[0]] for n in torch.bincount(r[r >= 0])}
+    assert {128, 129, 256, 257, 300, 389} <= lens
+    assert R.continuations(R.run_structure("long_b")[0])[5] == [4, 5, 6]
+
+
+@pytest.fixture(scope="module")
+def sum_rows():
+    """fp32 rows of the size of the edge kernel's y (LayerNorm output: unit scale, offset by beta), per structure."""
+    def rows(name):
+        recv, n_nodes = R.run_structure(name)
+        y = (0.1 + torch.randn(len(recv), 64, generator=R.gen(9000 + len(recv)), dtype=torch.float64)).float()
+        return recv, n_nodes, y
+    return rows
+
+
+@pytest.mark.parametrize("name", R.RUN_STRUCTURES)
+@pytest.mark.parametrize("order", ["forward", "reverse", "pairwise"])
+def test_summation_bound_accepts_fp32_sums_in_any_order(sum_rows, name, order):
+    recv, n_nodes, y = sum_rows(name)
+    got = R.fp32_run_sums(y, recv, n_nodes, order)
+    ratio, excess = R.sum_bound_excess(got, y, recv, n_nodes)
+    assert excess <= 0 and ratio <= 1
+    has = torch.bincount(recv[recv >= 0], minlength=n_nodes) > 0
+    assert torch.isnan(got[~has]).all()
+
+
+@pytest.mark.parametrize("name,mistake", [("seams", "drop_last"), ("long_a", "drop_last"), ("singles", "drop_last"), ("long_a", "cont_to_next"), ("long_b", "cont_to_next"),
+                                          ("mid", "cont_to_next"), ("seams", "miss_63")])
+def test_summation_bound_rejects_the_mistakes_of_a_receiver_sum(sum_rows, name, mistake):
+    recv, n_nodes, y = sum_rows(name)
+    got = torch.nan_to_num(R.fp32_run_sums(y, recv, n_nodes, "forward", mistake))          # (a run that lost all its rows stays unwritten)
+    ratio, excess = R.sum_bound_excess(got, y, recv, n_nodes)
+    assert excess > 0 and ratio > 100, (ratio, excess)
+
+
+@pytest.mark.parametrize("n_src,rows", [(1, 129), (2, 257), (2, 1)])
+def test_node_bound_catches_a_dropped_lo_plane(n_src, rows):
+    c = R.fused_node_case(n_src, rows, 8000 + 10 * rows + n_src)
+    res = c["srcs"][0]
+    ref = R.fused_node_ref(c, res)
+    R.assert_close(R.fused_node_fp32(c, res), ref, R.BAR_LN, "fp32")
+    _trips(R.fused_node_fp32(c, res, w2=R.split_hi(c["w2"])), ref, R.BAR_LN, "W2 rounded to fp16")
+    _trips(R.fused_node_fp32(c, res, a_map=R.split_hi), ref, R.BAR_LN, "the operand rounded to fp16")
+
+
+@pytest.mark.parametrize("n_src", [1, 2])
+def test_node_offset_and_far_bounds_and_their_recorded_figures(n_src):
+    """The recorded fp32 figures are reproduced (within a factor of 4 either way: the reduction order of this machine's fp32 products
+    may differ from where they were recorded), and the offset-row bound rejects the one-pass variance."""
+    c = R.fused_node_case(n_src, 129, 8100 + n_src, "offset")
+    res = c["srcs"][0]
+    ref = R.fused_node_ref(c, res)
+    bound = R.LN_OFFSET_FACTOR * R.NODE_OFFSET_FP32[n_src]
+    err = R.assert_close(R.fused_node_fp32(c, res), ref, bound, "two-pass fp32")
+    assert err >= R.NODE_OFFSET_FP32[n_src] / 4
+    _trips(R.fused_node_fp32(c, res, one_pass=True), ref, bound, "one-pass variance")
+    c = R.fused_node_case(n_src, 129, 8200 + n_src, "far")
+    far = list(R.FAR_ROWS)
+    err = R.row_rel_err(R.fused_node_fp32(c, c["srcs"][0])[far], R.fused_node_ref(c, c["srcs"][0])[far])
+    assert R.NODE_FAR_FP32[n_src] / 4 <= err <= R.LN_OFFSET_FACTOR * R.NODE_FAR_FP32[n_src]
+
+
+def test_node_constant_rows_are_exact_in_fp32():
+    c = R.fused_node_case(2, 5, 8502, "constant")
+    assert torch.equal(R.fused_node_fp32(c), c["beta"].expand(5, 512))
+    assert torch.equal(R.fused_node_fp32(c, c["srcs"][0]), c["srcs"][0] + c["beta"])
+
+
+def test_edge_restatement_is_the_edge_mlp_by_distributivity():
+    """fused_edge_ref is the edge MLP on concat(e, v_s[send], v_r[recv]) -- gather_gemm_ref + linear_layer_norm_ref, which
+    test_mlp_is_gather_gemm_then_linear_layer_norm ties to oracle.graphcast_oracle -- up to the one rounding it adds to float64 operands,
+    the fp16 plane of the hidden activation (2^-11 of each h): the restatement is no private definition."""
+    recv, n_nodes = R.run_structure("seams")
+    c = R.fused_edge_case(31, recv, n_nodes)
+    g = R.gen(5)
+    vs, vr = torch.randn(300, 512, generator=g, dtype=torch.float64), torch.randn(300, 512, generator=g, dtype=torch.float64)
+    ws, wr = torch.randn(512, 512, generator=g, dtype=torch.float64) / 512 ** 0.5, torch.randn(512, 512, generator=g, dtype=torch.float64) / 512 ** 0.5
+    b1 = 0.1 * torch.randn(512, generator=g, dtype=torch.float64)
+    x = c["e"].double()
+    a = torch.cat([x, vs[c["send"].long()], vr[c["near"].long()]], dim=1)
+    w1 = torch.cat([c["w1"].double(), ws, wr], dim=1)
+    want = R.linear_layer_norm_ref(R.gather_gemm_ref([a], [None], [1536], w1, b1, 2), 512, c["w2"], c["b2"], c["gamma"], c["beta"])
+    c2 = dict(c, ts=vs @ ws.T + b1, tr=vr @ wr.T)
+    got = R.fused_edge_ref(c2, 2, 2)
+    # what is left: 512 roundings of 2^-11 / sqrt(3) of an h of unit size, through weights of variance 1 / 512 and a LayerNorm that divides
+    # by a spread of about one half -- a mean |error| of a few 1e-4, on outputs whose maximum is about 5
+    assert R.rel_err(got, want) < 1e-3 and (got - want).abs().mean() < 5e-4
