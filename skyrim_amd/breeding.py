@@ -229,6 +229,22 @@ def factors(S, std, perturb_scale: float, norm: str, mask, weight_sum: float, n_
 
 
 # ---- the cycle ------------------------------------------------------------------------------------------------------------------------------ #
+def step_once(model, time, x: torch.Tensor, who: str) -> torch.Tensor:
+    """Lead 1 of the model's own generator from ``x`` (1, 1, C, H, W) at ``time``, as (C, H, W); the generator is closed and its pending
+    non-finite check taken.  What a breeding cycle and a stochastic step (skyrim_amd/stochastic.py) advance a member with."""
+    loop = model(time, x)
+    try:
+        next(loop)
+        _, out, _ = next(loop)
+    except FloatingPointError as e:
+        raise FloatingPointError(f"{who}: {e}") from e
+    try:
+        loop.close()
+    except FloatingPointError as e:
+        raise FloatingPointError(f"{who}: {e}") from e
+    return (out[0] if out.dim() == 4 else out).contiguous()
+
+
 class Breeder:
     """The breeding cycle of one ``ensemble_forecast``.
 
@@ -272,17 +288,7 @@ class Breeder:
 
     def _step(self, x: torch.Tensor, who: str) -> torch.Tensor:
         """Lead 1 of the model's own generator from ``x``; the generator is closed and its pending non-finite check taken."""
-        loop = self.model(self.start_time, x)
-        try:
-            next(loop)
-            _, out, _ = next(loop)
-        except FloatingPointError as e:
-            raise FloatingPointError(f"breeding, {who}: {e}") from e
-        try:
-            loop.close()
-        except FloatingPointError as e:
-            raise FloatingPointError(f"breeding, {who}: {e}") from e
-        return (out[0] if out.dim() == 4 else out).contiguous()
+        return step_once(self.model, self.start_time, x, f"breeding, {who}")
 
     def _check_memory(self, n_members: int, batch: int) -> None:
         state = self.x0.numel() * 4

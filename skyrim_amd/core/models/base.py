@@ -119,7 +119,8 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          scenarios: dict | None = None, breeding: dict | None = None, aggregates: List[str] | None = None,
+                          scenarios: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
+                          aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -173,7 +174,19 @@ class GlobalModel:
         perturbed channels, which keeps the balance between variables the model produced; ``"channel"``: every channel to its own
         amplitude) and puts it on the analysis again -- two device launches per cycle for all members.  ``paired=True`` makes the members
         2j - 1 and 2j the two signs of one bred vector.  Models with one history level and the same channels in and out (pangu,
-        fourcastnet, fourcastnet_v2); ``EnsembleForecast.breeding_growth`` holds the growth record (cycle, member, channel)."""
+        fourcastnet, fourcastnet_v2); ``EnsembleForecast.breeding_growth`` holds the growth record (cycle, member, channel).
+        ``stochastic={"kind": "sppt", "amplitude": 0.3, "tau_h": 6.0, "length_scale_km": 500.0}`` perturbs the MODEL as it runs, at
+        every step of every member but the control (skyrim_amd/stochastic.py), by a random pattern that is correlated in
+        space (the spectrum of ``perturbation="spherical"``: ``length_scale_km``, ``alpha``, ``lmax``) and in time (decorrelation time
+        ``tau_h`` hours; 0: a fresh pattern every step).  ``kind="sppt"`` multiplies the step's tendency x_k - x_{k-1} by 1 + w, ONE
+        pattern w for all channels with standard deviation ``amplitude``, clipped to +-``clip`` (0.9); ``"additive"`` puts one field
+        per channel on the state, ``additive_scale`` (default ``perturb_scale``) times the channel's sigma; ``"both"`` does both.
+        ``channels`` restricts either term to some input channels.  Each lead time is then the model's own first step from the
+        perturbed state before it, so the members are held as states: the same models as ``breeding``, and not a Pangu loaded with
+        its 24-h network.  It combines with every ``perturbation`` and with ``breeding``; ``perturb_scale=0`` leaves the stochastic
+        terms as the only source of spread.  The defaults are the first scale of ECMWF's SPPT; whether they give a calibrated spread
+        with real weights is not measured (``verify --stochastic`` prints spread against skill).  The normalised request lands in
+        ``EnsembleForecast.stochastic``."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -190,6 +203,8 @@ class GlobalModel:
             extra["scenarios"] = scenarios
         if breeding is not None:
             extra["breeding"] = breeding
+        if stochastic is not None:
+            extra["stochastic"] = stochastic
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,

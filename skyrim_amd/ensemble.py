@@ -8,7 +8,8 @@ Three layers:
   ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), with ``breeding=`` bred from those seeds
   through the model itself (skyrim_amd/breeding.py), ONE TimeLoop
   generator per member advanced step-major (all members one step, then the statistics of that lead time), so only the members'
-  current states are alive on the GPU;
+  current states are alive on the GPU; with ``stochastic=`` the members are held as states instead and every step of every member
+  but the control is perturbed (SPPT, additive noise: skyrim_amd/stochastic.py);
 * ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
 
 Members sharded over ranks stay with ``skyrim_amd/pangu/ensemble.py``; multi-MODEL ensembles are ``core/models/ensemble.py``.
@@ -170,6 +171,7 @@ class EnsembleForecast:
     scenarios: object = None     # scenarios.Scenarios with ``scenarios={...}``
     breeding: object = None      # the normalised ``breeding=`` request (cycles, norm, paired) or None
     breeding_growth: object = None      # (cycles, member, channel) float64 with ``breeding=``: breeding.Breeder.growth
+    stochastic: object = None    # the normalised ``stochastic=`` request (stochastic.Plan.as_dict) or None
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -202,7 +204,7 @@ def _world_size() -> int:
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
              neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, breeding=None,
-             aggregates=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             stochastic=None, aggregates=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
@@ -212,7 +214,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     ``points`` / ``point_channels`` / ``point_method``: the places every member is sampled at (skyrim_amd/points.py), the raw channels and
     derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation.  ``scenarios``: the dict of
     skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only.  ``breeding``:
-    the dict of skyrim_amd/breeding.py (cycles, norm, paired); ``perturbation`` then names the seed."""
+    the dict of skyrim_amd/breeding.py (cycles, norm, paired); ``perturbation`` then names the seed.  ``stochastic``: the dict of
+    skyrim_amd/stochastic.py (kind, amplitude, clip, additive_scale, tau_h, length_scale_km, alpha, lmax, channels)."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -268,6 +271,9 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     if breeding is not None:                                # cycles, norm, keys; one history level, the same channels in and out
         from . import breeding as breed
         breed.plan(model, breeding)
+    if stochastic is not None:                              # kind, amplitudes, the pattern's spectrum and grid, a model that steps from one state
+        from . import stochastic as stoch
+        stoch.plan(model, stochastic)
     saved = list(range(0, n_steps + 1, save_every))
     if points is not None:                                  # the points, their channels, a bilinear point outside the source rows, the host limit
         from . import points as pointing
@@ -316,7 +322,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, breeding=None, aggregates=None, derived=None, grid=None,
+        point_method: str = "bilinear", scenarios=None, breeding=None, stochastic=None, aggregates=None, derived=None, grid=None,
         regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
@@ -327,14 +333,18 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
                                                   keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, scenarios,
-                                                  breeding, aggregates, derived, grid, regrid_method, perturbation, length_scale_km, alpha, lmax,
-                                                  perturb_channels)
+                                                  breeding, stochastic, aggregates, derived, grid, regrid_method, perturbation, length_scale_km,
+                                                  alpha, lmax, perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     bplan = None
     if breeding is not None:
         from . import breeding as breed
         bplan = breed.plan(model, breeding)
+    splan = None
+    if stochastic is not None:
+        from . import stochastic as stoch
+        splan = stoch.plan(model, stochastic, perturb_scale)
     M = int(n_members)
     names = list(model.out_channel_names)
     n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
@@ -451,14 +461,20 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         breeder.run(M)
         if hasattr(model, "__dict__"):
             model._resident_state = None
-    loops = []
+    loops, current, stepper = [], [], None
+    if splan is not None:                                  # per-step perturbations (skyrim_amd/stochastic.py): the members are held as states,
+        from .breeding import step_once                    # each lead is the model's own lead 1 from the perturbed state before it
+        stepper = stoch.Stepper(splan, dev, x0.shape[2:], sigma_all, M, int(seed), float(perturb_scale))
     for m in range(M):
         if breeder is not None:
             xm = breeder.member(m)
         else:
             xm = torch.empty_like(x0)
             seed_member(m, xm)
-        loops.append(model(start_time, xm))
+        if stepper is not None:
+            current.append(xm)
+        else:
+            loops.append(model(start_time, xm))
         del xm
     breeding_growth = None if breeder is None else breeder.growth
     del x0, spherical, breeder, sigma_all                  # (with them the work buffers of one member's synthesis and of the cycle)
@@ -515,6 +531,16 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 except FloatingPointError as e:
                     raise FloatingPointError(f"ensemble member {m}, step {k}: {e}") from e
                 states.append((out[0] if out.dim() == 4 else out).contiguous())
+            if stepper is not None:
+                time = start_time + k * model.time_step
+                for m in range(M):
+                    if k >= 1:
+                        xp = current[m]
+                        xn = step_once(model, time - model.time_step, xp, f"ensemble member {m}, step {k}")
+                        stepper.advance(k, m, xp[0, 0], xn)           # in place on xn; member 0 is left as the model made it
+                        current[m] = xn.reshape(xp.shape)
+                        del xp, xn
+                    states.append(current[m][0, 0])
             table = member_table(states)
             keep = k in saved
             want = {p: dev_out[p] for p in (products if keep else ())}
@@ -656,7 +682,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
 
     ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=plan.kind,
                            length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None,
-                           breeding=None if bplan is None else bplan.as_dict(), breeding_growth=breeding_growth)
+                           breeding=None if bplan is None else bplan.as_dict(), breeding_growth=breeding_growth,
+                           stochastic=None if splan is None else splan.as_dict())
     if scorer is not None:
         ens.scores = scorer.result()
         ens.scores.forecast_id = fid

@@ -25,6 +25,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
     gram / member_combine                                (member Gram matrices and linear combinations of M states, include/skyrim_gram.h)
     breed_norms / breed_apply                            (the two passes of a breeding cycle over M states, include/skyrim_breed.h)
+    stoch_coeffs / stoch_evolve / stoch_apply            (per-step stochastic perturbations: SPPT and additive, include/skyrim_stoch.h)
 """
 from __future__ import annotations
 
@@ -619,6 +620,25 @@ def _noise_apply(x0, y, g, out, chan_stride: int) -> None:
     noise.apply(x0, y, g, out, chan_stride)
 
 
+# ---- per-step stochastic perturbations ------------------------------------------------------------------------------------------ #
+def _stoch_coeffs(out, sigma, F: int, f_first: int, seed: int, member_first: int, draw: int) -> None:
+    """``noise_coeffs`` with the generator's fourth counter word 1 + ``draw``."""
+    from . import stochastic
+    stochastic.coeffs(out, sigma, F, f_first, seed, member_first, draw)
+
+
+def _stoch_evolve(p, sigma, F: int, f_first: int, seed: int, member_first: int, draw: int, phi: float, psi: float) -> None:
+    """``p``: the coefficient state, evolved in place; ``phi``, ``psi``: fp32 values."""
+    from . import stochastic
+    stochastic.evolve(p, sigma, F, f_first, seed, member_first, draw, phi, psi)
+
+
+def _stoch_apply(xp, xn, r, y, gs, ga, lim: float, out, chan_stride: int) -> None:
+    """``r`` with ``gs`` (and ``xp``), or ``y`` with ``ga``, may be None: that term is skipped.  ``out`` may be ``xn``."""
+    from . import stochastic
+    stochastic.apply(xp, xn, r, y, gs, ga, lim, out, chan_stride)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -683,6 +703,11 @@ _SCHEMAS = [
     ("breed_apply(Tensor x0, Tensor y0, Tensor[] members, Tensor table, Tensor f, Tensor(a!)[] out, Tensor out_table) -> ()", _breed_apply),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
     ("noise_apply(Tensor x0, Tensor y, Tensor g, Tensor(a!) out, int chan_stride) -> ()", _noise_apply),
+    ("stoch_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first, int draw) -> ()", _stoch_coeffs),
+    ("stoch_evolve(Tensor(a!) p, Tensor sigma, int F, int f_first, int seed, int member_first, int draw, float phi, float psi) -> ()",
+     _stoch_evolve),
+    ("stoch_apply(Tensor? xp, Tensor xn, Tensor? r, Tensor? y, Tensor? gs, Tensor? ga, float lim, Tensor(a!) out, int chan_stride) -> ()",
+     _stoch_apply),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 

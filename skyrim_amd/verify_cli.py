@@ -2,6 +2,7 @@
 the ensemble to score (``--members 1``, the default, is the deterministic forecast), an optional climatology file for the ACC, and the
 channels to print, and the kind of perturbation (``--perturbation spherical --length_scale_km --lmax``: this is where spread against skill is
 tuned; ``--breed_cycles 3 --breed_norm total --breed_paired`` breeds those perturbations through the model, skyrim_amd/breeding.py;
+``--stochastic sppt --stoch_amplitude --stoch_tau_h --stoch_length_scale_km`` perturbs every step of every member, skyrim_amd/stochastic.py;
 the ``ensemble`` command keeps white noise), and the grid to score on (``--grid 1.5deg --regrid_method conservative``: forecast and
 truth are regridded on the device, skyrim_amd/regrid.py; the default scores on the model's own grid), and the threshold events to verify
 (``--event ws10m:15,25 --neighbourhood_km 100``, both repeatable: skyrim_amd/events.py).  Scores every lead time against the truth of the chosen source (``Skyrim.verify`` /
@@ -22,7 +23,8 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
                filter_vars: str, members: int = 1, climatology: str | None = None, channels: str = "", perturb_scale: float = 1e-3,
                seed: int = 0, perturbation: str = "white", length_scale_km: float = 500.0, lmax: int | None = None,
                grid: str | None = None, regrid_method: str = "conservative", event=(), neighbourhood_km=(), breed_cycles: int = 0,
-               breed_norm: str = "total", breed_paired: bool = False):
+               breed_norm: str = "total", breed_paired: bool = False, stochastic: str | None = None, stoch_amplitude: float | None = None,
+               stoch_tau_h: float | None = None, stoch_length_scale_km: float | None = None):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
     from .core.models.base import adjust_lead_time
@@ -46,6 +48,11 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
     on_grid = {} if not grid else dict(grid=grid, regrid_method=regrid_method)
     on_grid.update(asked)
     bred = {} if not breed_cycles else dict(breeding=dict(cycles=breed_cycles, norm=breed_norm, paired=breed_paired))
+    if stochastic:                                         # --stochastic sppt|additive|both: per-step perturbations, skyrim_amd/stochastic.py
+        given = dict(amplitude=stoch_amplitude, tau_h=stoch_tau_h, length_scale_km=stoch_length_scale_km)
+        bred["stochastic"] = dict(kind=stochastic, **{k: v for k, v in given.items() if v is not None})
+    elif any(v is not None for v in (stoch_amplitude, stoch_tau_h, stoch_length_scale_km)):
+        raise ValueError("--stoch_amplitude, --stoch_tau_h and --stoch_length_scale_km shape the per-step perturbations: they need --stochastic")
     if members == 1:
         scores = model.verify(start_time, n_steps=n_steps, climatology=climatology, channels=scored, save=True, save_config=cfg, **on_grid)
     else:
@@ -112,6 +119,12 @@ def event_lines(scores) -> list[str]:
 @click.option("--breed_norm", type=click.Choice(["total", "channel"]), default="total",
               help="Rescaling of a bred vector: one factor per member, or every channel to its own amplitude")
 @click.option("--breed_paired", is_flag=True, help="Members 2j-1 and 2j are the two signs of one bred vector")
+@click.option("--stochastic", type=click.Choice(["sppt", "additive", "both"]), default=None,
+              help="Perturb every step of every member (members > 1): SPPT multiplies the step's tendency by 1 + a random pattern, additive "
+              "puts correlated noise on the state")
+@click.option("--stoch_amplitude", type=float, default=None, help="Standard deviation of the SPPT multiplier's pattern (default 0.3)")
+@click.option("--stoch_tau_h", type=float, default=None, help="Decorrelation time of the stochastic pattern in hours (default 6; 0 = white in time)")
+@click.option("--stoch_length_scale_km", type=float, default=None, help="Correlation length of the stochastic pattern in km (default 500)")
 @click.option("--grid", type=str, default=None, help="Score on this grid instead of the model's own: a resolution that divides 180 degrees, "
               "such as 1.5deg; forecast and truth are regridded on the device")
 @click.option("--regrid_method", type=click.Choice(["conservative", "bilinear", "nearest"]), default="conservative",
@@ -121,13 +134,13 @@ def event_lines(scores) -> list[str]:
 @click.option("--neighbourhood_km", type=float, multiple=True, help="Radius in km of a neighbourhood of the events' fractions skill score "
               "(repeatable, at most 4; 0 = point-wise)")
 def verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, modal, members, climatology, channels,
-           perturb_scale, seed, perturbation, length_scale_km, lmax, breed_cycles, breed_norm, breed_paired, grid, regrid_method, event,
-           neighbourhood_km):
+           perturb_scale, seed, perturbation, length_scale_km, lmax, breed_cycles, breed_norm, breed_paired, stochastic, stoch_amplitude,
+           stoch_tau_h, stoch_length_scale_km, grid, regrid_method, event, neighbourhood_km):
     if modal:
         raise click.UsageError("--modal runs the reference on a hosted A100 service; this build runs on the local MI355X")
     scores = run_verify(model_name, date, time, lead_time, list_models, initial_conditions, output_dir, filter_vars, members, climatology,
                         channels, perturb_scale, seed, perturbation, length_scale_km, lmax, grid, regrid_method, event, neighbourhood_km,
-                        breed_cycles, breed_norm, breed_paired)
+                        breed_cycles, breed_norm, breed_paired, stochastic, stoch_amplitude, stoch_tau_h, stoch_length_scale_km)
     if scores is None:
         return None
     for ln in lines(scores, [c for c in channels.split(",") if c]):
