@@ -119,7 +119,7 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          scenarios: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
+                          scenarios: dict | None = None, spectra: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
                           aggregates: List[str] | None = None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
@@ -186,7 +186,13 @@ class GlobalModel:
         its 24-h network.  It combines with every ``perturbation`` and with ``breeding``; ``perturb_scale=0`` leaves the stochastic
         terms as the only source of spread.  The defaults are the first scale of ECMWF's SPPT; whether they give a calibrated spread
         with real weights is not measured (``verify --stochastic`` prints spread against skill).  The normalised request lands in
-        ``EnsembleForecast.stochastic``."""
+        ``EnsembleForecast.stochastic``.
+        ``spectra={"channels": ["z500", "u850", "v850"], "bands": {"nh_mid": (30, 60), "tropics": (-20, 20)}}`` makes zonal power spectra
+        (skyrim_amd/spectra.py) at each saved lead time in ONE device pass: per channel, latitude band (default: nh_mid,
+        tropics, sh_mid, globe) and zonal wavenumber the power of the members, of their mean and of their spread and, with
+        ``scores=True``, of the truth and of the errors of the mean and of the members.  Raw channels and fields of ``derived`` on the model's own grid; the
+        number of longitudes must be 2^a 3^b 5^c.  The ``spectra.Spectra`` land in ``EnsembleForecast.spectra``.  ``spectra=None``
+        launches nothing."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -205,6 +211,8 @@ class GlobalModel:
             extra["breeding"] = breeding
         if stochastic is not None:
             extra["stochastic"] = stochastic
+        if spectra is not None:
+            extra["spectra"] = spectra
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -268,6 +276,17 @@ class GlobalModel:
         the method cannot serve is refused with ValueError before the device is touched."""
         from ... import regrid
         return regrid.regrid_model(self, start_time, n_steps, grid, method, channels, save=save, save_config=save_config)
+
+    def spectrum_forecast(self, start_time: datetime.datetime, n_steps: int = 4, spectra: dict | None = None, truth=None, save: bool = False,
+                          save_config: dict | None = None):
+        """Zonal power spectra of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/spectra.py).
+        ``spectra``: ``{"channels": [...], "bands": {name: (lat_s, lat_n) or None}}`` (default bands: nh_mid, tropics, sh_mid, globe).
+        The model's TimeLoop is advanced and every state is transformed where it lies in HBM: no state goes to the host.  ``truth`` (the
+        forms ``verify`` takes, but not None): also the spectra of the truth and of the error.  Returns a ``spectra.Spectra`` whose
+        ``power`` is (time, channel, band, kind, wavenumber); ``save=True`` writes ``{model}-spectra.json`` under the forecast id
+        directory.  A request that cannot be served is refused with ValueError before the device is touched."""
+        from ... import spectra as spec
+        return spec.spectrum_model(self, start_time, n_steps=n_steps, spectra=spectra, truth=truth, save=save, save_config=save_config)
 
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels: List[str] | None = None,
                save: bool = False, save_config: dict | None = None, grid=None, regrid_method: str = "conservative", events=None,

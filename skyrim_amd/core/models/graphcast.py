@@ -125,6 +125,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator verify advances: score "
                                   "its forecast with skyrim_amd.verify.score_prediction(forecast_or_saved_files, truth)")
 
+    def spectrum_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator spectrum_forecast advances: "
+                                  "make the spectra of its forecast with skyrim_amd.spectra.spectra_prediction(forecast_or_saved_files)")
+
     def track_cyclones(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator track_cyclones advances: "
                                   "track its forecast with skyrim_amd.tracks.track_prediction(forecast_or_saved_files)")

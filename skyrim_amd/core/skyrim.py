@@ -49,6 +49,18 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.verify(start_time, n_steps=n_steps, **kwargs)
 
+    def spectrum_forecast(self, start_time: datetime.datetime, n_steps: int = 4, **kwargs):
+        """Zonal power spectra of the single model's forecast at every lead time (``GlobalModel.spectrum_forecast`` has the arguments)
+        as a ``spectra.Spectra``.  ``ensemble_forecast(..., spectra={...})`` makes those of an ensemble."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.spectrum_forecast(start_time, n_steps=n_steps, **kwargs)
+
+    @staticmethod
+    def spectra_prediction(pred, truth=None, device="cuda:0", **kwargs):
+        """Zonal power spectra of a forecast that is already in memory or on disk (``spectra.spectra_prediction``)."""
+        from .. import spectra
+        return spectra.spectra_prediction(pred, truth=truth, device=device, **kwargs)
+
     @staticmethod
     def score_prediction(pred, truth, climatology=None, device="cuda:0", **kwargs):
         """Scores of a forecast that is already in memory or on disk (``verify.score_prediction``)."""

@@ -24,6 +24,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
     point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
     gram / member_combine                                (member Gram matrices and linear combinations of M states, include/skyrim_gram.h)
+    zonal_spectra                                        (zonal power spectra of M states, their mean, spread and errors, include/skyrim_spec.h)
     breed_norms / breed_apply                            (the two passes of a breeding cycle over M states, include/skyrim_breed.h)
     stoch_coeffs / stoch_evolve / stoch_apply            (per-step stochastic perturbations: SPPT and additive, include/skyrim_stoch.h)
 """
@@ -595,6 +596,17 @@ def _member_combine(members, table, channels, coef, b, out) -> None:
     scenarios.combine(list(members), table, list(channels), coef, b, out)
 
 
+# ---- zonal power spectra ------------------------------------------------------------------------------------------------------------------ #
+def _zonal_spectra(members, table, truth, channels, bands, lat_weight, out, workspace) -> None:
+    """``bands``: j0, j1 of every band, flattened; ``out``: float64 (len(channels), n_bands, 3 or 6, W // 2 + 1), 6 kinds with a truth;
+    ``workspace``: spectra.workspace_bytes(M, H, W, nc, bands, truth) bytes."""
+    from . import spectra
+    bands = list(bands)
+    if len(bands) % 2:
+        raise ValueError("zonal_spectra: bands holds j0, j1 of every band")
+    spectra.zonal(list(members), table, truth, list(channels), list(zip(bands[0::2], bands[1::2])), lat_weight, out, workspace)
+
+
 # ---- breeding cycles ---------------------------------------------------------------------------------------------------------------------- #
 def _breed_norms(y0, members, table, lat_weight, S, workspace) -> None:
     """``S``: float64 (M, C); ``workspace``: breeding.workspace_bytes(M, C, H, W) bytes."""
@@ -699,6 +711,8 @@ _SCHEMAS = [
     ("gram(Tensor[] members, Tensor table, Tensor? truth, int[] channels, int[] region, Tensor lat_weight, Tensor(a!) out, "
      "Tensor(b!) workspace) -> ()", _gram),
     ("member_combine(Tensor[] members, Tensor table, int[] channels, Tensor coef, Tensor b, Tensor(a!) out) -> ()", _member_combine),
+    ("zonal_spectra(Tensor[] members, Tensor table, Tensor? truth, int[] channels, int[] bands, Tensor lat_weight, Tensor(a!) out, "
+     "Tensor(b!) workspace) -> ()", _zonal_spectra),
     ("breed_norms(Tensor y0, Tensor[] members, Tensor table, Tensor lat_weight, Tensor(a!) S, Tensor(b!) workspace) -> ()", _breed_norms),
     ("breed_apply(Tensor x0, Tensor y0, Tensor[] members, Tensor table, Tensor f, Tensor(a!)[] out, Tensor out_table) -> ()", _breed_apply),
     ("noise_coeffs(Tensor(a!) out, Tensor sigma, int F, int f_first, int seed, int member_first) -> ()", _noise_coeffs),
