@@ -24,6 +24,8 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import native
+from .common import world_size as _world_size
+from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS = 64, 16                                   # include/skyrim_agg.h SKAGG_MAX_*
 MAX, MIN, SUM, COUNT_ABOVE = 1, 2, 3, 4                         # SKAGG_MAX ...
@@ -113,36 +115,18 @@ def describe(ops, M, C, H, W, D, member_stride, stamp=0.0, member_align=16) -> A
     return d
 
 
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def run(members, table, ops, acc, stamp) -> None:
     """One ``skagg_update``: fold the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors of one lead time; ``table`` =
     ``ensemble.member_table(members)``) into ``acc``, float32 (M, D, H, W), by the ops ``ops``; ``stamp``: the lead time in hours.
     Queued on torch's current stream.  As in ``derived.run``, the contents of ``table`` are trusted to be the addresses of ``members``."""
     import torch
-    M, ops = len(members), list(ops)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"agg_update: {M} members; 1 to {MAX_MEMBERS} are supported")
+    ops = list(ops)
+    member_count(members, "agg_update", MAX_MEMBERS)
     if not 1 <= len(ops) <= MAX_OPS:
         raise ValueError(f"agg_update: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("agg_update: states are (C, H, W)")
+    M, dev, align = member_set(members, table, "agg_update", MAX_MEMBERS)
     C, H, W = members[0].shape
-    dev = members[0].device
-    align = 16
-    for t in members:
-        if _check(t, "agg_update: member", torch.float32, dev) % 16:
-            align = 4
-        if t.shape != members[0].shape:
-            raise ValueError("agg_update: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("agg_update: table must be member_table(members)")
-    pa = _check(acc, "agg_update: acc", torch.float32, dev)
+    pa = native.tensor_ptr(acc, "agg_update: acc", torch.float32, dev)
     if acc.dim() != 4 or acc.shape[0] != M or tuple(acc.shape[2:]) != (H, W):
         raise ValueError(f"agg_update: acc must be ({M}, D, {H}, {W})")
     D = acc.shape[1]
@@ -333,11 +317,6 @@ def plan(names, requests, time_step, n_steps: int) -> Plan:
     if sum(len(g.ops) for g in groups) > MAX_OPS:
         raise ValueError(f"aggregates: {sum(len(g.ops) for g in groups)} ops for {[r.name for r in reqs]}; one call holds {MAX_OPS}")
     return Plan(names, reqs, groups, hidden0, dt, int(n_steps), incomplete)
-
-
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
 def check_request(names, requests, time_step, n_steps, lat, lon, n_members: int = 1) -> Plan:

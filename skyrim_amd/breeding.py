@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import native
+from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, TILE, MAX_GROUPS = 64, 256, 256, 256       # include/skyrim_breed.h SKBREED_*
 MAX_CYCLES = 50
@@ -77,26 +78,14 @@ def bound_k(C: int, H: int, W: int) -> int:
     return min(3 + 1 + (tiles + G - 1) // G + 63 + (G - 1) + 1, H * W + H + 2)
 
 
-def _check(t, what: str, dtype, dev):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def _states(y0, members, table, what: str):
-    M = len(members)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"{what}: {M} members; 1 to {MAX_MEMBERS} are supported")
+    member_count(members, what, MAX_MEMBERS)
     if y0.dim() != 3:
         raise ValueError(f"{what}: states are (C, H, W)")
-    dev = y0.device
-    _check(y0, f"{what}: the control", torch.float32, None)
-    for t in members:
-        _check(t, f"{what}: member", torch.float32, dev)
-        if t.shape != y0.shape:
-            raise ValueError(f"{what}: a member differs from the control in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError(f"{what}: table must be member_table(members)")
+    native.tensor_ptr(y0, f"{what}: the control", torch.float32, None)
+    M, dev, _ = member_set(members, table, what, MAX_MEMBERS, ndim=None, dev=y0.device)
+    if members[0].shape != y0.shape:
+        raise ValueError(f"{what}: a member differs from the control in shape")
     return M, dev, (ctypes.c_void_p * M)(*[t.data_ptr() for t in members])
 
 
@@ -110,10 +99,10 @@ def norms(y0, members, table, lat_weight, S, workspace) -> None:
         raise ValueError(f"breed_norms: {C} channels; 1 to {MAX_CHANNELS} are supported")
     d = NormsDesc()
     d.y0, d.members, d.members_host, d.M, d.C, d.H, d.W = y0.data_ptr(), table.data_ptr(), ctypes.addressof(host), M, C, H, W
-    d.lat_weight = _check(lat_weight, "breed_norms: lat_weight", torch.float64, dev)
+    d.lat_weight = native.tensor_ptr(lat_weight, "breed_norms: lat_weight", torch.float64, dev)
     if lat_weight.numel() != H:
         raise ValueError(f"breed_norms: {lat_weight.numel()} weights for {H} rows")
-    d.S = _check(S, "breed_norms: S", torch.float64, dev)
+    d.S = native.tensor_ptr(S, "breed_norms: S", torch.float64, dev)
     if tuple(S.shape) != (M, C):
         raise ValueError(f"breed_norms: S must be ({M}, {C})")
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous():
@@ -136,12 +125,12 @@ def apply(x0, y0, members, table, f, out, out_table) -> None:
         raise ValueError(f"breed_apply: {len(out)} outputs for {M} members")
     _, _, out_host = _states(y0, out, out_table, "breed_apply: out")
     d = ApplyDesc()
-    d.x0, d.y0 = _check(x0, "breed_apply: x0", torch.float32, dev), y0.data_ptr()
+    d.x0, d.y0 = native.tensor_ptr(x0, "breed_apply: x0", torch.float32, dev), y0.data_ptr()
     if x0.shape != y0.shape:
         raise ValueError("breed_apply: x0 differs from the control forecast in shape")
     d.members, d.members_host, d.out, d.out_host = table.data_ptr(), ctypes.addressof(host), out_table.data_ptr(), ctypes.addressof(out_host)
     d.M, d.C, d.H, d.W = M, C, H, W
-    d.f = _check(f, "breed_apply: f", torch.float32, dev)
+    d.f = native.tensor_ptr(f, "breed_apply: f", torch.float32, dev)
     if tuple(f.shape) != (M, C):
         raise ValueError(f"breed_apply: f must be ({M}, {C})")
     lib = load_library()

@@ -29,6 +29,29 @@ OUTPUT_DIR = str(Path.cwd() / "outputs")
 _B58 = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
 
 
+def world_size() -> int:
+    """The ranks of the process group, 1 without one."""
+    import torch.distributed as dist
+    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def iso(t) -> str:
+    """A time as ISO 8601 text: a ``datetime`` by its own ``isoformat``, a ``numpy.datetime64`` to the second."""
+    import numpy as np
+    return t.isoformat() if hasattr(t, "isoformat") else str(np.datetime_as_string(np.datetime64(t, "s")))
+
+
+def finish(result, save: bool, save_config):
+    """``result`` (a product with ``save(output_dir)``, ``forecast_id`` and ``path``), saved under the forecast id of ``save_config``
+    when ``save``; an id made here is written back into ``save_config``."""
+    cfg = save_config if save_config is not None else {}
+    if save:
+        cfg.setdefault("forecast_id", generate_forecast_id())
+        result.forecast_id = cfg["forecast_id"]
+        result.path = result.save(cfg.get("output_dir") or OUTPUT_DIR)
+    return result
+
+
 def _b58encode(b: bytes) -> str:
     n = int.from_bytes(b, "big")
     out = ""

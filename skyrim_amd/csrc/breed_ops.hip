@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_breed.h"
+#include "fields.h"
 
 #pragma clang fp contract(off)
 
@@ -36,32 +37,17 @@ struct ApplyArgs {
     uint32_t HW;
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W <= 2^30)
-__device__ __forceinline__ float load1(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-}
-__device__ __forceinline__ f32x4 load4(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL f32x4*)((const SK_GLOBAL char*)base + 4u * elem);
-}
-__device__ __forceinline__ void store1(float* base, uint32_t elem, float v) {
-    *(SK_GLOBAL float*)((SK_GLOBAL char*)base + 4u * elem) = v;
-}
-__device__ __forceinline__ void store4(float* base, uint32_t elem, f32x4 v) {
-    *(SK_GLOBAL f32x4*)((SK_GLOBAL char*)base + 4u * elem) = v;
-}
+using namespace skfields;
 
 // the lane's four points of a tile: elements e.x .. e.w of the state.  VEC: one 16-byte load at e.x (the four are consecutive)
 template <bool VEC>
 __device__ __forceinline__ f32x4 gather(const float* base, const uint32_t (&e)[4]) {
-    if (VEC) return load4(base, e[0]);
+    if (VEC) return load_vec<4>(base, e[0]);
     f32x4 v;
-    v.x = load1(base, e[0]);
-    v.y = load1(base, e[1]);
-    v.z = load1(base, e[2]);
-    v.w = load1(base, e[3]);
+    v.x = load_vec<1>(base, e[0]);
+    v.y = load_vec<1>(base, e[1]);
+    v.z = load_vec<1>(base, e[2]);
+    v.w = load_vec<1>(base, e[3]);
     return v;
 }
 
@@ -157,12 +143,12 @@ __global__ void __launch_bounds__(APPLY_LANES) apply_kernel(const ApplyArgs a, c
                 r.z = copy ? xa.z : xa.z + fm * (v[g].z - ya.z);
                 r.w = copy ? xa.w : xa.w + fm * (v[g].w - ya.w);
                 if (VEC) {
-                    if (live[0]) store4(o, e[0], r);
+                    if (live[0]) store_vec<4>(o, e[0], r);
                 } else {
-                    if (live[0]) store1(o, e[0], r.x);
-                    if (live[1]) store1(o, e[1], r.y);
-                    if (live[2]) store1(o, e[2], r.z);
-                    if (live[3]) store1(o, e[3], r.w);
+                    if (live[0]) store_vec<1>(o, e[0], r.x);
+                    if (live[1]) store_vec<1>(o, e[1], r.y);
+                    if (live[2]) store_vec<1>(o, e[2], r.z);
+                    if (live[3]) store_vec<1>(o, e[3], r.w);
                 }
             }
         }

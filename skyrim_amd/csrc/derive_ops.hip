@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_derive.h"
+#include "fields.h"
 
 #pragma clang fp contract(off)
 
@@ -30,42 +31,11 @@ struct DeriveArgs {
     Level lev[SKDERIVE_LEVELS_PER_LAUNCH];
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// VEC consecutive points of a lane; an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W, D H W <= 2^30)
-template <int VEC> struct Pts { float v[VEC]; };
-
-template <int VEC>
-__device__ __forceinline__ Pts<VEC> load(const float* base, uint32_t elem) {
-    Pts<VEC> r;
-    if constexpr (VEC == 4) {
-        const f32x4 t = *(const SK_GLOBAL f32x4*)((const SK_GLOBAL char*)base + 4u * elem);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-    }
-    return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void store(float* base, uint32_t elem, const Pts<VEC>& p) {
-    if constexpr (VEC == 4)
-        *(SK_GLOBAL f32x4*)((SK_GLOBAL char*)base + 4u * elem) = f32x4{p.v[0], p.v[1], p.v[2], p.v[3]};
-    else
-        *(SK_GLOBAL float*)((SK_GLOBAL char*)base + 4u * elem) = p.v[0];
-}
+using namespace skfields;
 
 __device__ __forceinline__ float speed(float u, float v) {
     const float uu = u * u, vv = v * v;
     return sqrtf(uu + vv);
-}
-
-__device__ __forceinline__ double wave_sum(double s) {          // a butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
 }
 
 // SPEED, DIFF, COLUMN: TILE points of the planes, a lane VEC of them per step

@@ -4,8 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_event.h"
+#include "fields.h"
 
 namespace {
+
+using namespace skfields;
 
 constexpr int MAXT = SKEVENT_MAX_THRESHOLDS, MAXM = SKEVENT_MAX_MEMBERS;
 constexpr int CHUNK = 8;                    // member loads in flight per lane (x V floats each)
@@ -23,23 +26,6 @@ struct ScaleArgs {
     int hy[SKEVENT_MAX_SCALES];
 };
 
-template <int V> struct Vec;
-template <> struct Vec<1> { typedef float type; };
-template <> struct Vec<4> { typedef float type __attribute__((ext_vector_type(4))); };
-
-// (csrc/score_ops.hip) a pointer read from the member table is a global one, and said to be: the load then takes the pointer from scalar
-// registers and the 32-bit lane offset as it is
-#define SK_GLOBAL __attribute__((address_space(1)))
-template <int V> __device__ __forceinline__ void load_vec(const float* base, uint32_t byte_off, float* x) {
-    typedef const SK_GLOBAL typename Vec<V>::type* vptr;
-    const typename Vec<V>::type v = *(vptr)((const SK_GLOBAL char*)base + byte_off);
-    if constexpr (V == 1) {
-        x[0] = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < V; ++e) x[e] = v[e];
-    }
-}
 
 __device__ __forceinline__ int lanes_with(bool p) { return __popcll(__ballot(p)); }      // wave-uniform
 
@@ -79,11 +65,11 @@ __global__ void __launch_bounds__(256) event_count_kernel(const CountArgs a, con
 #pragma unroll
                 for (int v = 0; v < V; ++v) k[t][v] = 0;
             float y[V];
-            load_vec<V>(truth, off, y);
+            load_to<V>(truth, off, y);
             for (int m0 = 0; m0 < M; m0 += CHUNK) {
                 float x[CHUNK][V];
 #pragma unroll
-                for (int u = 0; u < CHUNK; ++u) load_vec<V>(members[min(m0 + u, M - 1)], off, x[u]);
+                for (int u = 0; u < CHUNK; ++u) load_to<V>(members[min(m0 + u, M - 1)], off, x[u]);
 #pragma unroll
                 for (int u = 0; u < CHUNK; ++u) {
                     const bool on = m0 + u < M;
@@ -154,12 +140,6 @@ __device__ __forceinline__ int wave_scan(int v, int lane) {             // inclu
         if (lane >= d) v += n;
     }
     return v;
-}
-
-__device__ __forceinline__ long long wave_sum(long long s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
 }
 
 // One workgroup per (e, t, scale, output row).  Dynamic LDS: 16 int64 of reduction scratch, 8 int32 of scan scratch, then the two

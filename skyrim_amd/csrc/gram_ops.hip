@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_gram.h"
+#include "fields.h"
 
 #pragma clang fp contract(off)
 
@@ -42,13 +43,8 @@ struct CombineArgs {
     uint32_t plane[SKGRAM_MAX_CHANNELS];
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
+using namespace skfields;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W <= 2^30)
-__device__ __forceinline__ float load(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-}
 
 // acc += (double)c * w, entry by entry (a product and a sum, each rounded)
 __device__ __forceinline__ void fold(double (&acc)[16], const f32x16& c, double w) {
@@ -99,7 +95,7 @@ __global__ void __launch_bounds__(LANES) gram_kernel(const GramArgs a, const flo
         int col = a.i0 + q * TILE + pt;                                    // (i0 < W and q TILE + pt < ni <= W for a live lane)
         col = col >= a.W ? col - a.W : col;
         const uint32_t off = plane + (uint32_t)j * (uint32_t)a.W + (uint32_t)(live ? col : 0);
-        const float x0 = live ? load(x0p, off) : 0.f;
+        const float x0 = live ? load_vec<1>(x0p, off) : 0.f;
         lds[pt] = x0 - x0;                                                 // d_0: exactly 0, not finite when x_0 is not
         for (int m0 = 1; m0 < a.Mp; m0 += STAGE) {
             float v[STAGE];
@@ -107,7 +103,7 @@ __global__ void __launch_bounds__(LANES) gram_kernel(const GramArgs a, const flo
             for (int g = 0; g < STAGE; ++g) {                              // all loads of the group before the first use
                 const int m = min(m0 + g, a.Mp - 1);                       // (past the last column: that column again, not stored)
                 const float* x = m < a.M ? members[m] : truth;             // wave-uniform
-                v[g] = live ? load(x, off) : x0;
+                v[g] = live ? load_vec<1>(x, off) : x0;
             }
 #pragma unroll
             for (int g = 0; g < STAGE; ++g)
@@ -188,14 +184,14 @@ __global__ void __launch_bounds__(LANES) combine_kernel(const CombineArgs a, con
     const uint32_t p = blockIdx.x * LANES + threadIdx.x;
     if (p >= a.HW) return;                                                 // (no barrier below)
     const uint32_t off = a.plane[blockIdx.y] + p;                          // member and channel are uniform
-    const float x0 = load(members[0], off);
+    const float x0 = load_vec<1>(members[0], off);
     float acc[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = b[k] * x0;
     for (int m0 = 1; m0 < a.M; m0 += GROUP) {
         float v[GROUP];
 #pragma unroll
-        for (int g = 0; g < GROUP; ++g) v[g] = load(members[min(m0 + g, a.M - 1)], off);      // all loads of the group before the first use
+        for (int g = 0; g < GROUP; ++g) v[g] = load_vec<1>(members[min(m0 + g, a.M - 1)], off);      // all loads of the group before the first use
 #pragma unroll
         for (int g = 0; g < GROUP; ++g) {
             if (m0 + g < a.M) {

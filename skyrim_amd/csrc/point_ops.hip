@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdint>
 #include "../../include/skyrim_point.h"
+#include "fields.h"
 
 #pragma clang fp contract(off)
 
@@ -24,14 +25,8 @@ struct PointArgs {
     uint32_t plane[SKPOINT_MAX_CHANNELS];       // first element of the k-th listed channel's plane: channels[k] H W
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace skfields;
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W <= 2^30)
-__device__ __forceinline__ float load(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-}
 
 __global__ void __launch_bounds__(LANES) point_kernel(const PointArgs a, const float* const* __restrict__ members,
                                                        const skpoint_rec* __restrict__ records, float* __restrict__ out) {
@@ -60,10 +55,10 @@ __global__ void __launch_bounds__(LANES) point_kernel(const PointArgs a, const f
 #pragma unroll
         for (int g = 0; g < GROUP; ++g) {                                  // all loads of the group before the first use
             const uint32_t base = a.plane[min(k + g, k1 - 1)];             // (past the chunk's end: the last channel again, not stored)
-            x00[g] = load(x, base + o00);
-            x01[g] = load(x, base + o01);
-            x10[g] = load(x, base + o10);
-            x11[g] = load(x, base + o11);
+            x00[g] = load_vec<1>(x, base + o00);
+            x01[g] = load_vec<1>(x, base + o01);
+            x10[g] = load_vec<1>(x, base + o10);
+            x11[g] = load_vec<1>(x, base + o11);
         }
 #pragma unroll
         for (int g = 0; g < GROUP; ++g) {

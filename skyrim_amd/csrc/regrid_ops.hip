@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdint>
 #include "../../include/skyrim_regrid.h"
+#include "fields.h"
 
 #pragma clang fp contract(off)
 
@@ -21,25 +22,9 @@ struct RegridArgs {
     int32_t channels[SKREGRID_MAX_CHANNELS];
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace skfields;
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// VEC consecutive columns of a lane; an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W <= 2^30)
-template <int VEC> struct Pts { float v[VEC]; };
-
-template <int VEC>
-__device__ __forceinline__ Pts<VEC> load(const float* base, uint32_t elem) {
-    Pts<VEC> r;
-    if constexpr (VEC == 4) {
-        const f32x4 t = *(const SK_GLOBAL f32x4*)((const SK_GLOBAL char*)base + 4u * elem);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-        r.v[0] = *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-    }
-    return r;
-}
 
 template <int VEC>
 __device__ __forceinline__ void add_tap(Pts<VEC>& acc, float w, const Pts<VEC>& p) {

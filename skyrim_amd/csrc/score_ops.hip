@@ -4,8 +4,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_score.h"
+#include "fields.h"
 
 namespace {
+
+using namespace skfields;
 
 struct ScoreArgs {
     int M, H, W, c0, nc, flags;
@@ -24,31 +27,6 @@ struct ScorePtrs {
 // slots of a row partial
 enum { P_BIAS, P_MAE, P_MSE, P_VAR, P_ABS, P_PAIR, P_FA, P_FF, P_AA };
 static_assert(P_AA + 1 == SKSCORE_PARTIALS, "row partial layout");
-
-template <int V> struct Vec;
-template <> struct Vec<1> { typedef float type; };
-template <> struct Vec<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct Vec<4> { typedef float type __attribute__((ext_vector_type(4))); };
-
-// A pointer read from the member table is a generic pointer to the compiler (flat loads from 64-bit per-lane addresses); it is a global one,
-// and said to be: the load then takes the pointer from scalar registers and the 32-bit lane offset as it is.
-#define SK_GLOBAL __attribute__((address_space(1)))
-template <int V> __device__ __forceinline__ void load_vec(const float* base, uint32_t byte_off, float* x) {
-    typedef const SK_GLOBAL typename Vec<V>::type* vptr;
-    const typename Vec<V>::type v = *(vptr)((const SK_GLOBAL char*)base + byte_off);
-    if constexpr (V == 1) {
-        x[0] = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < V; ++e) x[e] = v[e];
-    }
-}
-
-__device__ __forceinline__ double wave_sum(double s) {          // a butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
 
 // MB: the member-count bucket (M <= MB; every loop over members is unrolled over MB with the member index a compile-time constant, so the
 // values stay in registers: a register array indexed at run time would live in scratch); V: consecutive points per lane; SORT: the pair
@@ -81,13 +59,13 @@ __global__ void __launch_bounds__(256) score_rows_kernel(const ScoreArgs a, cons
             for (uint32_t t = lane; t < items; t += 64) {
                 const uint32_t off = base + 4u * V * t;
                 float x[MB][V], y[V], c[V];
-                load_vec<V>(truth, off, y);
-                if (acc) load_vec<V>(clim, off, c);
-                load_vec<V>(members[0], off, x[0]);
+                load_to<V>(truth, off, y);
+                if (acc) load_to<V>(clim, off, c);
+                load_to<V>(members[0], off, x[0]);
 #pragma unroll
                 for (int m = 1; m < MB; ++m) {
                     if (m < M) {
-                        load_vec<V>(members[m], off, x[m]);
+                        load_to<V>(members[m], off, x[m]);
                     } else {
 #pragma unroll
                         for (int e = 0; e < V; ++e) x[m][e] = x[0][e];      // a member that is not there: no term below counts it

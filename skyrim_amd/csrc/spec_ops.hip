@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 #include "../../include/skyrim_spec.h"
+#include "fields.h"
 #include "spec_fft.h"
 
 #pragma clang fp contract(off)
@@ -31,12 +32,7 @@ struct BandArgs {
     int j0[SKSPEC_MAX_BANDS], j1[SKSPEC_MAX_BANDS], c0[SKSPEC_MAX_BANDS], c1[SKSPEC_MAX_BANDS];      // rows and chunks of a band
 };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-
-// an address is a wave-uniform pointer plus one 32-bit per-lane byte offset (C H W <= 2^30)
-__device__ __forceinline__ float load(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-}
+using namespace skfields;
 
 // all passes of one transform, planes (re0, im0) -> ... ; returns with the result in (re0, im0) when n_pass is even, else in (re1, im1)
 template <int NL>
@@ -101,10 +97,10 @@ __global__ void __launch_bounds__(NL) spec_kernel(const SpecArgs a, const float*
     for (int j = row0; j < row1; ++j) {
         const uint32_t base = plane + (uint32_t)j * (uint32_t)a.W;
         double f0r[NB], f0i[NB], dyr[NB], dyi[NB], sr[NB], si[NB], q[NB], am[NB], ae[NB];
-        const float first = load(x0p, base);
+        const float first = load_vec<1>(x0p, base);
         __syncthreads();                                                   // the last row's reads of the planes are done
         for (int i = tid; i < a.W; i += NL) {
-            const float v = load(x0p, base + i);
+            const float v = load_vec<1>(x0p, base + i);
             x0row[i] = v;
             re0[spec_pad(i)] = v - first;
             im0[spec_pad(i)] = 0.f;
@@ -122,7 +118,7 @@ __global__ void __launch_bounds__(NL) spec_kernel(const SpecArgs a, const float*
         if (truth) {
             __syncthreads();
             for (int i = tid; i < a.W; i += NL) {
-                re0[spec_pad(i)] = load(truth, base + i) - x0row[i];
+                re0[spec_pad(i)] = load_vec<1>(truth, base + i) - x0row[i];
                 im0[spec_pad(i)] = 0.f;
             }
             transform<NL>(a, re0, im0, re1, im1, tw);
@@ -144,7 +140,7 @@ __global__ void __launch_bounds__(NL) spec_kernel(const SpecArgs a, const float*
             const float* xb = members[two ? m + 1 : m];
             __syncthreads();
             for (int i = tid; i < a.W; i += NL) {
-                const float va = load(xa, base + i), vb = load(xb, base + i), v0 = x0row[i];
+                const float va = load_vec<1>(xa, base + i), vb = load_vec<1>(xb, base + i), v0 = x0row[i];
                 re0[spec_pad(i)] = va - v0;
                 im0[spec_pad(i)] = two ? vb - v0 : 0.f;
             }

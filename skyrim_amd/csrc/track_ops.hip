@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/skyrim_track.h"
+#include "fields.h"
 
 namespace {
 
@@ -19,34 +20,10 @@ struct TrackArgs {
 // the workspace: one counter (16 bytes reserved), then the survivors as (member, idx) pairs
 struct Survivor { int32_t member, idx; };
 
-#define SK_GLOBAL __attribute__((address_space(1)))
-// a member's address is its pointer (wave-uniform, scalar registers) plus one 32-bit per-lane byte offset (C H W <= 2^30)
-__device__ __forceinline__ float load_f(const float* base, uint32_t elem) {
-    return *(const SK_GLOBAL float*)((const SK_GLOBAL char*)base + 4u * elem);
-}
+using namespace skfields;
 
-__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double s) {          // a butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
-
-__device__ __forceinline__ int wave_sum(int s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    return s;
-}
+// a member's address is its pointer (wave-uniform, scalar registers) plus one 32-bit per-lane offset (C H W <= 2^30)
+__device__ __forceinline__ float load_f(const float* base, uint32_t elem) { return load_vec<1>(base, elem); }
 
 // (pa, ia) strictly below (pb, ib) in the lexicographic order; false when either value is a NaN
 __device__ __forceinline__ bool lex_below(float pa, int ia, float pb, int ib) { return pa < pb || (pa == pb && ia < ib); }

@@ -24,6 +24,8 @@ from pathlib import Path
 import numpy as np
 
 from . import native
+from .common import world_size as _world_size
+from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS, MAX_LEVELS = 64, 16, 16                   # include/skyrim_derive.h SKDERIVE_MAX_*
 SPEED, DIFF, COLUMN, VORTDIV = 1, 2, 3, 4                       # SKDERIVE_SPEED ...
@@ -114,13 +116,6 @@ def decode(ints, floats) -> list:
     return ops
 
 
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def describe(ops, M, C, H, W, D, member_stride, member_align=16, edges=(EDGE_POLE, EDGE_POLE)) -> DeriveDesc:
     """The descriptor of a program, its pointers still NULL."""
     d = DeriveDesc()
@@ -149,24 +144,13 @@ def run(members, table, ops, out, rowc=None, edges=(EDGE_POLE, EDGE_POLE)) -> No
     ``edges`` = (edge_first, edge_last), needed with a VORTDIV op (``row_table``).  Queued on torch's current stream.  As in
     ``verify.score``, the contents of ``table`` are trusted to be the addresses of ``members``."""
     import torch
-    M, ops = len(members), list(ops)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"derive_fields: {M} members; 1 to {MAX_MEMBERS} are supported")
+    ops = list(ops)
+    member_count(members, "derive_fields", MAX_MEMBERS)
     if not 1 <= len(ops) <= MAX_OPS:
         raise ValueError(f"derive_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("derive_fields: states are (C, H, W)")
+    M, dev, align = member_set(members, table, "derive_fields", MAX_MEMBERS)
     C, H, W = members[0].shape
-    dev = members[0].device
-    align = 16
-    for t in members:
-        if _check(t, "derive_fields: member", torch.float32, dev) % 16:
-            align = 4
-        if t.shape != members[0].shape:
-            raise ValueError("derive_fields: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("derive_fields: table must be member_table(members)")
-    po = _check(out, "derive_fields: out", torch.float32, dev)
+    po = native.tensor_ptr(out, "derive_fields: out", torch.float32, dev)
     if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
         raise ValueError(f"derive_fields: out must be ({M}, D, {H}, {W})")
     for op in ops:
@@ -181,7 +165,7 @@ def run(members, table, ops, out, rowc=None, edges=(EDGE_POLE, EDGE_POLE)) -> No
     if any(op.kind == VORTDIV for op in ops):
         if rowc is None or tuple(rowc.shape) != (H, 4):
             raise ValueError(f"derive_fields: vorticity and divergence need rowc ({H}, 4)")
-        d.rowc = _check(rowc, "derive_fields: rowc", torch.float32, dev)
+        d.rowc = native.tensor_ptr(rowc, "derive_fields: rowc", torch.float32, dev)
     lib = load_library()
     with torch.cuda.device(dev):
         native.check(lib.skderive_run(ctypes.byref(d), native.stream(dev)), "skderive_run", lib)
@@ -350,11 +334,6 @@ def plan(names, fields, lat, lon, levels=None) -> Plan:
     elif len(lat) < 3 or len(lon) < 4:
         raise ValueError("derived fields need a grid of at least 3 rows and 4 columns")
     return out
-
-
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
 def check_request(names, fields, lat, lon, n_members: int = 1, levels=None) -> Plan:

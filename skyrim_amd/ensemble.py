@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import native
+from .common import world_size as _world_size
+from .members import member_set, member_table          # noqa: F401 (member_table: this module's callers build the table with it)
 
 MAX_MEMBERS, MAX_THRESHOLDS, MAX_QUANTILES = 64, 4, 4          # include/skyrim_ens.h SKENS_MAX_*
 PRODUCTS = ("mean", "spread", "min", "max")
@@ -73,17 +75,12 @@ def quantile_position(level: float, M: int) -> tuple[int, float]:
     return k, f
 
 
-def _dev_f32(t, what: str, dev=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous float32 tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def perturb(x0: torch.Tensor, std: torch.Tensor, out: torch.Tensor, chan_stride: int, scale: float, seed: int, member_first: int) -> None:
     """``out`` (``k * x0.numel()`` elements: members ``member_first .. member_first + k - 1``, one after the other) from the flat
     (L, C, H, W) state ``x0`` and the C per-channel sigmas ``std``; ``chan_stride`` = H * W.  Queued on torch's current stream."""
     dev = x0.device
-    px, ps, po = _dev_f32(x0, "ens_perturb: x0"), _dev_f32(std, "ens_perturb: std", dev), _dev_f32(out, "ens_perturb: out", dev)
+    px = native.tensor_ptr(x0, "ens_perturb: x0", torch.float32)
+    ps, po = (native.tensor_ptr(t, f"ens_perturb: {w}", torch.float32, dev) for t, w in ((std, "std"), (out, "out")))
     n = x0.numel()
     if n == 0 or out.numel() % n or out.numel() == 0:
         raise ValueError(f"ens_perturb: out holds {out.numel()} elements, not a multiple of the state's {n}")
@@ -95,28 +92,14 @@ def perturb(x0: torch.Tensor, std: torch.Tensor, out: torch.Tensor, chan_stride:
                      "skens_perturb", lib)
 
 
-def member_table(members) -> torch.Tensor:
-    """The device array of member pointers ``stats`` reads (one small upload; keep it while the members keep their storage)."""
-    return torch.tensor([t.data_ptr() for t in members], dtype=torch.int64).to(members[0].device)
-
-
 def stats(members, table: torch.Tensor, offset: int, n: int, mean=None, spread=None, min=None, max=None, exceed=None, thresholds=(),
           quant=None, levels=()) -> None:
     """One pass over the flat range [offset, offset + n) of the M ``members`` (equal-sized contiguous float32 device tensors; ``table`` =
     ``member_table(members)``): the outputs that are not None are written at range-relative positions -- ``mean / spread / min / max``: n
     elements, ``exceed``: len(thresholds) x n, ``quant``: len(levels) x n.  Queued on torch's current stream."""
-    M = len(members)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"ens_stats: {M} members; 1 to {MAX_MEMBERS} are supported")
-    dev = members[0].device
-    align = 16
-    for t in members:
-        if _dev_f32(t, "ens_stats: member", dev) % 16:
-            align = 4
-        if t.numel() < offset + n:
-            raise ValueError(f"ens_stats: a member holds {t.numel()} elements, the range ends at {offset + n}")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("ens_stats: table must be member_table(members)")
+    M, dev, align = member_set(members, table, "ens_stats", MAX_MEMBERS, ndim=None, same="numel")
+    if members[0].numel() < offset + n:
+        raise ValueError(f"ens_stats: a member holds {members[0].numel()} elements, the range ends at {offset + n}")
     if offset < 0 or n < 0 or len(thresholds) > MAX_THRESHOLDS or len(levels) > MAX_QUANTILES:
         raise ValueError(f"ens_stats: at most {MAX_THRESHOLDS} thresholds and {MAX_QUANTILES} quantile levels, a non-negative range")
     if (exceed is None) != (len(thresholds) == 0) or (quant is None) != (len(levels) == 0):
@@ -126,7 +109,7 @@ def stats(members, table: torch.Tensor, offset: int, n: int, mean=None, spread=N
     for name, t, rows in (("mean", mean, 1), ("spread", spread, 1), ("min", min, 1), ("max", max, 1), ("exceed", exceed, len(thresholds)),
                           ("quant", quant, len(levels))):
         if t is not None:
-            if _dev_f32(t, f"ens_stats: {name}", dev) and t.numel() != rows * n:
+            if native.tensor_ptr(t, f"ens_stats: {name}", torch.float32, dev) and t.numel() != rows * n:
                 raise ValueError(f"ens_stats: {name} holds {t.numel()} elements, expected {rows * n}")
             setattr(d, name, t.data_ptr())
     d.n_thr, d.n_quant = len(thresholds), len(levels)
@@ -196,11 +179,6 @@ def scenario_std(model, names) -> np.ndarray:
         raise NotImplementedError(f"{type(model).__name__}: channel_std holds {std.size} values for {len(names)} output channels; "
                                   "normalise='std' needs one per output channel")
     return std
-
-
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,

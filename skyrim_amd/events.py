@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import native
+from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, MAX_THRESHOLDS, MAX_SCALES, MAX_WIDTH = 64, 16, 4, 4, 8192       # include/skyrim_event.h SKEVENT_MAX_*
 _P = ctypes.c_void_p
@@ -51,12 +52,6 @@ def load_library() -> ctypes.CDLL:
     return _lib
 
 
-def _dev(t, what: str, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def run(members, table: torch.Tensor, truth: torch.Tensor, channels, thresholds, counts: torch.Tensor, hy=(), hx=None, sums=None,
         workspace=None) -> None:
     """One ``skevent_run``: the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors; ``table`` =
@@ -66,25 +61,18 @@ def run(members, table: torch.Tensor, truth: torch.Tensor, channels, thresholds,
     uint8 of E * 4 * 2 * H * W bytes, which holds the k and o planes afterwards.  Queued on torch's current stream.
 
     As in ``verify.score`` the CONTENTS of ``table`` are trusted to be the addresses of ``members`` in order."""
-    M, E, S = len(members), len(channels), len(hy)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"event_counts: {M} members; 1 to {MAX_MEMBERS} are supported")
+    E, S = len(channels), len(hy)
+    member_count(members, "event_counts", MAX_MEMBERS)
     if truth.dim() != 3:
         raise ValueError("event_counts: states are (C, H, W)")
     C, H, W = truth.shape
-    dev = truth.device
     if E > MAX_CHANNELS or len(thresholds) != E or S > MAX_SCALES:
         raise ValueError(f"event_counts: at most {MAX_CHANNELS} event channels, one list of thresholds each, and {MAX_SCALES} scales")
     d = EventDesc()
-    align = 16
-    for t in members:
-        if _dev(t, "event_counts: member", torch.float32, dev) % 16:
-            align = 4
-        if t.numel() != truth.numel():
-            raise ValueError(f"event_counts: a member holds {t.numel()} elements, the truth {truth.numel()}")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("event_counts: table must be member_table(members)")
-    d.members, d.M, d.member_align, d.truth = table.data_ptr(), M, align, _dev(truth, "event_counts: truth", torch.float32, dev)
+    M, dev, align = member_set(members, table, "event_counts", MAX_MEMBERS, ndim=None, same="numel", dev=truth.device)
+    if members[0].numel() != truth.numel():
+        raise ValueError(f"event_counts: a member holds {members[0].numel()} elements, the truth {truth.numel()}")
+    d.members, d.M, d.member_align, d.truth = table.data_ptr(), M, align, native.tensor_ptr(truth, "event_counts: truth", torch.float32, dev)
     d.C, d.H, d.W, d.n_events, d.n_scales = C, H, W, E, S
     for e, (ch, thr) in enumerate(zip(channels, thresholds)):
         if not 0 <= int(ch) < C or not 1 <= len(thr) <= MAX_THRESHOLDS or any(math.isnan(float(v)) for v in thr):
@@ -92,7 +80,7 @@ def run(members, table: torch.Tensor, truth: torch.Tensor, channels, thresholds,
         d.channel[e], d.n_thr[e] = int(ch), len(thr)
         for k, v in enumerate(thr):
             d.thr[e][k] = float(v)
-    d.counts = _dev(counts, "event_counts: counts", torch.int32, dev)
+    d.counts = native.tensor_ptr(counts, "event_counts: counts", torch.int32, dev)
     if counts.numel() != E * MAX_THRESHOLDS * H * 2 * (M + 1):
         raise ValueError(f"event_counts: counts must hold E * {MAX_THRESHOLDS} * H * 2 * (M + 1) = {E * MAX_THRESHOLDS * H * 2 * (M + 1)} int32")
     lib = load_library()
@@ -101,12 +89,12 @@ def run(members, table: torch.Tensor, truth: torch.Tensor, channels, thresholds,
             if int(v) < 0:
                 raise ValueError("event_counts: a half-height is a number of rows >= 0")
             d.hy[s] = min(int(v), 2 ** 31 - 1)
-        d.hx = _dev(hx, "event_counts: hx", torch.int32, dev)
-        d.sums = _dev(sums, "event_counts: sums", torch.int64, dev)
+        d.hx = native.tensor_ptr(hx, "event_counts: hx", torch.int32, dev)
+        d.sums = native.tensor_ptr(sums, "event_counts: sums", torch.int64, dev)
         if hx.numel() != S * H or sums.numel() != E * MAX_THRESHOLDS * S * H * 3:
             raise ValueError(f"event_counts: hx must hold S * H int32 and sums E * {MAX_THRESHOLDS} * S * H * 3 int64")
         need = lib.skevent_workspace_bytes(E, H, W, S)
-        d.workspace, d.workspace_bytes = _dev(workspace, "event_counts: workspace", torch.uint8, dev), workspace.numel()
+        d.workspace, d.workspace_bytes = native.tensor_ptr(workspace, "event_counts: workspace", torch.uint8, dev), workspace.numel()
         if E and (need == 0 or d.workspace_bytes < need):
             raise ValueError(f"event_counts: the workspace holds {workspace.numel()} bytes, {need} are needed"
                              if need else f"event_counts: neighbourhoods need W <= {MAX_WIDTH}")

@@ -3,7 +3,8 @@
 Each binding module declares a ``Spec`` -- file stem, override variable, symbol prefix, ABI version, signature table -- and its
 ``load_library()`` calls ``load(SPEC)`` once: the path (the override variable names a variant build), the ctypes signatures and the ABI
 check live here.  ``check`` turns a non-zero return code into a RuntimeError, ``stream`` is torch's current stream as the ``void* stream`` of
-every launch, and ``HiLoWeight`` is the fp16 hi/lo upload of a constant matrix that SFNO, GraphCast and FourCastNet v1 share.
+every launch, ``tensor_ptr`` is the address of a tensor a launch may be handed (contiguous, of the dtype, on the device), and
+``HiLoWeight`` is the fp16 hi/lo upload of a constant matrix that SFNO, GraphCast and FourCastNet v1 share.
 """
 from __future__ import annotations
 
@@ -65,6 +66,13 @@ def check(code: int, what: str, lib: ctypes.CDLL | None = None) -> None:
 def stream(device: torch.device) -> ctypes.c_void_p:
     """torch's current stream on ``device`` as the ``void* stream`` argument of a launch."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def tensor_ptr(t, what: str, dtype, dev=None) -> int:
+    """``t.data_ptr()`` of a contiguous ``dtype`` tensor on the GPU (on ``dev`` when given); anything else is a ValueError named ``what``."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
+    return t.data_ptr()
 
 
 class HiLoWeight:

@@ -151,17 +151,11 @@ def plan(model, perturbation: str = "white", length_scale_km: float = 500.0, alp
 
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------------------------- #
-def _dev_f32(t, what: str, dev=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous float32 tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def coeffs(out: torch.Tensor, sigma: torch.Tensor, F: int, f_first: int, seed: int, member_first: int) -> None:
     """``out`` ([members][lmax][lmax][2][F] floats: members ``member_first ..``) from the device table ``sigma`` (lmax floats, sigma_l 2^e)
     for the fields ``f_first .. f_first + F - 1``.  Queued on torch's current stream."""
     dev = out.device
-    po, ps = _dev_f32(out, "noise_coeffs: out"), _dev_f32(sigma, "noise_coeffs: sigma", dev)
+    po, ps = native.tensor_ptr(out, "noise_coeffs: out", torch.float32), native.tensor_ptr(sigma, "noise_coeffs: sigma", torch.float32, dev)
     lmax = sigma.numel()
     per = lmax * lmax * 2 * F
     if F < 1 or lmax < 1 or out.numel() == 0 or out.numel() % per:
@@ -177,8 +171,8 @@ def coeffs(out: torch.Tensor, sigma: torch.Tensor, F: int, f_first: int, seed: i
 def apply(x0: torch.Tensor, y: torch.Tensor, g: torch.Tensor, out: torch.Tensor, chan_stride: int) -> None:
     """``out = fma(g[c], y, x0)`` over the flat (L, C, H, W) state; ``g``: C amplitudes, ``chan_stride`` = H * W."""
     dev = x0.device
-    px, py, pg, po = (_dev_f32(x0, "noise_apply: x0"), _dev_f32(y, "noise_apply: y", dev), _dev_f32(g, "noise_apply: g", dev),
-                      _dev_f32(out, "noise_apply: out", dev))
+    px = native.tensor_ptr(x0, "noise_apply: x0", torch.float32)
+    py, pg, po = (native.tensor_ptr(t, f"noise_apply: {w}", torch.float32, dev) for t, w in ((y, "y"), (g, "g"), (out, "out")))
     n = x0.numel()
     if n == 0 or y.numel() != n or out.numel() != n:
         raise ValueError(f"noise_apply: x0, y and out must hold the same {n} elements")

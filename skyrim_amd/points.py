@@ -26,6 +26,8 @@ from pathlib import Path
 import numpy as np
 
 from . import native
+from .common import world_size as _world_size
+from .members import fill_channels, member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, MAX_POINTS, CHUNK = 64, 256, 1 << 20, 8          # include/skyrim_point.h SKPOINT_MAX_*, SKPOINT_CHUNK
 METHODS = ("bilinear", "nearest")
@@ -71,18 +73,8 @@ def describe(M, C, H, W, channels, P, member_stride) -> PointDesc:
     """The descriptor of a call, its pointers still NULL."""
     d = PointDesc()
     d.M, d.C, d.H, d.W, d.P, d.member_stride = M, C, H, W, P, member_stride
-    channels = list(channels)
-    d.nc = len(channels)
-    for k, c in enumerate(channels[:MAX_CHANNELS]):
-        d.channels[k] = int(c)
+    fill_channels(d, channels, MAX_CHANNELS)
     return d
-
-
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
 
 
 def run(members, table, channels, records, out) -> None:
@@ -92,26 +84,17 @@ def run(members, table, channels, records, out) -> None:
     first nc P elements are written.  Queued on torch's current stream.  As in ``regrid.run``, the contents of ``table`` are trusted to be
     the addresses of ``members``; the kernel clamps what it reads from the records, so their contents cannot cause an access out of range."""
     import torch
-    M, channels = len(members), [int(c) for c in channels]
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"point_gather: {M} members; 1 to {MAX_MEMBERS} are supported")
+    channels = [int(c) for c in channels]
+    member_count(members, "point_gather", MAX_MEMBERS)
     if not 1 <= len(channels) <= MAX_CHANNELS:
         raise ValueError(f"point_gather: {len(channels)} channels; 1 to {MAX_CHANNELS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("point_gather: states are (C, H, W)")
+    M, dev, _ = member_set(members, table, "point_gather", MAX_MEMBERS)
     C, H, W = members[0].shape
-    dev = members[0].device
-    for t in members:
-        _check(t, "point_gather: member", torch.float32, dev)
-        if t.shape != members[0].shape:
-            raise ValueError("point_gather: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("point_gather: table must be member_table(members)")
-    pr = _check(records, "point_gather: records", torch.int32, dev)
+    pr = native.tensor_ptr(records, "point_gather: records", torch.int32, dev)
     if records.dim() != 2 or records.shape[1] != 8 or not 1 <= records.shape[0] <= MAX_POINTS:
         raise ValueError(f"point_gather: records are int32 (P, 8), the bytes of P skpoint_rec, 1 <= P <= {MAX_POINTS}")
     P, nc = int(records.shape[0]), len(channels)
-    po = _check(out, "point_gather: out", torch.float32, dev)
+    po = native.tensor_ptr(out, "point_gather: out", torch.float32, dev)
     if out.dim() == 3 and tuple(out.shape) == (M, nc, P):
         stride = nc * P
     elif out.dim() == 2 and out.shape[0] == M and out.shape[1] >= nc * P:
@@ -254,7 +237,6 @@ def host_limit(n_members: int, n_times: int, n_channels: int, n_points: int) -> 
 
 def check_request(names, lat, lon, n_members, points, channels=None, method="bilinear", n_times=1) -> tuple:
     """Every refusal that needs no device; returns (Points, channels, records)."""
-    from .ensemble import _world_size
     if _world_size() > 1:
         raise NotImplementedError("points are sampled on one GPU from members that all lie there; members sharded over the ranks of a "
                                   "process group are out of scope (DESIGN.md 25)")
@@ -612,7 +594,6 @@ def point_model(gm, start_time: datetime.datetime, n_steps: int, points, channel
     if derived is not None:
         from . import derived as deriving
         deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, 1)
-    from .ensemble import _world_size
     if _world_size() > 1:
         raise NotImplementedError("points are sampled on one GPU; a process group of more than one rank is out of scope (DESIGN.md 25)")
     lp = LeadPoints(names, model.grid.lat, model.grid.lon, 1, points, channels, method, model.device, list(derived or []), n_steps + 1)      # before the device

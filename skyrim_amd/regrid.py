@@ -22,6 +22,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import native
+from .common import world_size as _world_size
+from .members import fill_channels, member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, MAX_TAPS, MAX_W = 64, 256, 32, 8192          # include/skyrim_regrid.h SKREGRID_MAX_*
 METHODS = ("conservative", "bilinear", "nearest")
@@ -371,21 +373,11 @@ def grid_label(spec) -> str:
 
 
 # ---- the binding ------------------------------------------------------------------------------------------------------------------------- #
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def describe(M, C, H, W, Ho, Wo, channels, member_stride, member_align=16) -> RegridDesc:
     """The descriptor of a call, its pointers still NULL."""
     d = RegridDesc()
     d.M, d.member_align, d.C, d.H, d.W, d.Ho, d.Wo, d.member_stride = M, member_align, C, H, W, Ho, Wo, member_stride
-    channels = list(channels)
-    d.nc = len(channels)
-    for k, c in enumerate(channels[:MAX_CHANNELS]):
-        d.channels[k] = int(c)
+    fill_channels(d, channels, MAX_CHANNELS)
     return d
 
 
@@ -396,24 +388,13 @@ def run(members, table, channels, row_table, col_table, out) -> None:
     ``verify.score``, the contents of ``table`` are trusted to be the addresses of ``members``; the kernel clamps what it reads from the
     tables, so their contents cannot cause an access out of range."""
     import torch
-    M, channels = len(members), [int(c) for c in channels]
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"regrid: {M} members; 1 to {MAX_MEMBERS} are supported")
+    channels = [int(c) for c in channels]
+    member_count(members, "regrid", MAX_MEMBERS)
     if not 1 <= len(channels) <= MAX_CHANNELS:
         raise ValueError(f"regrid: {len(channels)} channels; 1 to {MAX_CHANNELS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("regrid: states are (C, H, W)")
+    M, dev, align = member_set(members, table, "regrid", MAX_MEMBERS)
     C, H, W = members[0].shape
-    dev = members[0].device
-    align = 16
-    for t in members:
-        if _check(t, "regrid: member", torch.float32, dev) % 16:
-            align = 4
-        if t.shape != members[0].shape:
-            raise ValueError("regrid: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("regrid: table must be member_table(members)")
-    po = _check(out, "regrid: out", torch.float32, dev)
+    po = native.tensor_ptr(out, "regrid: out", torch.float32, dev)
     if out.dim() != 4 or out.shape[0] != M or out.shape[1] != len(channels):
         raise ValueError(f"regrid: out must be ({M}, {len(channels)}, Ho, Wo)")
     Ho, Wo = int(out.shape[2]), int(out.shape[3])
@@ -423,19 +404,14 @@ def run(members, table, channels, row_table, col_table, out) -> None:
         start, count, weight = tab
         if start.numel() != n or count.numel() != n or tuple(weight.shape) != (n, MAX_TAPS):
             raise ValueError(f"regrid: the {what} table must hold {n} starts, {n} counts and ({n}, {MAX_TAPS}) weights")
-        dst.start, dst.count = _check(start, f"regrid: {what} start", torch.int32, dev), _check(count, f"regrid: {what} count", torch.int32, dev)
-        dst.weight = _check(weight, f"regrid: {what} weight", torch.float32, dev)
+        dst.start, dst.count = native.tensor_ptr(start, f"regrid: {what} start", torch.int32, dev), native.tensor_ptr(count, f"regrid: {what} count", torch.int32, dev)
+        dst.weight = native.tensor_ptr(weight, f"regrid: {what} weight", torch.float32, dev)
     lib = load_library()
     with torch.cuda.device(dev):
         native.check(lib.skregrid_run(ctypes.byref(d), native.stream(dev)), "skregrid_run", lib)
 
 
 # ---- the drivers ------------------------------------------------------------------------------------------------------------------------- #
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
 def check_request(names, lat, lon, n_members, grid, method="conservative", channels=None) -> Tables:
     """Every refusal that needs no device; returns the tables (``.lat`` / ``.lon``: the target grid)."""
     if _world_size() > 1:

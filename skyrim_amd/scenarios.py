@@ -22,6 +22,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import native
+from .members import fill_channels, member_set
 
 # include/skyrim_gram.h SKGRAM_*
 MAX_MEMBERS, MAX_CHANNELS, MAX_OUT, TILE, CHAIN, GROUPS = 64, 32, 8, 256, 64, 512
@@ -73,19 +74,12 @@ def workspace_bytes(Mp: int, nc: int, nj: int, ni: int) -> int:
     return int(load_library().skgram_workspace_bytes(int(Mp), int(nc), int(nj), int(ni)))
 
 
-def _channels(d, channels) -> None:
-    channels = [int(c) for c in channels]
-    d.nc = len(channels)
-    for k, c in enumerate(channels[:MAX_CHANNELS]):
-        d.channels[k] = c
-
-
 def describe(M, C, H, W, channels, region) -> GramDesc:
     """The descriptor of a ``skgram_run`` call without a truth, its pointers still NULL.  ``region``: (j0, nj, i0, ni)."""
     d = GramDesc()
     d.M, d.C, d.H, d.W, d.out_stride = M, C, H, W, M * M
     d.j0, d.nj, d.i0, d.ni = (int(v) for v in region)
-    _channels(d, channels)
+    fill_channels(d, channels, MAX_CHANNELS)
     return d
 
 
@@ -93,32 +87,8 @@ def describe_combine(M, C, H, W, channels, K) -> CombineDesc:
     """The descriptor of a ``skgram_combine`` call, its pointers still NULL."""
     d = CombineDesc()
     d.M, d.C, d.H, d.W, d.K = M, C, H, W, K
-    _channels(d, channels)
+    fill_channels(d, channels, MAX_CHANNELS)
     return d
-
-
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
-def _members(members, table, what: str, lo: int):
-    import torch
-    M = len(members)
-    if not lo <= M <= MAX_MEMBERS:
-        raise ValueError(f"{what}: {M} members; {lo} to {MAX_MEMBERS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError(f"{what}: states are (C, H, W)")
-    dev = members[0].device
-    for t in members:
-        _check(t, f"{what}: member", torch.float32, dev)
-        if t.shape != members[0].shape:
-            raise ValueError(f"{what}: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError(f"{what}: table must be member_table(members)")
-    return M, dev
 
 
 def gram(members, table, truth, channels, region, lat_weight, out, workspace) -> None:
@@ -127,7 +97,7 @@ def gram(members, table, truth, channels, region, lat_weight, out, workspace) ->
     ``region`` = (j0, nj, i0, ni) with the H float64 weights ``lat_weight``, into ``out``, float64 (nc, M', M'), or (nc, stride) with stride >= M'^2 of which each channel's first M'^2 elements are written.  ``workspace``: a float64
     (or uint8) device tensor of at least ``workspace_bytes(M', nc, nj, ni)`` bytes.  Queued on torch's current stream."""
     import torch
-    M, dev = _members(members, table, "gram", 2)
+    M, dev, _ = member_set(members, table, "gram", MAX_MEMBERS, lo=2)
     C, H, W = members[0].shape
     channels = [int(c) for c in channels]
     if not 1 <= len(channels) <= MAX_CHANNELS:
@@ -137,13 +107,13 @@ def gram(members, table, truth, channels, region, lat_weight, out, workspace) ->
         raise ValueError(f"gram: {M} members and a truth; the truth needs a column of the {MAX_MEMBERS}")
     d = describe(M, C, H, W, channels, region)
     if truth is not None:
-        d.truth = _check(truth, "gram: truth", torch.float32, dev)
+        d.truth = native.tensor_ptr(truth, "gram: truth", torch.float32, dev)
         if truth.shape != members[0].shape:
             raise ValueError("gram: the truth differs from the members in shape")
-    d.members, d.lat_weight = table.data_ptr(), _check(lat_weight, "gram: lat_weight", torch.float64, dev)
+    d.members, d.lat_weight = table.data_ptr(), native.tensor_ptr(lat_weight, "gram: lat_weight", torch.float64, dev)
     if lat_weight.numel() != H:
         raise ValueError(f"gram: {lat_weight.numel()} weights for {H} rows")
-    d.out = _check(out, "gram: out", torch.float64, dev)
+    d.out = native.tensor_ptr(out, "gram: out", torch.float64, dev)
     if out.dim() == 3 and tuple(out.shape) == (len(channels), Mp, Mp):
         d.out_stride = Mp * Mp
     elif out.dim() == 2 and out.shape[0] == len(channels) and out.shape[1] >= Mp * Mp:
@@ -162,12 +132,12 @@ def combine(members, table, channels, coef, b, out) -> None:
     """One ``skgram_combine``: ``out`` (K, nc, H, W) float32, out[k] = b[k] x_0 + sum_{m >= 1} coef[k, m] (x_m - x_0) in the header's
     fp32 operation order, for the channels ``channels``.  ``coef``: float32 (K, M), ``b``: float32 (K,), both on the device."""
     import torch
-    M, dev = _members(members, table, "member_combine", 2)
+    M, dev, _ = member_set(members, table, "member_combine", MAX_MEMBERS, lo=2)
     C, H, W = members[0].shape
     channels = [int(c) for c in channels]
     if not 1 <= len(channels) <= MAX_CHANNELS:
         raise ValueError(f"member_combine: {len(channels)} channels; 1 to {MAX_CHANNELS} are supported")
-    pc, pb, po = (_check(t, f"member_combine: {w}", torch.float32, dev) for t, w in ((coef, "coef"), (b, "b"), (out, "out")))
+    pc, pb, po = (native.tensor_ptr(t, f"member_combine: {w}", torch.float32, dev) for t, w in ((coef, "coef"), (b, "b"), (out, "out")))
     if coef.dim() != 2 or coef.shape[1] != M or not 1 <= coef.shape[0] <= MAX_OUT or tuple(b.shape) != (coef.shape[0],):
         raise ValueError(f"member_combine: coef is (K, {M}) with 1 <= K <= {MAX_OUT}, b is (K,)")
     K = int(coef.shape[0])

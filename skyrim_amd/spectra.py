@@ -28,6 +28,7 @@ from pathlib import Path
 import numpy as np
 
 from . import native
+from .members import fill_channels, member_set
 
 # include/skyrim_spec.h SKSPEC_*
 MAX_MEMBERS, MAX_CHANNELS, MAX_BANDS, MIN_W, MAX_W, MAX_H, CHUNK, SLOTS = 64, 32, 8, 2, 4096, 4096, 8, 6
@@ -111,10 +112,7 @@ def describe(M, C, H, W, channels, bands, truth: bool = False) -> SpecDesc:
     ``bands``: row ranges (j0, j1)."""
     d = SpecDesc()
     d.M, d.C, d.H, d.W = int(M), int(C), int(H), int(W)
-    channels = [int(c) for c in channels]
-    d.nc = len(channels)
-    for k, c in enumerate(channels[:MAX_CHANNELS]):
-        d.channels[k] = c
+    fill_channels(d, channels, MAX_CHANNELS)
     bands = [(int(a), int(b)) for a, b in bands]
     d.nb = len(bands)
     for k, (a, b) in enumerate(bands[:MAX_BANDS]):
@@ -134,13 +132,6 @@ def n_bins(W: int) -> int:
     return int(W) // 2 + 1
 
 
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def device_twiddles(W: int, dev):
     """The twiddle table of ``W`` on ``dev``, uploaded once."""
     import torch
@@ -157,18 +148,7 @@ def zonal(members, table, truth, channels, bands, lat_weight, out, workspace) ->
     (nc, nb, 3 or 6, W // 2 + 1).  ``workspace``: a device tensor of at least ``workspace_bytes(...)`` bytes.  Queued on torch's current
     stream."""
     import torch
-    M = len(members)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"zonal_spectra: {M} members; 1 to {MAX_MEMBERS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("zonal_spectra: states are (C, H, W)")
-    dev = members[0].device
-    for t in members:
-        _check(t, "zonal_spectra: member", torch.float32, dev)
-        if t.shape != members[0].shape:
-            raise ValueError("zonal_spectra: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("zonal_spectra: table must be member_table(members)")
+    M, dev, _ = member_set(members, table, "zonal_spectra", MAX_MEMBERS)
     C, H, W = members[0].shape
     channels = [int(c) for c in channels]
     bands = [(int(a), int(b)) for a, b in bands]
@@ -180,14 +160,14 @@ def zonal(members, table, truth, channels, bands, lat_weight, out, workspace) ->
         raise ValueError(f"zonal_spectra: W = {W}; the transform takes W = 2^a 3^b 5^c in [{MIN_W}, {MAX_W}]")
     d = describe(M, C, H, W, channels, bands)
     if truth is not None:
-        d.truth = _check(truth, "zonal_spectra: truth", torch.float32, dev)
+        d.truth = native.tensor_ptr(truth, "zonal_spectra: truth", torch.float32, dev)
         if truth.shape != members[0].shape:
             raise ValueError("zonal_spectra: the truth differs from the members in shape")
-    d.members, d.lat_weight = table.data_ptr(), _check(lat_weight, "zonal_spectra: lat_weight", torch.float64, dev)
+    d.members, d.lat_weight = table.data_ptr(), native.tensor_ptr(lat_weight, "zonal_spectra: lat_weight", torch.float64, dev)
     if lat_weight.numel() != H:
         raise ValueError(f"zonal_spectra: {lat_weight.numel()} weights for {H} rows")
     slots = SLOTS if truth is not None else 3
-    d.out = _check(out, "zonal_spectra: out", torch.float64, dev)
+    d.out = native.tensor_ptr(out, "zonal_spectra: out", torch.float64, dev)
     if tuple(out.shape) != (len(channels), len(bands), slots, n_bins(W)):
         raise ValueError(f"zonal_spectra: out must be ({len(channels)}, {len(bands)}, {slots}, {n_bins(W)})")
     if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or workspace.device != dev or not workspace.is_contiguous():

@@ -51,12 +51,9 @@ def load_library() -> ctypes.CDLL:
 
 
 # ---- the kernels ----------------------------------------------------------------------------------------------------------------------- #
-_dev_f32 = noise._dev_f32
-
-
 def _coeff_args(out, sigma, F, f_first, seed, member_first, draw, what):
     dev = out.device
-    po, ps = _dev_f32(out, f"{what}: out"), _dev_f32(sigma, f"{what}: sigma", dev)
+    po, ps = native.tensor_ptr(out, f"{what}: out", torch.float32), native.tensor_ptr(sigma, f"{what}: sigma", torch.float32, dev)
     lmax = sigma.numel()
     per = lmax * lmax * 2 * F
     if F < 1 or lmax < 1 or out.numel() == 0 or out.numel() % per:
@@ -95,17 +92,17 @@ def apply(xp, xn: torch.Tensor, r, y, gs, ga, lim: float, out: torch.Tensor, cha
     n = xn.numel()
     if (r is None) != (gs is None) or (y is None) != (ga is None) or (r is None and y is None):
         raise ValueError("stoch_apply: r goes with gs, y with ga, and one of the two terms must be given")
-    pn, po = _dev_f32(xn, "stoch_apply: xn"), _dev_f32(out, "stoch_apply: out", dev)
+    pn, po = native.tensor_ptr(xn, "stoch_apply: xn", torch.float32), native.tensor_ptr(out, "stoch_apply: out", torch.float32, dev)
     if n == 0 or out.numel() != n:
         raise ValueError(f"stoch_apply: xn and out must hold the same {n} elements")
     C = (gs if gs is not None else ga).numel()
     pp = pr = pgs = py = pga = None
     if r is not None:
-        pp, pr, pgs = _dev_f32(xp, "stoch_apply: xp", dev), _dev_f32(r, "stoch_apply: r", dev), _dev_f32(gs, "stoch_apply: gs", dev)
+        pp, pr, pgs = (native.tensor_ptr(t, f"stoch_apply: {w}", torch.float32, dev) for t, w in ((xp, "xp"), (r, "r"), (gs, "gs")))
         if xp.numel() != n or r.numel() != chan_stride:
             raise ValueError(f"stoch_apply: xp must hold the state's {n} elements and r one plane of {chan_stride}")
     if y is not None:
-        py, pga = _dev_f32(y, "stoch_apply: y", dev), _dev_f32(ga, "stoch_apply: ga", dev)
+        py, pga = native.tensor_ptr(y, "stoch_apply: y", torch.float32, dev), native.tensor_ptr(ga, "stoch_apply: ga", torch.float32, dev)
         if y.numel() != n or ga.numel() != C:
             raise ValueError(f"stoch_apply: y must hold the state's {n} elements and ga as many amplitudes as gs")
     if not 0.0 < lim <= 1.0:

@@ -24,6 +24,8 @@ from pathlib import Path
 import numpy as np
 
 from . import native
+from .common import finish as _finish, iso as _iso, world_size as _world_size
+from .members import member_set
 
 MAX_MEMBERS = 64                                                # include/skyrim_track.h SKTRACK_MAX_MEMBERS
 EARTH_RADIUS_KM = 6371.0
@@ -267,13 +269,6 @@ def workspace_bytes(M: int, Hb: int, W: int) -> int:
     return int(load_library().sktrack_workspace_bytes(M, Hb, W))
 
 
-def _check(t, what: str, dtype, dev):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def detect(members, table, channels, band, thresholds, h_msl, h_vort, h_wind, h_core, rowc, records, count, workspace) -> None:
     """One ``sktrack_detect``: the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors; ``table`` =
     ``ensemble.member_table(members)``).  ``channels``: the seven indices msl, u10, v10, u850, v850, z_up, z_lo (the last two -1: no warm
@@ -282,19 +277,8 @@ def detect(members, table, channels, band, thresholds, h_msl, h_vort, h_wind, h_
     ``count``: one int32; ``workspace``: uint8.  Queued on torch's current stream.  As in ``verify.score``, the contents of ``table``
     are trusted to be the addresses of ``members``."""
     import torch
-    M = len(members)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"track_detect: {M} members; 1 to {MAX_MEMBERS} are supported")
-    if members[0].dim() != 3:
-        raise ValueError("track_detect: states are (C, H, W)")
+    M, dev, _ = member_set(members, table, "track_detect", MAX_MEMBERS)
     C, H, W = members[0].shape
-    dev = members[0].device
-    for t in members:
-        _check(t, "track_detect: member", torch.float32, dev)
-        if t.shape != members[0].shape:
-            raise ValueError("track_detect: the members differ in shape")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("track_detect: table must be member_table(members)")
     channels, thresholds = [int(c) for c in channels], [float(t) for t in thresholds]
     if len(channels) != 7 or len(thresholds) != 4 or len(band) != 2:
         raise ValueError("track_detect: seven channel indices, a band (j0, j1) and four thresholds")
@@ -308,20 +292,20 @@ def detect(members, table, channels, band, thresholds, h_msl, h_vort, h_wind, h_
     for name, t in (("msl", h_msl), ("vort", h_vort), ("wind", h_wind), ("core", h_core)):
         if name == "core" and not core:
             continue
-        _check(t, f"track_detect: h_{name}", torch.int32, dev)
+        native.tensor_ptr(t, f"track_detect: h_{name}", torch.int32, dev)
         if t.dim() != 2 or t.shape[0] != j1 - j0 or t.shape[1] % 2 != 1:
             raise ValueError(f"track_detect: h_{name} must be (j1 - j0, 2 D + 1)")
         setattr(d, f"h_{name}", t.data_ptr())
         setattr(d, f"d_{name}", t.shape[1] // 2)
-    d.rowc = _check(rowc, "track_detect: rowc", torch.float32, dev)
+    d.rowc = native.tensor_ptr(rowc, "track_detect: rowc", torch.float32, dev)
     if tuple(rowc.shape) != (H, 4):
         raise ValueError(f"track_detect: rowc must be ({H}, 4)")
-    d.records = _check(records, "track_detect: records", torch.uint8, dev)
+    d.records = native.tensor_ptr(records, "track_detect: records", torch.uint8, dev)
     if records.numel() % RECORD.itemsize:
         raise ValueError(f"track_detect: the record buffer holds whole records of {RECORD.itemsize} bytes")
     d.capacity = records.numel() // RECORD.itemsize
-    d.count = _check(count, "track_detect: count", torch.int32, dev)
-    d.workspace, d.workspace_bytes = _check(workspace, "track_detect: workspace", torch.uint8, dev), workspace.numel()
+    d.count = native.tensor_ptr(count, "track_detect: count", torch.int32, dev)
+    d.workspace, d.workspace_bytes = native.tensor_ptr(workspace, "track_detect: workspace", torch.uint8, dev), workspace.numel()
     lib = load_library()
     need = lib.sktrack_workspace_bytes(M, j1 - j0, W)
     if need and d.workspace_bytes < need:
@@ -391,10 +375,6 @@ def link(times, candidates, max_speed_kmh: float = 90.0, min_points: int = 2) ->
 
 
 # ---- the result -------------------------------------------------------------------------------------------------------------------------- #
-def _iso(t) -> str:
-    return t.isoformat() if hasattr(t, "isoformat") else str(np.datetime_as_string(np.datetime64(t, "s")))
-
-
 class Tracks:
     """What tracking returns.  ``tracks``: a list of dicts {member, times, lat, lon, msl, wind, vort, core} (lists of equal length,
     longitudes in [0, 360)); ``criteria``: the criteria in effect (radii, thresholds, band, whether the warm core was applied and why
@@ -462,11 +442,6 @@ class Tracks:
 
 
 # ---- the drivers ------------------------------------------------------------------------------------------------------------------------- #
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
 def check_request(model_name: str, names, lat, lon, n_members: int, cfg) -> tuple:
     """Every refusal that needs no device; returns (config, channel plan, geometry)."""
     if _world_size() > 1:
@@ -539,16 +514,6 @@ class LeadTracker:
             for tr in link(self.times, [self.candidates(t, m) for t in range(len(self.times))], self.cfg.max_speed_kmh, self.cfg.min_points):
                 tracks.append(dict(member=m, **tr))
         return Tracks(self.model_name, self.M, self.times, self.geo.lat, self.geo.lon, tracks, self.criteria(), self.forecast_id)
-
-
-def _finish(tracks: Tracks, save: bool, save_config):
-    from .common import OUTPUT_DIR, generate_forecast_id
-    cfg = save_config if save_config is not None else {}
-    if save:
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        tracks.forecast_id = cfg["forecast_id"]
-        tracks.path = tracks.save(cfg.get("output_dir") or OUTPUT_DIR)
-    return tracks
 
 
 def track_model(gm, start_time: datetime.datetime, n_steps: int = 4, config=None, save: bool = False, save_config: dict | None = None) -> Tracks:

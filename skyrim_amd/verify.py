@@ -22,6 +22,8 @@ import numpy as np
 import torch
 
 from . import native
+from .common import finish as _finish, iso as _iso, world_size as _world_size
+from .members import member_count, member_set
 
 MAX_MEMBERS = 64                                                # include/skyrim_score.h SKSCORE_MAX_MEMBERS
 DET, VAR, CRPS, ACC, RANK = 1, 2, 4, 8, 16                      # SKSCORE_DET ...
@@ -58,12 +60,6 @@ def load_library() -> ctypes.CDLL:
     return _lib
 
 
-def _dev(t, what: str, dtype, dev=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or not t.is_cuda or (dev is not None and t.device != dev):
-        raise ValueError(f"{what}: expected a contiguous {str(dtype).split('.')[-1]} tensor on {dev or 'the GPU'}")
-    return t.data_ptr()
-
-
 def score(members, table: torch.Tensor, truth: torch.Tensor, weights: torch.Tensor, out, workspace: torch.Tensor, flags: int,
           clim=None, counts=None, c0: int = 0, nc: int | None = None) -> None:
     """One ``skscore_run``: the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors; ``table`` =
@@ -73,45 +69,37 @@ def score(members, table: torch.Tensor, truth: torch.Tensor, weights: torch.Tens
 
     The members themselves are checked here; the CONTENTS of ``table`` (device memory) are not read back and are trusted to be the
     addresses of ``members`` in order, as in ``ensemble.stats``: build it with ``member_table`` from the same list."""
-    M = len(members)
-    if not 1 <= M <= MAX_MEMBERS:
-        raise ValueError(f"score_fields: {M} members; 1 to {MAX_MEMBERS} are supported")
+    member_count(members, "score_fields", MAX_MEMBERS)
     if truth.dim() != 3:
         raise ValueError("score_fields: states are (C, H, W)")
     C, H, W = truth.shape
     nc = C - c0 if nc is None else nc
-    dev = truth.device
     d = ScoreDesc()
-    align = 16
-    for t in members:
-        if _dev(t, "score_fields: member", torch.float32, dev) % 16:
-            align = 4
-        if t.numel() != truth.numel():
-            raise ValueError(f"score_fields: a member holds {t.numel()} elements, the truth {truth.numel()}")
-    if table.dtype != torch.int64 or table.device != dev or table.numel() != M or not table.is_contiguous():
-        raise ValueError("score_fields: table must be member_table(members)")
+    M, dev, align = member_set(members, table, "score_fields", MAX_MEMBERS, ndim=None, same="numel", dev=truth.device)
+    if members[0].numel() != truth.numel():
+        raise ValueError(f"score_fields: a member holds {members[0].numel()} elements, the truth {truth.numel()}")
     if not (0 <= c0 and 0 <= nc and c0 + nc <= C) or flags <= 0 or flags & ~31:
         raise ValueError("score_fields: a channel range inside the states and at least one group of outputs")
-    d.members, d.M, d.member_align, d.truth = table.data_ptr(), M, align, _dev(truth, "score_fields: truth", torch.float32, dev)
+    d.members, d.M, d.member_align, d.truth = table.data_ptr(), M, align, native.tensor_ptr(truth, "score_fields: truth", torch.float32, dev)
     d.C, d.H, d.W, d.c0, d.nc, d.flags = C, H, W, c0, nc, flags
-    d.lat_weight = _dev(weights, "score_fields: weights", torch.float64, dev)
+    d.lat_weight = native.tensor_ptr(weights, "score_fields: weights", torch.float64, dev)
     if weights.numel() != H:
         raise ValueError(f"score_fields: {weights.numel()} latitude weights for {H} rows")
     if flags & ACC:
         if clim is None or clim.shape != truth.shape:
             raise ValueError("score_fields: the ACC sums need a climatology of the truth's shape")
-        d.clim = _dev(clim, "score_fields: clim", torch.float32, dev)
+        d.clim = native.tensor_ptr(clim, "score_fields: clim", torch.float32, dev)
     if flags & RANK:
-        d.counts = _dev(counts, "score_fields: counts", torch.int32, dev)
+        d.counts = native.tensor_ptr(counts, "score_fields: counts", torch.int32, dev)
         if counts.numel() != nc * H * (M + 1):
             raise ValueError(f"score_fields: counts must hold nc * H * (M + 1) = {nc * H * (M + 1)} int32")
     if flags & ~RANK:
-        d.out = _dev(out, "score_fields: out", torch.float64, dev)
+        d.out = native.tensor_ptr(out, "score_fields: out", torch.float64, dev)
         if out.numel() != nc * len(SLOTS):
             raise ValueError(f"score_fields: out must hold nc * {len(SLOTS)} float64")
     lib = load_library()
     need = lib.skscore_workspace_bytes(C, H, M, flags)
-    d.workspace, d.workspace_bytes = _dev(workspace, "score_fields: workspace", torch.float64, dev), workspace.numel() * 8
+    d.workspace, d.workspace_bytes = native.tensor_ptr(workspace, "score_fields: workspace", torch.float64, dev), workspace.numel() * 8
     if d.workspace_bytes < need:
         raise ValueError(f"score_fields: the workspace holds {workspace.numel() * 8} bytes, {need} are needed")
     with torch.cuda.device(dev):
@@ -141,10 +129,6 @@ def cell_bounds(lat, what: str = "cell_bounds") -> np.ndarray:
         raise ValueError(f"{what}: the latitude axis must be strictly monotonic")
     mid = (lat[:-1] + lat[1:]) / 2
     return np.clip(np.concatenate([[lat[0] - step[0] / 2], mid, [lat[-1] + step[-1] / 2]]), -90.0, 90.0)
-
-
-def _iso(t) -> str:
-    return t.isoformat() if hasattr(t, "isoformat") else str(np.datetime_as_string(np.datetime64(t, "s")))
 
 
 class Scores:
@@ -299,11 +283,6 @@ def default_truth(gm):
                            state_fn=getattr(gm.model, "synthetic_state", None))
 
 
-def _world_size() -> int:
-    import torch.distributed as dist
-    return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-
-
 def check_request(n_members: int, out_names, channels=None) -> None:
     """The refusals that need no device."""
     if _world_size() > 1:
@@ -422,16 +401,6 @@ class LeadScorer:
         if self.events is not None:
             scores.events = self.events.result(self.times, self.weights_host)
         return scores
-
-
-def _finish(scores: Scores, save: bool, save_config):
-    from .common import OUTPUT_DIR, generate_forecast_id
-    cfg = save_config if save_config is not None else {}
-    if save:
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        scores.forecast_id = cfg["forecast_id"]
-        scores.path = scores.save(cfg.get("output_dir") or OUTPUT_DIR)
-    return scores
 
 
 def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None, climatology=None, channels=None, save: bool = False,

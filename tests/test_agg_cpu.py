@@ -28,12 +28,8 @@ H6 = datetime.timedelta(hours=6)
 def test_library_exports_every_declared_symbol():
     text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
     syms = sorted(set(re.findall(r"\b(skagg_[a-z0-9_]+)\s*\(", text)))
-    lib = A.load_library()
-    assert syms == sorted(A.EXPORTS) and len(syms) == 2
-    for s in syms:
-        assert hasattr(lib, s), f"{s} declared in skyrim_agg.h but not exported"
-    assert lib.skagg_abi_version() == A.ABI_VERSION == int(re.search(r"SKAGG_ABI_VERSION (\d+)", text).group(1))
-    assert A.SPEC.env == "SKYRIM_AGG_LIB" and A.SPEC.stem == "skyrim_agg" and A.SPEC.prefix == "skagg"
+    assert len(syms) == 2                                        # (that they are EXPORTS, exported, and the ABI version: tests/test_native.py)
+    assert A.SPEC.stem == "skyrim_agg" and A.SPEC.prefix == "skagg"
     for name, val in (("MAX_MEMBERS", A.MAX_MEMBERS), ("MAX_OPS", A.MAX_OPS), ("MAX", A.MAX), ("MIN", A.MIN), ("SUM", A.SUM),
                       ("COUNT_ABOVE", A.COUNT_ABOVE), ("FIRST", A.FIRST), ("LAST", A.LAST), ("E_ARG", -1), ("E_HIP", -2)):
         assert int(re.search(rf"SKAGG_{name} \(?(-?\d+)\)?", text).group(1)) == val, name
@@ -41,18 +37,6 @@ def test_library_exports_every_declared_symbol():
     for doc in (native.__doc__, (ROOT / "skyrim_amd/csrc/Makefile").read_text().splitlines()[0]):
         assert "regrid,agg,event}" in doc
     assert "-ffp-contract=off -shared -o $@ agg_ops.hip" in (ROOT / "skyrim_amd/csrc/Makefile").read_text()
-
-
-def test_missing_or_other_abi_library_is_refused(monkeypatch, tmp_path):
-    monkeypatch.setattr(A, "_lib", None)
-    monkeypatch.setenv("SKYRIM_AGG_LIB", str(tmp_path / "nope.so"))
-    with pytest.raises(RuntimeError, match="not found"):
-        A.load_library()
-    monkeypatch.delenv("SKYRIM_AGG_LIB")
-    with pytest.raises(RuntimeError, match="ABI"):
-        native.load(native.Spec(A.SPEC.stem, A.SPEC.env, A.SPEC.prefix, A.SPEC.abi + 1, A.SPEC.symbols))
-    monkeypatch.setattr(A, "_lib", None)
-    assert A.load_library().skagg_abi_version() == A.ABI_VERSION
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not installed")

@@ -1,19 +1,25 @@
-"""The binding policy of the five C-ABI libraries (skyrim_amd/native.py), without a GPU: each header's declared entry points are the
-binding's EXPORTS and are exported by the built library, the library reports the header's ABI version, and a missing file or another
-ABI version is refused at load."""
+"""The binding policy of the twenty-one C-ABI libraries, engines and products alike (skyrim_amd/native.py), without a GPU: each header's
+declared entry points are the binding's EXPORTS and are exported by the built library, the library reports the header's ABI version,
+and a missing file or another ABI version is refused at load."""
 import re
 from pathlib import Path
 
 import pytest
 
-from skyrim_amd import deliver, native
+from skyrim_amd import (aggregate, breeding, deliver, derived, ensemble, events, native, noise, points, regrid, scenarios, spectra, stochastic,
+                        tracks, verify)
+from skyrim_amd.dlwp import engine as dlwp
 from skyrim_amd.fcn import engine as fcn
+from skyrim_amd.fengwu import engine as fengwu
+from skyrim_amd.fuxi import engine as fuxi
 from skyrim_amd.graphcast import engine as graphcast
 from skyrim_amd.pangu import engine as pangu
 from skyrim_amd.sfno import engine as sfno
 
 INCLUDE = Path(__file__).resolve().parent.parent / "include"
-BINDINGS = {"pangu": pangu, "sfno": sfno, "graphcast": graphcast, "fcn": fcn, "io": deliver}
+BINDINGS = {"pangu": pangu, "sfno": sfno, "graphcast": graphcast, "fcn": fcn, "dlwp": dlwp, "fuxi": fuxi, "fengwu": fengwu, "io": deliver,
+            "ens": ensemble, "score": verify, "noise": noise, "track": tracks, "derive": derived, "regrid": regrid, "event": events,
+            "agg": aggregate, "point": points, "gram": scenarios, "breed": breeding, "stoch": stochastic, "spec": spectra}
 
 
 @pytest.fixture(params=list(BINDINGS))
