@@ -17,7 +17,6 @@ from __future__ import annotations
 import ctypes
 import datetime
 import math
-import os
 import re
 from dataclasses import dataclass, field, replace
 
@@ -25,6 +24,7 @@ import numpy as np
 
 from . import native
 from .common import world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS = 64, 16                                   # include/skyrim_agg.h SKAGG_MAX_*
@@ -503,9 +503,9 @@ def _labelled(arr, fields, ends, starts, lat, lon):
     return DataArray(arr, ["time", "channel", "lat", "lon"], dict(time=ends, channel=list(fields), lat=lat, lon=lon, window_start=starts))
 
 
-def _fold_sequence(names, lat, lon, requests, t0, time_step, n_steps, device, states_of, derived=None):
-    """The aggregates of ONE forecast (M = 1): ``states_of(k)`` delivers the (C, H, W) device state of step k = 0 .. n_steps.  Returns
-    {label: DataArray(time = window ends, channel, lat, lon)} and the dict of incomplete windows."""
+def _fold_sequence(names, lat, lon, requests, t0, time_step, n_steps, device, drive, derived=None):
+    """The aggregates of ONE forecast (M = 1): ``drive(each)`` calls ``each(k, time, state)`` with the (C, H, W) device state of step
+    k = 0 .. n_steps.  Returns {label: DataArray(time = window ends, channel, lat, lon)}, each with the dict of incomplete windows."""
     dnames = list(derived or [])
     agg = LeadAggregator(names, lat, lon, 1, requests, t0, time_step, device=device, n_steps=n_steps, derived=dnames)
     deriver = None
@@ -513,28 +513,28 @@ def _fold_sequence(names, lat, lon, requests, t0, time_step, n_steps, device, st
         from .derived import LeadDeriver
         deriver = LeadDeriver(names, lat, lon, 1, dnames, device=device)
     host = {g.label: ([], [], []) for g in agg.plan.groups}
-    for k in range(n_steps + 1):
-        state = states_of(k)
+
+    def each(k, time, state):
         if k == 0:
-            continue                                           # the initial state belongs to no window
+            return                                             # the initial state belongs to no window
         for c in agg.add(k, t0 + k * agg.step, [state], None, deriver.add([state]) if deriver is not None else None):
             arrs, ends, starts = host[c.label]
             arrs.append(c.states[0].cpu().numpy())
             ends.append(c.end)
             starts.append(c.start)
-        del state
+    drive(each)
     lat, lon = np.asarray(lat), np.asarray(lon)
-    return {g.label: _labelled(np.stack(host[g.label][0]), g.fields, host[g.label][1], host[g.label][2], lat, lon)
-            for g in agg.plan.groups}, dict(agg.incomplete)
+    out = {g.label: _labelled(np.stack(host[g.label][0]), g.fields, host[g.label][1], host[g.label][2], lat, lon) for g in agg.plan.groups}
+    incomplete = dict(agg.incomplete)
+    for da in out.values():
+        da.incomplete = incomplete
+    return out
 
 
 def _save(out: dict, model_name: str, source: str, save_config):
-    from .common import generate_forecast_id, save_forecast
+    from .common import save_config_with_id, save_forecast
     from .labeled import DataArray
-    cfg = dict(save_config or {})
-    cfg.setdefault("forecast_id", generate_forecast_id())
-    if save_config is not None:
-        save_config["forecast_id"] = cfg["forecast_id"]
+    cfg = save_config_with_id(save_config)
     zarr = (cfg.get("file_type") or "netcdf") == "zarr"
     for label, da in out.items():
         times = list(da.time.values.astype("datetime64[s]").astype(datetime.datetime))
@@ -555,28 +555,9 @@ def aggregate_model(gm, start_time: datetime.datetime, n_steps: int, aggregates,
         from . import derived as deriving
         deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, 1)
     check_request(names + list(derived or []), aggregates, model.time_step, n_steps, model.grid.lat, model.grid.lon, 1)      # before the device
-    import torch
-    from .datasource import get_initial_condition_for_model
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("aggregate_forecast aggregates with HIP kernels where the forecast lies: the model must be on a GPU")
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
-
-    def states_of(k):
-        _, out, _ = next(loop)
-        return (out[0] if out.dim() == 4 else out).contiguous()
-    try:
-        out, incomplete = _fold_sequence(names, model.grid.lat, model.grid.lon, aggregates, start_time, model.time_step, n_steps, model.device,
-                                         states_of, derived)
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
-    for da in out.values():
-        da.incomplete = incomplete
+    require_gpu(model.device, "aggregate_forecast aggregates with HIP kernels where the forecast lies: the model must be on a GPU")
+    out = _fold_sequence(names, model.grid.lat, model.grid.lon, aggregates, start_time, model.time_step, n_steps, model.device,
+                         lambda each: run_model(gm, start_time, n_steps, each), derived)
     if save:
         _save(out, gm.model_name, gm.source_label, save_config)
     return out
@@ -587,29 +568,8 @@ def aggregate_prediction(pred, aggregates, derived=None, device="cuda:0"):
     zarr store, or a list of such files (their time entries in order, duplicates of a valid time used once).  The first time entry is the
     initial state; the entries must be equally spaced.  Each entry is uploaded on its own and goes through the same kernel as
     ``aggregate_forecast``.  Returns {window label: DataArray(time = window ends, channel = aggregates, lat, lon)}."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("aggregate_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    seen, entries = set(), []
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("aggregate_prediction: the files of one forecast must share channels and grid")
-        for k, t in enumerate(np.asarray(da._coords["time"]).astype("datetime64[s]")):
-            if t not in seen:
-                seen.add(t)
-                entries.append((t.astype(datetime.datetime), da, k))
+    saved = open_saved(pred, "aggregate_prediction")
+    names, lat, lon, entries = saved.names, saved.lat, saved.lon, saved.entries
     if len(entries) < 2:
         raise ValueError("aggregate_prediction: a forecast of at least one step (two time entries)")
     step = entries[1][0] - entries[0][0]
@@ -620,13 +580,9 @@ def aggregate_prediction(pred, aggregates, derived=None, device="cuda:0"):
         from . import derived as deriving
         deriving.check_request(names, list(derived), lat, lon, 1)
     check_request(names + list(derived or []), aggregates, step, n_steps, lat, lon, 1)
-    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("aggregate_prediction aggregates with HIP kernels: it needs a GPU")
+    require_gpu(device, "aggregate_prediction aggregates with HIP kernels: it needs a GPU", present=True)
 
-    def states_of(k):
-        _, da, i = entries[k]
-        return torch.from_numpy(np.ascontiguousarray(da.values[i], dtype=np.float32)).to(device)
-    out, incomplete = _fold_sequence(names, lat, lon, aggregates, entries[0][0], step, n_steps, device, states_of, derived)
-    for da in out.values():
-        da.incomplete = incomplete
-    return out
+    def drive(each):
+        for k, time, state in saved.states(device):
+            each(k, time, state)
+    return _fold_sequence(names, lat, lon, aggregates, entries[0][0], step, n_steps, device, drive, derived)

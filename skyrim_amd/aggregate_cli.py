@@ -5,14 +5,13 @@ forecast lies on the device (``Skyrim.aggregate_forecast`` / ``Skyrim.ensemble_f
 aggregate and echoes the paths of the files."""
 from __future__ import annotations
 
-import datetime
 from pathlib import Path
 
 import click
 import numpy as np
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 
 
 def run_aggregate(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
@@ -21,18 +20,16 @@ def run_aggregate(model_name: str, date: str, time: str, lead_time: int, list_mo
     forecast, or the ensemble mean of the aggregates with ``members`` > 1; (None, []) with ``list_models``."""
     from . import aggregate
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None, []
     for a in aggregates:
         aggregate.parse_request(a)                           # the grammar, before a model is built
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
-    step_h = model.model.time_step.total_seconds() / 3600
-    n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+    start_time = start_time_of(date, time)
+    n_steps = steps_for(model, lead_time)
     if n_steps < 1:
-        raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
+        raise ValueError(f"lead time {lead_time} h is shorter than one {model.model.time_step.total_seconds() / 3600:g}-h step of {model_name}")
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
     derived = list(derived) or None
     if members == 1:

@@ -52,6 +52,15 @@ def finish(result, save: bool, save_config):
     return result
 
 
+def save_config_with_id(save_config) -> dict:
+    """A copy of ``save_config`` (None: empty) that holds a forecast id; an id drawn here is written back into the caller's dict."""
+    cfg = dict(save_config or {})
+    cfg.setdefault("forecast_id", generate_forecast_id())
+    if save_config is not None:
+        save_config["forecast_id"] = cfg["forecast_id"]
+    return cfg
+
+
 def _b58encode(b: bytes) -> str:
     n = int.from_bytes(b, "big")
     out = ""

@@ -14,7 +14,7 @@ from typing import List
 
 import numpy as np
 
-from ...common import generate_forecast_id, save_forecast
+from ...common import save_config_with_id, save_forecast
 from ...datasource import IC_SOURCES, get_data_source
 from ...labeled import DataArray, open_dataarray
 from .utils import run_basic_inference
@@ -317,10 +317,7 @@ class GlobalModel:
         ``n_history_levels`` time entries are the state at ``start_time``; default: fetched from the data source.
         A ``save_config`` dict handed in by the caller receives the forecast id drawn here, as in the reference
         (base.py:129-130); there is no shared ``{}`` default, so an id never leaks from one call into the next."""
-        cfg = dict(save_config or {})
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        if save_config is not None:
-            save_config["forecast_id"] = cfg["forecast_id"]
+        cfg = save_config_with_id(save_config)
         pred, pending = initial_condition, []
         source = "file" if initial_condition is not None else self.source_label
         # Step k's file is written by a worker thread while the next steps run (the reference writes 573 MB synchronously between two

@@ -13,7 +13,7 @@ import logging
 import numpy as np
 import torch
 
-from ...common import generate_forecast_id, save_forecast
+from ...common import save_config_with_id, save_forecast
 from ...datasource import get_initial_condition_for_model
 from ...graphcast.spec import CHANNELS  # noqa: F401  (same list as the reference's graphcast.py:17-26)
 from ...labeled import DataArray, Dataset, concat, open_dataarray
@@ -154,10 +154,7 @@ class GraphcastModel(GlobalModel):
         """Final two time levels + per-step file paths; the stepper state is fed back step to step (never through a file).
         Files carry the stepper's latitude order (ascending), as the reference writes them."""
         times = [start_time + i * self.time_step for i in range(n_steps + 1)]
-        cfg = dict(save_config or {})
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        if save_config is not None:
-            save_config["forecast_id"] = cfg["forecast_id"]
+        cfg = save_config_with_id(save_config)
         state, output_paths = initial_condition, []
         source = "file" if initial_condition is not None else self.source_label
         for n in range(n_steps):

@@ -127,7 +127,8 @@ class Skyrim:
     def predict(self, date: str, time: str, lead_time: int = 6, save: bool = False, save_config: dict | None = None):
         """Predict a single lead-time snapshot, optionally saving every intermediate step.
         date: YYYYMMDD, time: HHMM, lead_time in hours (clipped down to a multiple of 6, at least 6)."""
-        start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
+        from ..forecast import start_time_of
+        start_time = start_time_of(date, time)
         lead_time = adjust_lead_time(lead_time, step_size=6)
         step_h = self.model.time_step.total_seconds() / 3600
         n_steps = int(lead_time // step_h)

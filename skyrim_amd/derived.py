@@ -16,15 +16,14 @@ from __future__ import annotations
 
 import ctypes
 import datetime
-import os
 import re
 from dataclasses import dataclass, field
-from pathlib import Path
 
 import numpy as np
 
 from . import native
 from .common import world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS, MAX_LEVELS = 64, 16, 16                   # include/skyrim_derive.h SKDERIVE_MAX_*
@@ -452,36 +451,19 @@ def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: 
         raise ValueError("n_steps >= 0")
     check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1)                 # before anything of the device
     deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device)
-    import torch
-    from .datasource import get_initial_condition_for_model
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("derive_fields derives with HIP kernels where the forecast lies: the model must be on a GPU")
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
+    require_gpu(model.device, "derive_fields derives with HIP kernels where the forecast lies: the model must be on a GPU")
     times, host = [], []
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            states, _ = deriver.add([state])
-            times.append(time)
-            host.append(states[0].cpu().numpy())
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
+
+    def each(k, time, state):
+        states, _ = deriver.add([state])
+        times.append(time)
+        host.append(states[0].cpu().numpy())
+    run_model(gm, start_time, n_steps, each)
     da = DataArray(np.stack(host), ["time", "channel", "lat", "lon"],
                    dict(time=times, channel=list(fields), lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
     if save:
-        from .common import generate_forecast_id, save_forecast
-        cfg = dict(save_config or {})
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        if save_config is not None:
-            save_config["forecast_id"] = cfg["forecast_id"]
+        from .common import save_config_with_id, save_forecast
+        cfg = save_config_with_id(save_config)
         da.path = save_forecast(da, f"{gm.model_name}-derived", times[0], times[-1], gm.source_label, config=cfg)
     return da
 
@@ -490,36 +472,14 @@ def derive_prediction(pred, fields, device="cuda:0"):
     """Derived fields of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF
     file or zarr store, or a list of such files (their time entries in order, duplicates of a valid time derived once).  Each time
     entry is uploaded on its own and goes through the same kernel as ``derive_fields``.  Returns DataArray(time, channel=fields, lat, lon)."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("derive_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    deriver = LeadDeriver(names, lat, lon, 1, fields, device=device)
-    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("derive_prediction derives with HIP kernels: it needs a GPU")
-    seen, times, host = set(), [], []
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("derive_prediction: the files of one forecast must share channels and grid")
-        stamps = np.asarray(da._coords["time"]).astype("datetime64[s]")
-        for k, t in enumerate(stamps):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(deriver.device)
-            states, _ = deriver.add([state])
-            times.append(t.astype(datetime.datetime))
-            host.append(states[0].cpu().numpy())
-            del state
+    from .labeled import DataArray
+    saved = open_saved(pred, "derive_prediction")
+    lat, lon = saved.lat, saved.lon
+    deriver = LeadDeriver(saved.names, lat, lon, 1, fields, device=device)
+    require_gpu(device, "derive_prediction derives with HIP kernels: it needs a GPU", present=True)
+    times, host = [], []
+    for _, time, state in saved.states(deriver.device):
+        states, _ = deriver.add([state])
+        times.append(time)
+        host.append(states[0].cpu().numpy())
     return DataArray(np.stack(host), ["time", "channel", "lat", "lon"], dict(time=times, channel=list(fields), lat=lat, lon=lon))

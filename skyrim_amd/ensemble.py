@@ -311,8 +311,9 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
-    from .common import generate_forecast_id, save_forecast
+    from .common import save_config_with_id, save_forecast
     from .datasource import get_initial_condition_for_model
+    from .leads import forget_resident
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
@@ -431,15 +432,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     dev = x0.device
     if dev.type != "cuda":
         raise RuntimeError("ensemble_forecast makes and reduces its members with HIP kernels: the model must be on a GPU")
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the interleaved loops below are not a state a later rollout continues from
+    forget_resident(model, closed=False)                   # the interleaved loops below are not a state a later rollout continues from
     std = channel_std(model)
     if std.numel() != x0.shape[2]:
         raise ValueError(f"channel_std holds {std.numel()} values for {x0.shape[2]} input channels")
-    cfg = dict(save_config or {})
-    cfg.setdefault("forecast_id", generate_forecast_id())
-    if save_config is not None:
-        save_config["forecast_id"] = cfg["forecast_id"]
+    cfg = save_config_with_id(save_config)
     fid = cfg["forecast_id"]
     zarr = (cfg.get("file_type") or "netcdf") == "zarr"
 
@@ -458,8 +455,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if bplan is not None:                                  # the seeds bred through the model (skyrim_amd/breeding.py): they replace the seeds
         breeder = breed.Breeder(model, bplan, x0, sigma_all, float(perturb_scale), int(seed), start_time, seed_member, mask=plan.channel_mask)
         breeder.run(M)
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
+        forget_resident(model, closed=False)
     loops, current, stepper = [], [], None
     if splan is not None:                                  # per-step perturbations (skyrim_amd/stochastic.py): the members are held as states,
         from .breeding import step_once                    # each lead is the model's own lead 1 from the perturbed state before it
@@ -673,9 +669,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 loop.close()
             except FloatingPointError:
                 pass                                       # every delivered step was checked above, by member
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
+        forget_resident(model)
 
     grid = dict(lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon))
 

@@ -3,28 +3,25 @@ perturbation scale and seed of a perturbed-initial-condition ensemble (``Skyrim.
 spread of every step and echoes the paths."""
 from __future__ import annotations
 
-import datetime
 from pathlib import Path
 
 import click
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 
 
 def run_ensemble(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
                  filter_vars: str, members: int = 10, perturb_scale: float = 1e-3, seed: int = 0):
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return []
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
-    step_h = model.model.time_step.total_seconds() / 3600
-    n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+    start_time = start_time_of(date, time)
+    n_steps = steps_for(model, lead_time)
     if n_steps < 1:
-        raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
+        raise ValueError(f"lead time {lead_time} h is shorter than one {model.model.time_step.total_seconds() / 3600:g}-h step of {model_name}")
     ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed,
                                   products=("mean", "spread"), save=True,
                                   save_config={"output_dir": output_dir or str(Path.cwd() / "outputs"),

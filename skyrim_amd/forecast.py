@@ -13,6 +13,17 @@ from .common import AVAILABLE_MODELS
 yesterday = (datetime.now() - timedelta(days=1)).date().isoformat().replace("-", "")
 
 
+def start_time_of(date: str, time: str) -> datetime:
+    """The start time of the options ``--date YYYYMMDD --time HHMM``."""
+    return datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
+
+
+def steps_for(model, lead_time: int) -> int:
+    """The steps of ``model`` (a ``Skyrim``) in ``lead_time`` hours, the lead time clipped down to a multiple of 6 h, at least 6."""
+    from .core.models.base import adjust_lead_time
+    return int(adjust_lead_time(lead_time, step_size=6) // (model.model.time_step.total_seconds() / 3600))
+
+
 def run_forecast(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str,
                  output_dir: str, filter_vars: str):
     from .core import Skyrim

@@ -26,7 +26,8 @@ from pathlib import Path
 import numpy as np
 
 from . import native
-from .common import world_size as _world_size
+from .common import finish as _finish, world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import fill_channels, member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, MAX_POINTS, CHUNK = 64, 256, 1 << 20, 8          # include/skyrim_point.h SKPOINT_MAX_*, SKPOINT_CHUNK
@@ -597,71 +598,21 @@ def point_model(gm, start_time: datetime.datetime, n_steps: int, points, channel
     if _world_size() > 1:
         raise NotImplementedError("points are sampled on one GPU; a process group of more than one rank is out of scope (DESIGN.md 25)")
     lp = LeadPoints(names, model.grid.lat, model.grid.lon, 1, points, channels, method, model.device, list(derived or []), n_steps + 1)      # before the device
-    import torch
-    from .datasource import get_initial_condition_for_model
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("point_forecast samples with HIP kernels where the forecast lies: the model must be on a GPU")
+    require_gpu(model.device, "point_forecast samples with HIP kernels where the forecast lies: the model must be on a GPU")
     if lp.needs_derived:
         deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, 1, list(derived), device=model.device)
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            lp.add(time, [state], None, deriver.add([state]) if deriver is not None else None)
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
-    pf = lp.result(gm.model_name)
-    if save:
-        from .common import OUTPUT_DIR, generate_forecast_id
-        cfg = dict(save_config or {})
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        if save_config is not None:
-            save_config["forecast_id"] = cfg["forecast_id"]
-        pf.forecast_id = cfg["forecast_id"]
-        pf.save(cfg.get("output_dir") or OUTPUT_DIR)
-    return pf
+    run_model(gm, start_time, n_steps,
+              lambda k, time, state: lp.add(time, [state], None, deriver.add([state]) if deriver is not None else None))
+    return _finish(lp.result(gm.model_name), save, save_config)
 
 
 def extract_prediction(pred, points, channels=None, method: str = "bilinear", device="cuda:0") -> PointForecast:
     """Point values of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file
     or zarr store, or a list of such files (their time entries in order, duplicates of a valid time sampled once).  Each time entry is
     uploaded, sampled by the same kernel as ``point_forecast`` and dropped.  Returns a ``PointForecast`` with one member."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("extract_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    n_times = len({t for da in arrays for t in np.asarray(da._coords["time"]).astype("datetime64[s]")})
-    lp = LeadPoints(names, lat, lon, 1, points, channels, method, device, (), n_times)
-    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("extract_prediction samples with HIP kernels: it needs a GPU")
-    seen = set()
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("extract_prediction: the files of one forecast must share channels and grid")
-        for k, t in enumerate(np.asarray(da._coords["time"]).astype("datetime64[s]")):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.array(da.values[k], dtype=np.float32, order="C")).to(device)       # (a copy: the file's array may be read-only)
-            lp.add(t.astype(datetime.datetime), [state])
-            del state
+    saved = open_saved(pred, "extract_prediction")
+    lp = LeadPoints(saved.names, saved.lat, saved.lon, 1, points, channels, method, device, (), len(saved.entries))
+    require_gpu(device, "extract_prediction samples with HIP kernels: it needs a GPU", present=True)
+    for _, time, state in saved.states(device):
+        lp.add(time, [state])
     return lp.result()

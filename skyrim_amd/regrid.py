@@ -16,13 +16,13 @@ from __future__ import annotations
 
 import ctypes
 import datetime
-import os
 from dataclasses import dataclass, field
 
 import numpy as np
 
 from . import native
 from .common import world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import fill_channels, member_count, member_set
 
 MAX_MEMBERS, MAX_CHANNELS, MAX_TAPS, MAX_W = 64, 256, 32, 8192          # include/skyrim_regrid.h SKREGRID_MAX_*
@@ -521,35 +521,18 @@ def regrid_model(gm, start_time: datetime.datetime, n_steps: int, grid, method: 
     if n_steps < 0:
         raise ValueError("n_steps >= 0")
     rg = LeadRegridder(model.out_channel_names, model.grid.lat, model.grid.lon, 1, grid, method, channels, device=model.device)      # before anything of the device
-    import torch
-    from .datasource import get_initial_condition_for_model
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("regrid_forecast regrids with HIP kernels where the forecast lies: the model must be on a GPU")
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
+    require_gpu(model.device, "regrid_forecast regrids with HIP kernels where the forecast lies: the model must be on a GPU")
     times, host = [], []
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            states, _ = rg.add([state])
-            times.append(time)
-            host.append(states[0].cpu().numpy())
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
+
+    def each(k, time, state):
+        states, _ = rg.add([state])
+        times.append(time)
+        host.append(states[0].cpu().numpy())
+    run_model(gm, start_time, n_steps, each)
     da = DataArray(np.stack(host), ["time", "channel", "lat", "lon"], dict(time=times, channel=list(rg.channels), lat=rg.lat_out, lon=rg.lon_out))
     if save:
-        from .common import generate_forecast_id, save_forecast
-        cfg = dict(save_config or {})
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        if save_config is not None:
-            save_config["forecast_id"] = cfg["forecast_id"]
+        from .common import save_config_with_id, save_forecast
+        cfg = save_config_with_id(save_config)
         da.path = save_forecast(da, f"{gm.model_name}-regrid", times[0], times[-1], gm.source_label, config=cfg)
     return da
 
@@ -558,36 +541,13 @@ def regrid_prediction(pred, grid, method: str = "conservative", device="cuda:0",
     """A forecast that already exists, on the target grid: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF
     file or zarr store, or a list of such files (their time entries in order, duplicates of a valid time regridded once).  Each time entry
     is uploaded on its own and goes through the same kernel as ``regrid_forecast``.  Returns DataArray(time, channel, lat, lon)."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("regrid_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    rg = LeadRegridder(names, lat, lon, 1, grid, method, channels, device=device)
-    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("regrid_prediction regrids with HIP kernels: it needs a GPU")
-    seen, times, host = set(), [], []
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("regrid_prediction: the files of one forecast must share channels and grid")
-        stamps = np.asarray(da._coords["time"]).astype("datetime64[s]")
-        for k, t in enumerate(stamps):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.array(da.values[k], dtype=np.float32, order="C")).to(rg.device)       # (a copy: the file's array may be read-only)
-            states, _ = rg.add([state])
-            times.append(t.astype(datetime.datetime))
-            host.append(states[0].cpu().numpy())
-            del state
+    from .labeled import DataArray
+    saved = open_saved(pred, "regrid_prediction")
+    rg = LeadRegridder(saved.names, saved.lat, saved.lon, 1, grid, method, channels, device=device)
+    require_gpu(device, "regrid_prediction regrids with HIP kernels: it needs a GPU", present=True)
+    times, host = [], []
+    for _, time, state in saved.states(rg.device):
+        states, _ = rg.add([state])
+        times.append(time)
+        host.append(states[0].cpu().numpy())
     return DataArray(np.stack(host), ["time", "channel", "lat", "lon"], dict(time=times, channel=list(rg.channels), lat=rg.lat_out, lon=rg.lon_out))

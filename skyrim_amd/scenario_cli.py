@@ -5,7 +5,6 @@ Gram matrix is made where the members lie on the device (``Skyrim.ensemble_forec
 probabilities and representative members and the variance fractions of the EOFs are printed, ``--output`` writes them as ``.json``."""
 from __future__ import annotations
 
-import datetime
 import json
 from pathlib import Path
 
@@ -13,7 +12,7 @@ import click
 import numpy as np
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 
 
 def parse_region(text: str):
@@ -51,15 +50,13 @@ def run_scenario(model_name: str, date: str, time: str, lead_time: int, list_mod
                  members: int = 10, perturb_scale: float = 1e-3, seed: int = 0):
     """Returns the ``scenarios.Scenarios``; None with ``list_models``."""
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
+    start_time = start_time_of(date, time)
     if n_steps is None:
-        step_h = model.model.time_step.total_seconds() / 3600
-        n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+        n_steps = steps_for(model, lead_time)
     ens = model.ensemble_forecast(start_time, n_steps=n_steps, n_members=members, perturb_scale=perturb_scale, seed=seed, products=(),
                                   scenarios=spec)
     return ens.scenarios

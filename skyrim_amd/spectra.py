@@ -22,12 +22,13 @@ import ctypes
 import datetime
 import json
 import math
-import os
 from pathlib import Path
 
 import numpy as np
 
 from . import native
+from .common import finish as _finish
+from .leads import open_saved, require_gpu, run_model
 from .members import fill_channels, member_set
 
 # include/skyrim_spec.h SKSPEC_*
@@ -461,8 +462,6 @@ class TruthStates:
 def spectrum_model(gm, start_time, n_steps: int = 4, spectra=None, truth=None, save: bool = False, save_config: dict | None = None) -> Spectra:
     """``GlobalModel.spectrum_forecast`` (core/models/base.py has the user-facing description): the deterministic route, M = 1, driven
     like ``verify``; no state goes to the host."""
-    import torch
-    from .datasource import get_initial_condition_for_model
     model = gm.model
     if spectra is None:
         raise ValueError("spectrum_forecast: spectra={'channels': [...], 'bands': {...}}")
@@ -470,78 +469,27 @@ def spectrum_model(gm, start_time, n_steps: int = 4, spectra=None, truth=None, s
         raise ValueError("n_steps >= 0")
     names = list(model.out_channel_names)
     ls = LeadSpectra(names, model.grid.lat, model.grid.lon, 1, spectra, device=model.device, truth=truth is not None)
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("spectrum_forecast makes the spectra with HIP kernels where the states lie: the model must be on a GPU")
+    require_gpu(model.device, "spectrum_forecast makes the spectra with HIP kernels where the states lie: the model must be on a GPU")
     truths = None if truth is None else TruthStates(truth, names, ls.req["channels"], model.grid.lat, model.grid.lon, model.device)
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            ls.add(time, [state], None, None if truths is None else truths.at(time))
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
-    res = ls.result(gm.model_name)
-    if save:
-        from .common import OUTPUT_DIR, generate_forecast_id
-        cfg = save_config if save_config is not None else {}
-        cfg.setdefault("forecast_id", generate_forecast_id())
-        res.forecast_id = cfg["forecast_id"]
-        res.path = res.save(cfg.get("output_dir") or OUTPUT_DIR)
-    return res
+    run_model(gm, start_time, n_steps, lambda k, time, state: ls.add(time, [state], None, None if truths is None else truths.at(time)))
+    return _finish(ls.result(gm.model_name), save, save_config)
 
 
 def spectra_prediction(pred, truth=None, channels=None, bands=None, device="cuda:0", model_name: str = "") -> Spectra:
     """The spectra of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file
     or zarr store, or a list of such files (their time entries in order, duplicates of a valid time taken once) -- the route for GraphCast,
     as ``verify.score_prediction``.  Each time entry is uploaded on its own and goes through the same kernel as ``spectrum_forecast``."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            model_name = model_name or (p.model if isinstance(p.model, str) else "")
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            model_name = model_name or Path(p).name.split("__")[0].split(".")[0]
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("spectra_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a "
-                             "saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
+    saved = open_saved(pred, "spectra_prediction")
+    names, lat, lon = saved.names, saved.lat, saved.lon
     spec = dict(channels=list(channels) if channels is not None else names)
     if bands is not None:
         spec["bands"] = bands
     ls = LeadSpectra(names, lat, lon, 1, spec, device=device, truth=truth is not None)
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("spectra_prediction makes the spectra with HIP kernels: it needs a GPU")
-    truths = None if truth is None else TruthStates(truth, names, ls.req["channels"], lat, lon, dev)
-    seen = set()
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("spectra_prediction: the files of one forecast must share channels and grid")
-        times = np.asarray(da._coords["time"]).astype("datetime64[s]")
-        for k, t in enumerate(times):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(dev)
-            when = t.astype(datetime.datetime)
-            ls.add(when, [state], None, None if truths is None else truths.at(when))
-            del state
-    return ls.result(model_name or "forecast")
+    require_gpu(device, "spectra_prediction makes the spectra with HIP kernels: it needs a GPU", present=True)
+    truths = None if truth is None else TruthStates(truth, names, ls.req["channels"], lat, lon, device)
+    for _, time, state in saved.states(device):
+        ls.add(time, [state], None, None if truths is None else truths.at(time))
+    return ls.result(model_name or saved.model_name or "forecast")
 
 
 def from_members(members, lat, lon, names=None, channels=None, bands=None, truth=None, times=None) -> Spectra:

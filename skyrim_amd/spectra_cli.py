@@ -6,14 +6,13 @@ At every lead time the spectra are made where the states lie on the device (``Sk
 adds the effective resolution against the model's own kind of data source, ``--output`` writes everything as ``.json``."""
 from __future__ import annotations
 
-import datetime
 from pathlib import Path
 
 import click
 import numpy as np
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 
 
 def parse_band(text: str):
@@ -60,15 +59,13 @@ def run_spectra(model_name: str, date: str, time: str, lead_time: int, list_mode
                 members: int = 1, perturb_scale: float = 1e-3, seed: int = 0, perturbation: str = "white", truth: bool = False):
     """Returns the ``spectra.Spectra``; None with ``list_models``."""
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
+    start_time = start_time_of(date, time)
     if n_steps is None:
-        step_h = model.model.time_step.total_seconds() / 3600
-        n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+        n_steps = steps_for(model, lead_time)
     if members == 1:
         from .verify import default_truth
         return model.spectrum_forecast(start_time, n_steps=n_steps, spectra=spec, truth=default_truth(model.model) if truth else None)

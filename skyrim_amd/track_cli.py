@@ -4,29 +4,26 @@ are tuned most.  Detects cyclone centres at every lead time where the forecast l
 ``Skyrim.ensemble_forecast(tracks=True)``), prints one line per track point and echoes the path of the JSON file."""
 from __future__ import annotations
 
-import datetime
 from pathlib import Path
 
 import click
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 
 
 def run_track(model_name: str, date: str, time: str, lead_time: int, list_models: bool, initial_conditions: str, output_dir: str,
               members: int = 1, perturb_scale: float = 1e-3, seed: int = 0, config: dict | None = None):
     """Returns the ``tracks.Tracks`` (None with ``list_models``); the JSON file's path is ``tracks.path``."""
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
-    step_h = model.model.time_step.total_seconds() / 3600
-    n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+    start_time = start_time_of(date, time)
+    n_steps = steps_for(model, lead_time)
     if n_steps < 1:
-        raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
+        raise ValueError(f"lead time {lead_time} h is shorter than one {model.model.time_step.total_seconds() / 3600:g}-h step of {model_name}")
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
     if members == 1:
         return model.track_cyclones(start_time, n_steps=n_steps, config=config, save=True, save_config=cfg)

@@ -17,7 +17,6 @@ import ctypes
 import datetime
 import json
 import math
-import os
 from dataclasses import asdict, dataclass
 from pathlib import Path
 
@@ -25,6 +24,7 @@ import numpy as np
 
 from . import native
 from .common import finish as _finish, iso as _iso, world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import member_set
 
 MAX_MEMBERS = 64                                                # include/skyrim_track.h SKTRACK_MAX_MEMBERS
@@ -523,25 +523,8 @@ def track_model(gm, start_time: datetime.datetime, n_steps: int = 4, config=None
         raise ValueError("n_steps >= 0")
     check_request(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1, config)      # before anything of the device
     tracker = LeadTracker(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1, config, device=model.device)
-    import torch
-    from .datasource import get_initial_condition_for_model
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("track_cyclones detects with HIP kernels where the forecast lies: the model must be on a GPU")
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            tracker.add(time, [state])
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
+    require_gpu(model.device, "track_cyclones detects with HIP kernels where the forecast lies: the model must be on a GPU")
+    run_model(gm, start_time, n_steps, lambda k, time, state: tracker.add(time, [state]))
     return _finish(tracker.result(), save, save_config)
 
 
@@ -549,36 +532,9 @@ def track_prediction(pred, config=None, device="cuda:0", model_name: str = "") -
     """Tracks of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file or
     zarr store, or a list of such files (their time entries in order, duplicates of a valid time searched once).  Each time entry is
     uploaded on its own and goes through the same kernels as ``track_cyclones``."""
-    import torch
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            model_name = model_name or (p.model if isinstance(p.model, str) else "")
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            model_name = model_name or Path(p).name.split("__")[0].split(".")[0]
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("track_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    tracker = LeadTracker(model_name or "forecast", names, lat, lon, 1, config, device=device)
-    if torch.device(device).type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("track_prediction detects with HIP kernels: it needs a GPU")
-    seen = set()
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("track_prediction: the files of one forecast must share channels and grid")
-        times = np.asarray(da._coords["time"]).astype("datetime64[s]")
-        for k, t in enumerate(times):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(tracker.device)
-            tracker.add(t.astype(datetime.datetime), [state])
-            del state
+    saved = open_saved(pred, "track_prediction")
+    tracker = LeadTracker(model_name or saved.model_name or "forecast", saved.names, saved.lat, saved.lon, 1, config, device=device)
+    require_gpu(device, "track_prediction detects with HIP kernels: it needs a GPU", present=True)
+    for _, time, state in saved.states(tracker.device):
+        tracker.add(time, [state])
     return tracker.result()

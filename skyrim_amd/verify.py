@@ -23,6 +23,7 @@ import torch
 
 from . import native
 from .common import finish as _finish, iso as _iso, world_size as _world_size
+from .leads import open_saved, require_gpu, run_model
 from .members import member_count, member_set
 
 MAX_MEMBERS = 64                                                # include/skyrim_score.h SKSCORE_MAX_MEMBERS
@@ -407,7 +408,6 @@ def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None
                  save_config: dict | None = None, grid=None, regrid_method: str = "conservative", events=None,
                  neighbourhoods_km=()) -> Scores:
     """``GlobalModel.verify`` (core/models/base.py has the user-facing description)."""
-    from .datasource import get_initial_condition_for_model
     model = gm.model
     check_request(1, model.out_channel_names, channels)
     ev = {} if events is None else dict(events=events, neighbourhoods_km=neighbourhoods_km)
@@ -427,26 +427,14 @@ def verify_model(gm, start_time: datetime.datetime, n_steps: int = 4, truth=None
     else:
         scorer = LeadScorer(gm.model_name, model.out_channel_names, model.grid.lat, model.grid.lon, 1,
                             default_truth(gm) if truth is None else truth, climatology, channels, device=model.device, **ev)
-    if torch.device(model.device).type != "cuda":
-        raise RuntimeError("verify scores the forecast with HIP kernels where it lies: the model must be on a GPU")
-    x0 = get_initial_condition_for_model(model, gm.data_source, start_time)
-    if hasattr(model, "__dict__"):
-        model._resident_state = None                       # the loop below is not a state a later rollout continues from
-    loop = model(start_time, x0)
-    try:
-        for k in range(n_steps + 1):
-            time, out, _ = next(loop)
-            state = (out[0] if out.dim() == 4 else out).contiguous()
-            if regridder is None:
-                scorer.add(time, [state])
-            else:
-                scorer.add(time, *regridder.add([state]))
-            del state, out
-    finally:
-        loop.close()
-        if hasattr(model, "__dict__"):
-            model._resident_state = None
-            model.__dict__.pop("_state_is_own_output", None)
+    require_gpu(model.device, "verify scores the forecast with HIP kernels where it lies: the model must be on a GPU")
+
+    def each(k, time, state):
+        if regridder is None:
+            scorer.add(time, [state])
+        else:
+            scorer.add(time, *regridder.add([state]))
+    run_model(gm, start_time, n_steps, each)
     result = scorer.result()
     if regridder is not None:
         result.grid = regrid.grid_label(grid)
@@ -458,36 +446,10 @@ def score_prediction(pred, truth, climatology=None, device="cuda:0", channels=No
     """Scores of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF file or
     zarr store, or a list of such files (their time entries in order, duplicates of a valid time scored once).  Each time entry is
     uploaded on its own and goes through the same kernel as ``verify``; ``events`` / ``neighbourhoods_km`` as there."""
-    from .labeled import DataArray, open_dataarray
-    items = list(pred) if isinstance(pred, (list, tuple)) else [pred]
-    arrays = []
-    for p in items:
-        if hasattr(p, "prediction") and isinstance(getattr(p, "prediction"), DataArray):
-            model_name = model_name or (p.model if isinstance(p.model, str) else "")
-            p = p.prediction
-        elif isinstance(p, (str, os.PathLike)):
-            model_name = model_name or Path(p).name.split("__")[0].split(".")[0]
-            p = open_dataarray(os.fspath(p))
-        if not isinstance(p, DataArray) or tuple(p.dims) != ("time", "channel", "lat", "lon"):
-            raise ValueError("score_prediction: a forecast is a (time, channel, lat, lon) DataArray, a GlobalPrediction holding one, or a saved file / store")
-        arrays.append(p)
-    first = arrays[0]
-    names = first.channel.values.tolist()
-    lat, lon = np.asarray(first._coords["lat"]), np.asarray(first._coords["lon"])
-    scorer = LeadScorer(model_name or "forecast", names, lat, lon, 1, truth, climatology, channels, device=device,
-                        **({} if events is None else dict(events=events, neighbourhoods_km=neighbourhoods_km)))
-    if scorer.device.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("score_prediction scores with HIP kernels: it needs a GPU")
-    seen = set()
-    for da in arrays:
-        if da.channel.values.tolist() != names or not np.array_equal(da._coords["lat"], lat) or not np.array_equal(da._coords["lon"], lon):
-            raise ValueError("score_prediction: the files of one forecast must share channels and grid")
-        times = np.asarray(da._coords["time"]).astype("datetime64[s]")
-        for k, t in enumerate(times):
-            if t in seen:
-                continue
-            seen.add(t)
-            state = torch.from_numpy(np.ascontiguousarray(da.values[k], dtype=np.float32)).to(scorer.device)
-            scorer.add(t.astype(datetime.datetime), [state])
-            del state
+    saved = open_saved(pred, "score_prediction")
+    scorer = LeadScorer(model_name or saved.model_name or "forecast", saved.names, saved.lat, saved.lon, 1, truth, climatology, channels,
+                        device=device, **({} if events is None else dict(events=events, neighbourhoods_km=neighbourhoods_km)))
+    require_gpu(scorer.device, "score_prediction scores with HIP kernels: it needs a GPU", present=True)
+    for _, time, state in saved.states(scorer.device):
+        scorer.add(time, [state])
     return scorer.result()

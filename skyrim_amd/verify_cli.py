@@ -9,13 +9,12 @@ truth are regridded on the device, skyrim_amd/regrid.py; the default scores on t
 ``Skyrim.ensemble_forecast(scores=True)``), prints one line per lead time and channel and echoes the path of the JSON file."""
 from __future__ import annotations
 
-import datetime
 from pathlib import Path
 
 import click
 
 from .common import AVAILABLE_MODELS
-from .forecast import yesterday
+from .forecast import start_time_of, steps_for, yesterday
 from .verify import DEFAULT_CHANNELS
 
 
@@ -27,7 +26,6 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
                stoch_tau_h: float | None = None, stoch_length_scale_km: float | None = None):
     """Returns the ``verify.Scores`` (None with ``list_models``); the JSON file's path is ``scores.path``."""
     from .core import Skyrim
-    from .core.models.base import adjust_lead_time
     if list_models:
         print("Available models:", Skyrim.list_available_models())
         return None
@@ -38,11 +36,10 @@ def run_verify(model_name: str, date: str, time: str, lead_time: int, list_model
     elif neighbourhood_km:
         raise ValueError("--neighbourhood_km gives the scales of the events' fractions skill score: it needs --event")
     model = Skyrim(model_name, ic_source=initial_conditions)
-    start_time = datetime.datetime(int(date[:4]), int(date[4:6]), int(date[6:8]), int(time[:2]), int(time[2:4]))
-    step_h = model.model.time_step.total_seconds() / 3600
-    n_steps = int(adjust_lead_time(lead_time, step_size=6) // step_h)
+    start_time = start_time_of(date, time)
+    n_steps = steps_for(model, lead_time)
     if n_steps < 1:
-        raise ValueError(f"lead time {lead_time} h is shorter than one {step_h:g}-h step of {model_name}")
+        raise ValueError(f"lead time {lead_time} h is shorter than one {model.model.time_step.total_seconds() / 3600:g}-h step of {model_name}")
     scored = filter_vars.split(",") if bool(filter_vars) else None
     cfg = {"output_dir": output_dir or str(Path.cwd() / "outputs")}
     on_grid = {} if not grid else dict(grid=grid, regrid_method=regrid_method)
