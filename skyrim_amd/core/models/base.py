@@ -120,7 +120,7 @@ class GlobalModel:
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
                           scenarios: dict | None = None, spectra: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
-                          aggregates: List[str] | None = None,
+                          aggregates: List[str] | None = None, derived_surface=None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -140,7 +140,9 @@ class GlobalModel:
         every member at every lead time, right after the scores and on the same states (skyrim_amd/tracks.py, DESIGN.md 20;
         ``track_config``: a ``tracks.TrackerConfig`` or a dict of its fields); the linked ``tracks.Tracks`` land in
         ``EnsembleForecast.tracks``.  ``derived=[...]`` names derived fields (``ws10m``, ``ws100m``, ``ws<level>``, ``thk<a>_<b>``, ``vo<X>``,
-        ``div<X>``, ``ivt``, ``ivtu``, ``ivtv``, ``iwv``: skyrim_amd/derived.py) that are formed from every member on the device at
+        ``div<X>``, ``ivt``, ``ivtu``, ``ivtv``, ``iwv``: skyrim_amd/derived.py; and the column thermodynamics ``td<level>``,
+        ``thetae<level>``, ``kx``, ``tt``, ``zdeg0``, ``sbcape``, ``mucape``, ``muli`` ... of DESIGN.md 30, with ``derived_surface=`` the (lat, lon) surface
+        geopotential that masks the levels below the ground -- without it they are treated as air) that are formed from every member on the device at
         each lead time; the same ``products`` of them, ``exceed`` / ``quantiles`` under their names and, with ``scores=True``, their scores land
         in ``EnsembleForecast.derived``.  ``grid=`` names a target grid (``"1.5deg"`` or a float, ``(lat, lon)`` arrays, or
         ``dict(region=(lat_s, lat_n, lon_w, lon_e), res=...)``: skyrim_amd/regrid.py) every member is also put on at each lead
@@ -199,6 +201,8 @@ class GlobalModel:
             extra.update(events=events, neighbourhoods_km=neighbourhoods_km)
         if derived is not None:
             extra["derived"] = derived
+        if derived_surface is not None:
+            extra["derived_surface"] = derived_surface
         if grid is not None:
             extra.update(grid=grid, regrid_method=regrid_method)
         if aggregates is not None:
@@ -230,14 +234,16 @@ class GlobalModel:
         return tracks.track_model(self, start_time, n_steps=n_steps, config=config, save=save, save_config=save_config)
 
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields: List[str] = (), save: bool = False,
-                      save_config: dict | None = None):
+                      save_config: dict | None = None, derived_surface=None):
         """Derived fields of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/derived.py): wind speed
         (``ws10m``, ``ws100m``, ``ws<level>``), thickness (``thk<a>_<b>``), vorticity and divergence (``vo<X>``, ``div<X>``) and the column
-        integrals ``ivt``, ``ivtu``, ``ivtv``, ``iwv``.  The model's TimeLoop is advanced and every state is derived where it lies in HBM; only
+        integrals ``ivt``, ``ivtu``, ``ivtv``, ``iwv``, and the column thermodynamics of DESIGN.md 30 (``td<level>``, ``thetae<level>``, ``kx``,
+        ``tt``, ``zdeg0``, ``sbcape``, ``mucape``, ``muli`` ...; ``derived_surface``: the (lat, lon) surface geopotential that masks the levels
+        below the ground -- without it they are treated as air).  The model's TimeLoop is advanced and every state is derived where it lies in HBM; only
         the derived planes cross to the host.  Returns DataArray(time, channel=fields, lat, lon); ``save=True`` writes it as the forecast of
         ``{model}-derived``.  A field whose input channels the model lacks is refused with ValueError before the device is touched."""
         from ... import derived
-        return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config)
+        return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config, surface=derived_surface)
 
     def aggregate_forecast(self, start_time: datetime.datetime, n_steps: int = 4, aggregates: List[str] = (), derived: List[str] | None = None,
                            save: bool = False, save_config: dict | None = None):

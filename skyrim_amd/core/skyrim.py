@@ -113,10 +113,10 @@ class Skyrim:
         return regrid.regrid_prediction(pred, grid, method, device=device, **kwargs)
 
     @staticmethod
-    def derive_prediction(pred, fields, device="cuda:0"):
+    def derive_prediction(pred, fields, device="cuda:0", derived_surface=None):
         """Derived fields of a forecast that is already in memory or on disk (``derived.derive_prediction``)."""
         from .. import derived
-        return derived.derive_prediction(pred, fields, device=device)
+        return derived.derive_prediction(pred, fields, device=device, surface=derived_surface)
 
     @staticmethod
     def track_prediction(pred, config=None, device="cuda:0", **kwargs):

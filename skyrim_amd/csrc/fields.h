@@ -1,4 +1,4 @@
-// What the product kernels (score, event, track, derive, regrid, agg, point, gram, breed, spec) share on the device: how a lane reads and
+// What the product kernels (score, event, track, derive, thermo, regrid, agg, point, gram, breed, spec) share on the device: how a lane reads and
 // writes the points of a member state, and the wave reductions.  Everything is __device__ __forceinline__ and leaves no call behind.
 // (ens_ops.hip is not among them: its load goes through a generic pointer.)
 #pragma once

@@ -7,7 +7,9 @@ Layers:
 * the binding of libskyrim_derive.so (``SPEC``, ``load_library``, ``run``); the same call is ``torch.ops.skyrim_hip.derive_fields``.
   Derivation has no CPU fallback;
 * the catalogue: ``plan`` resolves user-facing names (``ws10m``, ``thk500_1000``, ``vo850``, ``div850``, ``ivt`` ...) against a model's
-  channels into a program of ops, ``row_table`` makes the row coefficients of vorticity and divergence in float64;
+  channels into a program of ops, ``row_table`` makes the row coefficients of vorticity and divergence in float64.  The names of column
+  thermodynamics (``td850``, ``thetae850``, ``kx``, ``zdeg0``, ``mucape`` ...: DESIGN.md 30) resolve into ops of libskyrim_thermo.so
+  (skyrim_amd/thermo.py), which write into the same buffer; a request that names none of them never loads that library;
 * the drivers: ``LeadDeriver`` (what ``ensemble.run`` calls at every lead time with ``derived=[...]``), ``TruthDeriver`` (the hook that
   lets ``verify.LeadScorer`` score derived fields against a truth of raw channels), ``derive_model`` (``GlobalModel.derive_fields``)
   and ``derive_prediction`` for forecasts that are already on disk.
@@ -222,7 +224,9 @@ def row_table(lat, lon) -> tuple:
 class Plan:
     """A resolved request.  ``fields``: the derived names, slot d = fields[d]; ``ops``: the program; ``inputs[name]``: the raw channels a
     derived field reads; ``rowc / edges``: the row table when vorticity or divergence is asked for; ``levels / weights``: the pressure
-    levels (hPa) and float64 trapezoid weights of the column integrals, when asked for."""
+    levels (hPa) and float64 trapezoid weights of the column integrals, when asked for.  ``thermo_ops``: the program of
+    libskyrim_thermo.so (``thermo.Op``), whose slots are numbered with those of ``ops``; ``moisture``: "q" or "r", what they read;
+    ``column``: {"parcel" / "freeze": the pressure levels (hPa, bottom-up) of their columns}."""
     fields: list
     ops: list
     inputs: dict
@@ -230,6 +234,9 @@ class Plan:
     edges: tuple = (EDGE_POLE, EDGE_POLE)
     levels: list = field(default_factory=list)
     weights: object = None
+    thermo_ops: list = field(default_factory=list)
+    moisture: str | None = None
+    column: dict = field(default_factory=dict)
 
 
 def column_weights(levels) -> np.ndarray:
@@ -262,6 +269,125 @@ def _parse(name: str):
     return None
 
 
+MOIST_FIELDS = ("td", "rh", "thetae", "theta")                 # in the order of a MOIST op's slots; slot 1 is ``q<level>`` for a model with r
+INDEX_FIELDS = ("kx", "tt")
+PARCEL_FIELDS = {"sbcape": (0, 0), "sbli": (0, 1), "mucape": (1, 0), "muli": (1, 1), "mucape_src": (1, 2)}      # (thermo.SRC_*, slot)
+THERMO_KNOWN = "td<level>, rh<level> (q<level> for a model with r), thetae<level>, theta<level>, kx, tt, zdeg0, sbcape, sbli, mucape, muli, mucape_src"
+
+
+def _parse_thermo(name: str):
+    """(op, key, slot) of a name of column thermodynamics -- op one of "moist", "index", "freeze", "parcel"; key the level (moist) or
+    the source (parcel) -- or None."""
+    if name in INDEX_FIELDS:
+        return "index", None, INDEX_FIELDS.index(name)
+    if name == "zdeg0":
+        return "freeze", None, 0
+    if name in PARCEL_FIELDS:
+        return ("parcel",) + PARCEL_FIELDS[name]
+    m = re.fullmatch(r"(td|rh|q|thetae|theta)(\d+)", name)
+    if m:
+        return "moist", int(m.group(2)), 1 if m.group(1) == "q" else MOIST_FIELDS.index(m.group(1))
+    return None
+
+
+def moisture_of(names):
+    """"q" when the channels hold specific humidity on a level, else "r" (relative humidity), else None"""
+    for letter in "qr":
+        if any(re.fullmatch(letter + r"\d+", n) for n in names):
+            return letter
+    return None
+
+
+def thermo_levels(names, letters, what: str, given=None, lo: int = 2) -> list:
+    """The pressure levels (hPa, descending: bottom-up) at which ``names`` holds every channel ``<letter><level>`` of ``letters``, or
+    ``given`` (then every channel must be there)."""
+    names = set(names)
+    if given is not None:
+        use = sorted((int(l) for l in given), reverse=True)
+        missing = [f"{x}{l}" for l in use for x in letters if f"{x}{l}" not in names]
+        if missing:
+            raise ValueError(f"derived: {what} needs the channels {missing}, which this model lacks")
+    else:
+        have = sorted((int(n[1:]) for n in names if re.fullmatch(letters[0] + r"\d+", n)), reverse=True)
+        use = [l for l in have if all(f"{x}{l}" in names for x in letters)]
+    if not lo <= len(use) <= MAX_LEVELS:
+        raise ValueError(f"derived: {what} runs over {lo} to {MAX_LEVELS} levels with the channels "
+                         f"{', '.join(x + '<level>' for x in letters)}; this model has {len(use)}")
+    return use
+
+
+def _thermo_raw(op: str, key, slot: int, moisture, surface: bool, levels) -> list:
+    """The raw channel names a thermo field reads, given the levels of its column (None for the fields of fixed levels)"""
+    if op == "moist":
+        return [f"t{key}"] + ([] if slot == 3 else [f"{moisture}{key}"])
+    if op == "index":
+        return ["t850", "t700", "t500", f"{moisture}850", f"{moisture}700"]
+    letters = "tz" if op == "freeze" else "t" + moisture + ("z" if surface else "")
+    return [f"{x}{l}" for x in letters for l in levels]
+
+
+def thermo_inputs(name: str, names, moisture, surface: bool, column=None):
+    """(raw channel names a thermo field reads, the levels of its column or None); every refusal of such a name is a ValueError here."""
+    op, key, slot = _parse_thermo(name)
+    names = list(names)
+    wet = not (op == "moist" and slot == 3) and op != "freeze"
+    if wet and moisture is None:
+        raise ValueError(f"derived: {name!r} needs humidity: this model has neither specific humidity (q<level>) nor relative humidity "
+                         "(r<level>) among its channels")
+    levels = None
+    if op == "moist" and name.startswith("rh") and moisture == "r":
+        raise ValueError(f"derived: {name!r}: this model carries relative humidity itself (r{key}); q{key} is what can be derived")
+    if op == "freeze":
+        levels = thermo_levels(names, "tz", repr(name), (column or {}).get("freeze"))
+    elif op == "parcel":
+        levels = thermo_levels(names, "t" + moisture + ("z" if surface else ""), repr(name), (column or {}).get("parcel"))
+        if slot == 1 and 500 not in levels:
+            raise ValueError(f"derived: {name!r} is the parcel's temperature against the environment's at 500 hPa: the column {levels} has no such level")
+    raw = _thermo_raw(op, key, slot, moisture, surface, levels)
+    missing = [c for c in raw if c not in names]
+    if missing:
+        raise ValueError(f"derived: {name!r} needs the channel{'s' if len(missing) > 1 else ''} "
+                         f"{', '.join(repr(c) for c in missing)}, which this model lacks")
+    return raw, levels
+
+
+def _thermo_plan(out: Plan, names, requests, surface: bool, column) -> None:
+    """The thermo ops of ``requests`` = [(slot, name)]: the four fields of a level share a MOIST op, kx and tt the INDEX op, the fields of
+    one source a PARCEL op."""
+    from . import thermo
+    names = list(names)
+    ch = names.index
+    out.moisture = moisture_of(names)
+    kind = thermo.R if out.moisture == "r" else thermo.Q
+    merged = {}
+    for slot, name in requests:
+        op, key, result = _parse_thermo(name)
+        raw, levels = thermo_inputs(name, names, out.moisture, surface, column)
+        out.inputs[name] = raw
+        if levels is not None:
+            out.column.setdefault(op, levels)
+        if (op, key) not in merged:
+            merged[(op, key)] = len(out.thermo_ops)
+            if op == "moist":
+                m = f"{out.moisture}{key}"
+                new = thermo.Op(thermo.MOIST, (ch(f"t{key}"),), (ch(m),) if m in names else (), (), (-1,) * 4, kind, (float(key),))
+            elif op == "index":
+                new = thermo.Op(thermo.INDEX, tuple(ch(c) for c in raw[:3]), tuple(ch(c) for c in raw[3:]), (), (-1,) * 2, kind)
+            elif op == "freeze":
+                new = thermo.Op(thermo.FREEZE, tuple(ch(f"t{l}") for l in levels), (), tuple(ch(f"z{l}") for l in levels), (-1,))
+            else:
+                new = thermo.Op(thermo.PARCEL, tuple(ch(f"t{l}") for l in levels), tuple(ch(f"{out.moisture}{l}") for l in levels),
+                                tuple(ch(f"z{l}") for l in levels) if surface else (), (-1,) * 3, kind, tuple(float(l) for l in levels), key)
+            out.thermo_ops.append(new)
+        k = merged[(op, key)]
+        old = out.thermo_ops[k]
+        slots = list(old.outputs)
+        slots[result] = slot
+        out.thermo_ops[k] = thermo.Op(old.kind, old.t, old.m, old.z, tuple(slots), old.moisture, old.pressures, old.source, old.p_src_min, old.p_top)
+    if len(out.thermo_ops) > thermo.MAX_OPS:
+        raise ValueError(f"derived: {len(out.thermo_ops)} thermodynamic ops for {[n for _, n in requests]}; one call holds {thermo.MAX_OPS}")
+
+
 def column_levels(names, levels=None) -> list:
     """The pressure levels (hPa, ascending) with q, u and v among ``names`` and 300 <= level <= 1000 (or those of ``levels``)."""
     names = set(names)
@@ -281,25 +407,29 @@ def column_levels(names, levels=None) -> list:
     return use
 
 
-def plan(names, fields, lat, lon, levels=None) -> Plan:
+def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=None) -> Plan:
     """Resolve the derived ``fields`` against the channels ``names`` of a (C, H, W) state on the grid (lat, lon).  Every refusal is a
     ValueError before the device is touched: an unknown name, a name that is one of the model's channels, missing input channels (named),
     more than ``MAX_OPS`` ops, a grid vorticity cannot be formed on.  ``vo<X>`` and ``div<X>`` of one level share an op, and so do the
-    four column integrals."""
+    four column integrals.  ``surface``: a surface geopotential will be given, so the parcel columns need z; ``column``: the levels of the
+    thermodynamic columns when they are not to be taken from the channels (``Plan.column`` of the forecast, for its truth)."""
     names, fields = list(names), list(fields)
     if not fields:
         raise ValueError("derived: at least one field")
     if len(set(fields)) != len(fields):
         raise ValueError(f"derived: a field is named twice in {fields}")
-    ops, inputs, merged = [], {}, {}
+    ops, inputs, merged, thermal = [], {}, {}, []
     out = Plan(fields, ops, inputs)
     for slot, name in enumerate(fields):
         if name in names:
             raise ValueError(f"derived: {name!r} is a channel of this model, not a derived field")
         parsed = _parse(name)
+        if parsed is None and _parse_thermo(name) is not None:
+            thermal.append((slot, name))
+            continue
         if parsed is None:
             raise ValueError(f"derived: unknown field {name!r}; known are ws10m, ws100m, ws<level>, thk<a>_<b>, vo<X>, div<X> "
-                             f"(X a level, 10m or 100m), {', '.join(COLUMN_FIELDS)}")
+                             f"(X a level, 10m or 100m), {', '.join(COLUMN_FIELDS)}, {THERMO_KNOWN}")
         kind, raw, result = parsed
         if kind == COLUMN:
             if not out.levels:
@@ -327,6 +457,8 @@ def plan(names, fields, lat, lon, levels=None) -> Plan:
         ops[k] = Op(ops[k].kind, ops[k].inputs, tuple(slots), ops[k].weights)
     if len(ops) > MAX_OPS:
         raise ValueError(f"derived: {len(ops)} ops for {fields}; one call holds {MAX_OPS}")
+    if thermal:
+        _thermo_plan(out, names, thermal, surface, column)
     if any(op.kind == VORTDIV for op in ops):
         out.rowc, e0, e1 = row_table(lat, lon)
         out.edges = (e0, e1)
@@ -335,25 +467,32 @@ def plan(names, fields, lat, lon, levels=None) -> Plan:
     return out
 
 
-def check_request(names, fields, lat, lon, n_members: int = 1, levels=None) -> Plan:
+def check_request(names, fields, lat, lon, n_members: int = 1, levels=None, surface: bool = False, column=None) -> Plan:
     """Every refusal that needs no device; returns the plan."""
     if _world_size() > 1:
         raise NotImplementedError("derived fields are made on one GPU from members that all lie there; members sharded over the ranks of "
                                   "a process group are out of scope (DESIGN.md 21)")
     if not 1 <= int(n_members) <= MAX_MEMBERS:
         raise ValueError(f"n_members = {n_members}: derived fields are made for 1 to {MAX_MEMBERS} members (SKDERIVE_MAX_MEMBERS)")
-    return plan(names, fields, lat, lon, levels)
+    return plan(names, fields, lat, lon, levels, surface, column)
 
 
 # ---- the drivers ------------------------------------------------------------------------------------------------------------------------- #
 class LeadDeriver:
     """Derives one lead time after the other into its own (M, D, H, W) buffer.  ``names``: the forecast's channels in the order of its
-    (C, H, W) states; ``fields``: the derived names, channel d of the buffer is fields[d]."""
+    (C, H, W) states; ``fields``: the derived names, channel d of the buffer is fields[d].  ``surface``: the (H, W) surface geopotential
+    in the units of z, which masks the levels below the ground for zdeg0 and the parcel fields (None: they are treated as air);
+    ``column``: ``Plan.column`` of another plan, whose thermodynamic columns this one is to use."""
 
-    def __init__(self, names, lat, lon, n_members, fields, device="cuda:0", levels=None):
-        self.plan = check_request(names, fields, lat, lon, n_members, levels)
+    def __init__(self, names, lat, lon, n_members, fields, device="cuda:0", levels=None, surface=None, column=None):
+        self.plan = check_request(names, fields, lat, lon, n_members, levels, surface is not None, column)
         self.names, self.fields, self.M = list(names), list(fields), int(n_members)
         self.lat, self.lon, self.device = np.asarray(lat, np.float64), np.asarray(lon, np.float64), device
+        self.surface = None
+        if surface is not None:
+            self.surface = np.ascontiguousarray(np.asarray(surface, np.float32))
+            if self.surface.shape != (self.lat.size, self.lon.size):
+                raise ValueError(f"derived: the surface geopotential must be ({self.lat.size}, {self.lon.size}), not {self.surface.shape}")
         self._dev = None
 
     def _buffers(self):
@@ -364,33 +503,50 @@ class LeadDeriver:
             out = torch.empty((self.M, len(self.fields), self.lat.size, self.lon.size), dtype=torch.float32, device=dev)
             states = [out[m] for m in range(self.M)]
             self._dev = dict(out=out, states=states, table=member_table(states),
-                             rowc=None if self.plan.rowc is None else torch.from_numpy(self.plan.rowc).to(dev))
+                             rowc=None if self.plan.rowc is None else torch.from_numpy(self.plan.rowc).to(dev),
+                             surface=None if self.surface is None or not self.plan.thermo_ops else torch.from_numpy(self.surface).to(dev))
         return self._dev
 
     def add(self, states, table=None) -> tuple:
-        """ONE derive launch over the M device states (C, H, W); returns (derived_states, derived_table): M (D, H, W) views of the
-        buffer and their ``ensemble.member_table``, ready for ``ensemble.stats`` and ``LeadScorer.add``.  The next ``add`` overwrites
-        them."""
+        """ONE derive launch over the M device states (C, H, W), then one of the thermodynamic ops when the request names any; returns
+        (derived_states, derived_table): M (D, H, W) views of the buffer and their ``ensemble.member_table``, ready for
+        ``ensemble.stats`` and ``LeadScorer.add``.  The next ``add`` overwrites them."""
         from .ensemble import member_table
         if len(states) != self.M:
             raise ValueError(f"{len(states)} states for a deriver of {self.M} members")
         b = self._buffers()
-        run(states, member_table(states) if table is None else table, self.plan.ops, b["out"], b["rowc"], self.plan.edges)
+        table = member_table(states) if table is None else table
+        if self.plan.ops:
+            run(states, table, self.plan.ops, b["out"], b["rowc"], self.plan.edges)
+        if self.plan.thermo_ops:
+            from . import thermo
+            thermo.run(states, table, self.plan.thermo_ops, b["out"], b["surface"])
         return b["states"], b["table"]
 
 
 class TruthDeriver:
     """The hook ``verify.LeadScorer(adapt=...)`` calls so that a truth (or climatology) of RAW channels scores derived fields: the raw
     inputs of a valid time are uploaded into a (C, H, W) state and derived by the same kernel with M = 1.  A derived field whose inputs
-    the truth lacks is not offered to the scorer; ``dropped`` names it and the channels that are missing.  ``levels``: the pressure levels of
-    the forecast's column integrals, so that the truth's are the same integral (None: those the truth holds between 300 and 1000 hPa)."""
+    the truth lacks is not offered to the scorer; ``dropped`` names it and the channels that are missing (for a thermodynamic column the
+    truth holds no part of, the plan's own refusal).  ``levels``: the pressure levels of the forecast's column integrals, so that the
+    truth's are the same integral (None: those the truth holds between 300 and 1000 hPa).
+    ``surface``, ``column``, ``moisture``: the surface geopotential, ``Plan.column`` and ``Plan.moisture`` of the forecast's deriver, so
+    that the truth's thermodynamic fields are made from the same levels and the same kind of humidity."""
 
-    def __init__(self, fields, lat, lon, device="cuda:0", levels=None):
+    def __init__(self, fields, lat, lon, device="cuda:0", levels=None, surface=None, column=None, moisture=None):
         self.fields, self.lat, self.lon, self.device, self.levels = list(fields), lat, lon, device, levels
+        self.surface, self.column, self.moisture = surface, column, moisture
         self.dropped: dict = {}
         self._derivers: dict = {}
 
     def _needs(self, name, have) -> list:
+        if _parse(name) is None:                               # column thermodynamics, over the forecast's levels when they are given
+            op, key, slot = _parse_thermo(name)
+            moisture = self.moisture or moisture_of(have) or "q"
+            levels = (self.column or {}).get(op)
+            if levels is None and op in ("freeze", "parcel"):          # (no column to be had from these channels: the plan's ValueError)
+                levels = thermo_inputs(name, have, moisture, self.surface is not None)[1]
+            return _thermo_raw(op, key, slot, moisture, self.surface is not None, levels)
         kind, raw, _ = _parse(name)
         if kind == COLUMN:
             lv = self.levels
@@ -399,11 +555,21 @@ class TruthDeriver:
             raw = [f"{x}{l}" for x in ("q" if name == "iwv" else "quv") for l in lv] or ["q<level>"]
         return list(raw)
 
+    def _partners(self, name, have) -> list:
+        """The channels that would complete the levels ``have`` holds in part for the column of ``name``: t850 without z850 names z850"""
+        op = _parse_thermo(name)[0]
+        letters = "tz" if op == "freeze" else "t" + (self.moisture or moisture_of(have) or "q") + ("z" if self.surface is not None else "")
+        levels = sorted({int(n[1:]) for n in have if n[0] in letters and n[1:].isdigit()}, reverse=True)
+        return [f"{x}{l}" for l in levels for x in letters if f"{x}{l}" not in have]
+
     def names(self, fields) -> list:
         """The derived names that can be formed from the channels ``fields`` (a ``verify._Fields``) holds."""
         have, ok = set(fields.names), []
         for name in self.fields:
-            missing = [c for c in self._needs(name, have) if c not in have]
+            try:
+                missing = [c for c in self._needs(name, have) if c not in have]
+            except ValueError as e:                            # no thermodynamic column in these channels
+                missing = self._partners(name, have) or [str(e)]
             if missing:
                 self.dropped.setdefault(name, missing)
             else:
@@ -419,7 +585,7 @@ class TruthDeriver:
             raw = []
             for name in scored:
                 raw += [c for c in self._needs(name, set(fields.names)) if c not in raw]
-            hit = (raw, LeadDeriver(raw, self.lat, self.lon, 1, list(scored), self.device, self.levels), fields)
+            hit = (raw, LeadDeriver(raw, self.lat, self.lon, 1, list(scored), self.device, self.levels, self.surface, self.column), fields)
             self._derivers[key] = hit                          # (holds ``fields``: its id stays taken while the entry lives)
         raw, deriver, _ = hit
         state = torch.from_numpy(fields.at(time, raw)).to(deriver.device)
@@ -443,14 +609,14 @@ class DerivedProducts:
     dropped: dict = field(default_factory=dict)
 
 
-def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: bool = False, save_config: dict | None = None):
+def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: bool = False, save_config: dict | None = None, surface=None):
     """``GlobalModel.derive_fields`` (core/models/base.py has the user-facing description)."""
     from .labeled import DataArray
     model = gm.model
     if n_steps < 0:
         raise ValueError("n_steps >= 0")
-    check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1)                 # before anything of the device
-    deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device)
+    check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1, surface=surface is not None)      # before anything of the device
+    deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device, surface=surface)
     require_gpu(model.device, "derive_fields derives with HIP kernels where the forecast lies: the model must be on a GPU")
     times, host = [], []
 
@@ -468,14 +634,15 @@ def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: 
     return da
 
 
-def derive_prediction(pred, fields, device="cuda:0"):
+def derive_prediction(pred, fields, device="cuda:0", surface=None):
     """Derived fields of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF
     file or zarr store, or a list of such files (their time entries in order, duplicates of a valid time derived once).  Each time
-    entry is uploaded on its own and goes through the same kernel as ``derive_fields``.  Returns DataArray(time, channel=fields, lat, lon)."""
+    entry is uploaded on its own and goes through the same kernel as ``derive_fields``.  ``surface``: the (lat, lon) surface
+    geopotential of ``LeadDeriver``.  Returns DataArray(time, channel=fields, lat, lon)."""
     from .labeled import DataArray
     saved = open_saved(pred, "derive_prediction")
     lat, lon = saved.lat, saved.lon
-    deriver = LeadDeriver(saved.names, lat, lon, 1, fields, device=device)
+    deriver = LeadDeriver(saved.names, lat, lon, 1, fields, device=device, surface=surface)
     require_gpu(device, "derive_prediction derives with HIP kernels: it needs a GPU", present=True)
     times, host = [], []
     for _, time, state in saved.states(deriver.device):

@@ -183,7 +183,7 @@ def scenario_std(model, names) -> np.ndarray:
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
              neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, breeding=None,
-             stochastic=None, aggregates=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
     derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
@@ -214,7 +214,7 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     names = list(model.out_channel_names)
     if derived is not None:
         from . import derived as deriving
-        deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members)
+        deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None)
     known = names + list(derived or [])
     aplan = None
     if aggregates is not None:
@@ -306,8 +306,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, breeding=None, stochastic=None, aggregates=None, derived=None, grid=None,
-        regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
+        derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
@@ -317,9 +317,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, events, neighbourhoods_km, scores, points, point_channels, point_method, scenarios,
-                                                  spectra, breeding, stochastic, aggregates, derived, grid, regrid_method, perturbation, length_scale_km,
-                                                  alpha, lmax, perturb_channels)
+                                                  keep_members, events=events, neighbourhoods_km=neighbourhoods_km, scores=scores, points=points,
+                                                  point_channels=point_channels, point_method=point_method, scenarios=scenarios, spectra=spectra,
+                                                  breeding=breeding, stochastic=stochastic, aggregates=aggregates, derived_surface=derived_surface,
+                                                  derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
+                                                  length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     bplan = None
@@ -370,11 +372,14 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if derived is not None:                                # derived fields (skyrim_amd/derived.py): their own products, labelled with their names
         from . import derived as deriving
         dnames = list(derived)
-        deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, M, dnames, device=model.device)
+        deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, M, dnames, device=model.device, surface=derived_surface)
+        # what every truth of these fields shares with the forecast: its thermodynamic columns, its kind of humidity and its surface mask
+        thermal = dict(column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=derived_surface)
         d_exceed, d_quant = ({k: v for k, v in t.items() if k in dnames} for t in (exceed, quantiles))
         exceed, quantiles = ({k: v for k, v in t.items() if k not in dnames} for t in (exceed, quantiles))
         if scores:
-            adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None)
+            adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None,
+                                          **thermal)
             dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
                                         device=model.device, adapt=adapt, **d_ev)
             if spectra is not None:
@@ -383,7 +388,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if aggregator is not None and scores:                  # one scorer per window group, against the same aggregates of the truth
         for g in aggregator.plan.groups:
             inner = None if derived is None else deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device,
-                                                                       levels=deriver.plan.levels or None)
+                                                                       levels=deriver.plan.levels or None, **thermal)
             hook = aggregate.TruthAggregator(g.requests, model.grid.lat, model.grid.lon, start_time, model.time_step, device=model.device,
                                              inner=inner)
             g_ev = {k: v for k, v in a_events.items() if k in g.fields}

@@ -1,6 +1,6 @@
 """The member set of the product libraries: M member states on one device plus the device table of their addresses.
 
-Every product binding (ensemble, verify, events, tracks, derived, regrid, aggregate, points, scenarios, spectra, breeding) takes
+Every product binding (ensemble, verify, events, tracks, derived, thermo, regrid, aggregate, points, scenarios, spectra, breeding) takes
 ``members`` and ``table = member_table(members)`` and validates them here, with its own name in front of every message.
 """
 from __future__ import annotations
