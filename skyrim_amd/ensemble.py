@@ -1,9 +1,11 @@
 """Perturbed-initial-condition ensembles of ONE model (include/skyrim_ens.h).
 
-Three layers:
+Four layers:
 
 * the binding of libskyrim_ens.so (``SPEC``, ``load_library``, ``perturb``, ``stats``, ``member_table``); the same calls are
   ``torch.ops.skyrim_hip.ens_perturb / ens_stats`` (skyrim_amd/ops.py);
+* ``ProductSet`` -- the products of one family of fields (raw, derived, regridded, one window group of aggregates): their buffers,
+  the ``stats`` launches and copies of an entry, its files, its labelled arrays;
 * ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb`` (white noise) or
   ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), with ``breeding=`` bred from those seeds
   through the model itself (skyrim_amd/breeding.py), ONE TimeLoop
@@ -18,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import datetime
+import functools
 import math
 from dataclasses import dataclass, field
 
@@ -120,6 +123,106 @@ def stats(members, table: torch.Tensor, offset: int, n: int, mean=None, spread=N
     lib = load_library()
     with torch.cuda.device(dev):
         native.check(lib.skens_stats(ctypes.byref(d), native.stream(dev)), "skens_stats", lib)
+
+
+# ---- the products of one family of fields ------------------------------------------------------------------------------------------- #
+class ProductSet:
+    """The statistics of ONE family of fields on one grid, entry by entry: the raw channels, the derived fields, the regridded channels
+    or the aggregates of one window group (DESIGN.md 17 has the launch rule).  ``entries``: the saved leads, or the group's windows;
+    ``exceed`` / ``quantiles``: the tables of this family's fields; ``prefix``: what stands before the product in a file's model name
+    (``""``, ``"derived-"``, ``"regrid-"``, ``"agg{label}-"``); ``always``: the outputs every ``reduce`` computes, stored or not."""
+
+    def __init__(self, model_name, M, products, device, fields, lat, lon, entries, exceed, quantiles, keep_members, prefix="", always=()):
+        self.model_name, self.M, self.products, self.prefix, self.always = model_name, M, products, prefix, always
+        self.fields, self.lat, self.lon, self.exceed, self.quantiles = list(fields), np.asarray(lat), np.asarray(lon), exceed, quantiles
+        F, grid = len(self.fields), (len(self.lat), len(self.lon))
+        self.hw = grid[0] * grid[1]
+
+        def host(rows):
+            return np.empty((entries, rows, *grid), np.float32)
+
+        def dev(rows):
+            return torch.empty((rows, *grid), dtype=torch.float32, device=device)
+        self.host = {p: host(F) for p in products}
+        self.host_ex = {ch: host(len(v)) for ch, v in exceed.items()}
+        self.host_q = {ch: host(len(v)) for ch, v in quantiles.items()}
+        self.members = np.empty((M, entries, F, *grid), np.float32) if keep_members else None
+        self.dev = {p: dev(F) for p in dict.fromkeys((*products, *always))}
+        self.dev_ex = {ch: dev(len(v)) for ch, v in exceed.items()}
+        self.dev_q = {ch: dev(len(v)) for ch, v in quantiles.items()}
+
+    def reduce(self, states, table, slot) -> None:
+        """Entry ``slot`` from the M ``states`` of this family's fields: one launch over all fields for the products, one per exceed
+        channel and one per quantile channel, each result to the host, then the states themselves with ``keep_members``.
+        ``slot=None``: the ``always`` outputs only, left on the device (``dev``)."""
+        n = self.hw
+        out = {p: self.dev[p] for p in (*(self.products if slot is not None else ()), *self.always)}
+        if out:
+            stats(states, table, 0, len(self.fields) * n, **out)
+        if slot is None:
+            return
+        for p in self.products:
+            self.host[p][slot] = self.dev[p].cpu().numpy()
+        for ch, thr in self.exceed.items():
+            stats(states, table, self.fields.index(ch) * n, n, exceed=self.dev_ex[ch], thresholds=thr)
+            self.host_ex[ch][slot] = self.dev_ex[ch].cpu().numpy()
+        for ch, lev in self.quantiles.items():
+            stats(states, table, self.fields.index(ch) * n, n, quant=self.dev_q[ch], levels=lev)
+            self.host_q[ch][slot] = self.dev_q[ch].cpu().numpy()
+        if self.members is not None:
+            for m, st in enumerate(states):
+                self.members[m, slot] = st.cpu().numpy()
+
+    def save(self, first, times, start, source, cfg) -> list:
+        """One file per product with the entries ``first ..`` valid at ``times``, named from ``start`` to ``times[-1]``; returns the
+        paths.  zarr: one store per product under the forecast id, appended along time."""
+        from .common import save_forecast
+        from .labeled import DataArray
+        paths = []
+        for p in self.products:
+            da = DataArray(self.host[p][first:first + len(times)], ["time", "channel", "lat", "lon"],
+                           dict(time=times, channel=self.fields, lat=self.lat, lon=self.lon))
+            name = product_model_name(self.model_name, self.M, self.prefix + p)
+            pcfg = dict(cfg, forecast_id=f"{cfg['forecast_id']}/{name}") if (cfg.get("file_type") or "netcdf") == "zarr" else cfg
+            paths.append(save_forecast(da, name, start, times[-1], source, config=pcfg))
+        return paths
+
+    def fill(self, result, times, channels=None, window_start=None) -> None:
+        """The labelled arrays as attributes of ``result``: the products, ``exceedance``, ``quantile`` and, when kept, ``members``.
+        ``channels``: the selection on the channel dimension of products and members; ``window_start``: the coordinate that goes with
+        ``times`` when those are window ends."""
+        from .labeled import DataArray
+        coords = dict({} if window_start is None else dict(window_start=window_start), lat=self.lat, lon=self.lon)
+
+        def labelled(arr, dim, labels):
+            da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **coords))
+            return da.sel(channel=list(channels)) if channels and dim == "channel" else da
+        for p in self.products:
+            setattr(result, p, labelled(self.host[p], "channel", self.fields))
+        result.exceedance = {ch: labelled(self.host_ex[ch], "threshold", np.asarray(v, np.float32)) for ch, v in self.exceed.items()}
+        result.quantile = {ch: labelled(self.host_q[ch], "quantile", np.asarray(v, np.float64)) for ch, v in self.quantiles.items()}
+        if self.members is not None:
+            da = DataArray(self.members, ["member", "time", "channel", "lat", "lon"],
+                           dict(member=np.arange(self.M), time=times, channel=self.fields, **coords))
+            result.members = da.sel(channel=list(channels)) if channels else da
+
+
+def split_table(table, fields) -> tuple[dict, dict]:
+    """(the entries of the ``{field: values}`` table that name one of ``fields``, the other entries)."""
+    return {k: v for k, v in table.items() if k in fields}, {k: v for k, v in table.items() if k not in fields}
+
+
+def _stamped(maker, fid):
+    """``maker.result()`` with the forecast id on it."""
+    res = maker.result()
+    res.forecast_id = fid
+    return res
+
+
+def _save_result(res, cfg, paths) -> None:
+    """Write a result object under the forecast's output directory and note its path."""
+    from .common import OUTPUT_DIR
+    paths.append(res.save(cfg.get("output_dir") or OUTPUT_DIR))
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------- #
@@ -311,10 +414,9 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
     from . import noise
-    from .common import save_config_with_id, save_forecast
+    from .common import save_config_with_id
     from .datasource import get_initial_condition_for_model
     from .leads import forget_resident
-    from .labeled import DataArray
     model = gm.model
     products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
                                                   keep_members, events=events, neighbourhoods_km=neighbourhoods_km, scores=scores, points=points,
@@ -343,15 +445,13 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         aggregator = aggregate.LeadAggregator(names, model.grid.lat, model.grid.lon, M, aggregates, start_time, model.time_step,
                                               device=model.device, n_steps=n_steps, derived=list(derived or []))
         a_fields = [f for g in aggregator.plan.groups for f in g.fields]
-        a_exceed, a_quant = ({k: v for k, v in t.items() if k in a_fields} for t in (exceed, quantiles))
-        exceed, quantiles = ({k: v for k, v in t.items() if k not in a_fields} for t in (exceed, quantiles))
+        (a_exceed, exceed), (a_quant, quantiles) = split_table(exceed, a_fields), split_table(quantiles, a_fields)
     if events is not None:                                 # names of derived fields go to the derived scorer, as those of ``exceed`` do
         known = names + list(derived or []) + (a_fields if aggregator is not None else [])
         events, radii = event_request(events, neighbourhoods_km, dict(exceed, **a_exceed) if aggregator is not None else exceed, known, M, scores)
         if aggregator is not None:
-            a_events, a_radii = {k: v for k, v in events.items() if k in a_fields}, radii
-            events = {k: v for k, v in events.items() if k not in a_fields}
-        raw, der = ({k: v for k, v in events.items() if (k in names) == own} for own in (True, False))
+            (a_events, events), a_radii = split_table(events, a_fields), radii
+        raw, der = split_table(events, names)
         ev = dict(events=raw, neighbourhoods_km=radii) if raw else {}
         d_ev = dict(events=der, neighbourhoods_km=radii) if der else {}
     if scores:                                             # (refusals of the request come before anything touches the device)
@@ -375,8 +475,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, M, dnames, device=model.device, surface=derived_surface)
         # what every truth of these fields shares with the forecast: its thermodynamic columns, its kind of humidity and its surface mask
         thermal = dict(column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=derived_surface)
-        d_exceed, d_quant = ({k: v for k, v in t.items() if k in dnames} for t in (exceed, quantiles))
-        exceed, quantiles = ({k: v for k, v in t.items() if k not in dnames} for t in (exceed, quantiles))
+        (d_exceed, exceed), (d_quant, quantiles) = split_table(exceed, dnames), split_table(quantiles, dnames)
         if scores:
             adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None,
                                           **thermal)
@@ -391,7 +490,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                                                                        levels=deriver.plan.levels or None, **thermal)
             hook = aggregate.TruthAggregator(g.requests, model.grid.lat, model.grid.lon, start_time, model.time_step, device=model.device,
                                              inner=inner)
-            g_ev = {k: v for k, v in a_events.items() if k in g.fields}
+            g_ev = split_table(a_events, g.fields)[0]
             ascorers[g.label] = (hook, verify.LeadScorer(gm.model_name, g.fields, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology,
                                                          None, device=model.device, adapt=hook,
                                                          **(dict(events=g_ev, neighbourhoods_km=a_radii) if g_ev else {})))
@@ -399,7 +498,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if grid is not None:                                   # the same products on the target grid (skyrim_amd/regrid.py)
         from . import regrid
         regridder = regrid.LeadRegridder(names, model.grid.lat, model.grid.lon, M, grid, regrid_method, device=model.device)
-        grid_label = regrid.grid_label(grid)                # (``grid`` names the coordinates of the raw products further down)
+        grid_label = regrid.grid_label(grid)
         if scores:
             rscorer = verify.LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, M, scorer.truth.src, climatology, channels,
                                         device=model.device,
@@ -443,7 +542,6 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         raise ValueError(f"channel_std holds {std.numel()} values for {x0.shape[2]} input channels")
     cfg = save_config_with_id(save_config)
     fid = cfg["forecast_id"]
-    zarr = (cfg.get("file_type") or "netcdf") == "zarr"
 
     sigma_all = std                                        # (breeding normalises with every channel's own sigma)
     if plan.channel_mask is not None and plan.kind == "white":
@@ -478,50 +576,21 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         del xm
     breeding_growth = None if breeder is None else breeder.growth
     del x0, spherical, breeder, sigma_all                  # (with them the work buffers of one member's synthesis and of the cycle)
-    n_saved, C = len(saved), len(names)
-    host = {p: np.empty((n_saved, C, n_lat, n_lon), np.float32) for p in products}
-    host_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in exceed.items()}
-    host_q = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in quantiles.items()}
-    host_members = np.empty((M, n_saved, C, n_lat, n_lon), np.float32) if keep_members else None
-    dev_out = {p: torch.empty((C, n_lat, n_lon), dtype=torch.float32, device=dev) for p in set(products) | {"mean"}}
-    dev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in exceed.items()}
-    dev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in quantiles.items()}
     times, paths, source = [], [], gm.source_label
+    lat, lon, n_saved = model.grid.lat, model.grid.lon, len(saved)
+    family = functools.partial(ProductSet, gm.model_name, M, products, dev)
+    raw_set = family(names, lat, lon, n_saved, exceed, quantiles, keep_members, always=("mean",))
+    derived_set = regrid_set = None
+    agg_sets = {}                                          # {window label: (its set, the ends of its closed windows, their starts)}
     if deriver is not None:
-        D = len(dnames)
-        dhost = {p: np.empty((n_saved, D, n_lat, n_lon), np.float32) for p in products}
-        dhost_ex = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in d_exceed.items()}
-        dhost_q = {ch: np.empty((n_saved, len(v), n_lat, n_lon), np.float32) for ch, v in d_quant.items()}
-        dhost_members = np.empty((M, n_saved, D, n_lat, n_lon), np.float32) if keep_members else None
-        ddev_out = {p: torch.empty((D, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products}
-        ddev_ex = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_exceed.items()}
-        ddev_q = {ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in d_quant.items()}
+        derived_set = family(dnames, lat, lon, n_saved, d_exceed, d_quant, keep_members, "derived-")
     if aggregator is not None:                             # per window group: one entry per complete window
-        ahost = {}
         for g in aggregator.plan.groups:
-            nf, nw = len(g.fields), g.n_windows
-            ex = {ch: v for ch, v in a_exceed.items() if ch in g.fields}
-            qu = {ch: v for ch, v in a_quant.items() if ch in g.fields}
-            ahost[g.label] = dict(
-                ends=[], starts=[], ex=ex, qu=qu,
-                host={p: np.empty((nw, nf, n_lat, n_lon), np.float32) for p in products},
-                host_ex={ch: np.empty((nw, len(v), n_lat, n_lon), np.float32) for ch, v in ex.items()},
-                host_q={ch: np.empty((nw, len(v), n_lat, n_lon), np.float32) for ch, v in qu.items()},
-                members=np.empty((M, nw, nf, n_lat, n_lon), np.float32) if keep_members else None,
-                dev={p: torch.empty((nf, n_lat, n_lon), dtype=torch.float32, device=dev) for p in products},
-                dev_ex={ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in ex.items()},
-                dev_q={ch: torch.empty((len(v), n_lat, n_lon), dtype=torch.float32, device=dev) for ch, v in qu.items()})
+            own = [split_table(t, g.fields)[0] for t in (a_exceed, a_quant)]
+            agg_sets[g.label] = (family(g.fields, lat, lon, g.n_windows, *own, keep_members, f"agg{g.label}-"), [], [])
         agg_derived = any(r.channel in (derived or []) for r in aggregator.plan.requests)
     if regridder is not None:
-        r_lat, r_lon = regridder.lat_out.size, regridder.lon_out.size
-        rhw = r_lat * r_lon
-        rhost = {p: np.empty((n_saved, C, r_lat, r_lon), np.float32) for p in products}
-        rhost_ex = {ch: np.empty((n_saved, len(v), r_lat, r_lon), np.float32) for ch, v in exceed.items()}
-        rhost_q = {ch: np.empty((n_saved, len(v), r_lat, r_lon), np.float32) for ch, v in quantiles.items()}
-        rhost_members = np.empty((M, n_saved, C, r_lat, r_lon), np.float32) if keep_regridded else None
-        rdev_out = {p: torch.empty((C, r_lat, r_lon), dtype=torch.float32, device=dev) for p in products}
-        rdev_ex = {ch: torch.empty((len(v), r_lat, r_lon), dtype=torch.float32, device=dev) for ch, v in exceed.items()}
-        rdev_q = {ch: torch.empty((len(v), r_lat, r_lon), dtype=torch.float32, device=dev) for ch, v in quantiles.items()}
+        regrid_set = family(names, regridder.lat_out, regridder.lon_out, n_saved, exceed, quantiles, keep_regridded, "regrid-")
     try:
         for k in range(n_steps + 1):
             states, time = [], None
@@ -543,12 +612,13 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                     states.append(current[m][0, 0])
             table = member_table(states)
             keep = k in saved
-            want = {p: dev_out[p] for p in (products if keep else ())}
-            want["mean"] = dev_out["mean"]                 # every step: a non-finite member makes the mean non-finite, one flag to read
-            stats(states, table, 0, C * hw, **want)
-            if not bool(torch.isfinite(dev_out["mean"]).all().item()):
-                bad = [m for m, s in enumerate(states) if not bool(torch.isfinite(s).all().item())]
+            s = saved.index(k) if keep else None
+            raw_set.reduce(states, table, s)               # every step: a non-finite member makes the mean non-finite, one flag to read
+            if not bool(torch.isfinite(raw_set.dev["mean"]).all().item()):
+                bad = [m for m, st in enumerate(states) if not bool(torch.isfinite(st).all().item())]
                 raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {k}")
+            if keep:
+                times.append(time)
             if scorer is not None:
                 scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
             if tracker is not None:
@@ -561,20 +631,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 if dspectrist is not None and keep:        # the derived planes are (D, H, W) states with a member table of their own
                     dspectrist.add(time, dstates, dtable, dscorer.truth_state() if dscorer is not None else None)
                 if keep:
-                    s = saved.index(k)
-                    if products:
-                        stats(dstates, dtable, 0, D * hw, **{p: ddev_out[p] for p in products})
-                    for p in products:
-                        dhost[p][s] = ddev_out[p].cpu().numpy()
-                    for ch, thr in d_exceed.items():
-                        stats(dstates, dtable, dnames.index(ch) * hw, hw, exceed=ddev_ex[ch], thresholds=thr)
-                        dhost_ex[ch][s] = ddev_ex[ch].cpu().numpy()
-                    for ch, lev in d_quant.items():
-                        stats(dstates, dtable, dnames.index(ch) * hw, hw, quant=ddev_q[ch], levels=lev)
-                        dhost_q[ch][s] = ddev_q[ch].cpu().numpy()
-                    if keep_members:
-                        for m, st in enumerate(dstates):
-                            dhost_members[m, s] = st.cpu().numpy()
+                    derived_set.reduce(dstates, dtable, s)
             if scenarist is not None and keep:             # one Gram launch, its M' x M' doubles to the host, cluster means, EOF patterns
                 scenarist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
             if spectrist is not None and keep:             # one launch, nc x nb x kinds x K doubles to the host
@@ -583,90 +640,29 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 pointer.add(time, states, table, (dstates, dtable) if pointer.needs_derived else None)
             if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
                 for c in aggregator.add(k, time, states, table, (dstates, dtable) if fold_derived else None):
-                    a, w, nf = ahost[c.label], c.window, len(c.fields)
-                    a["ends"].append(c.end)                # windows close independently of ``save_every``
-                    a["starts"].append(c.start)
-                    if products:
-                        stats(c.states, c.table, 0, nf * hw, **{p: a["dev"][p] for p in products})
-                    for p in products:
-                        a["host"][p][w] = a["dev"][p].cpu().numpy()
-                    for ch, thr in a["ex"].items():
-                        stats(c.states, c.table, c.fields.index(ch) * hw, hw, exceed=a["dev_ex"][ch], thresholds=thr)
-                        a["host_ex"][ch][w] = a["dev_ex"][ch].cpu().numpy()
-                    for ch, lev in a["qu"].items():
-                        stats(c.states, c.table, c.fields.index(ch) * hw, hw, quant=a["dev_q"][ch], levels=lev)
-                        a["host_q"][ch][w] = a["dev_q"][ch].cpu().numpy()
-                    if keep_members:
-                        for m, st in enumerate(c.states):
-                            a["members"][m, w] = st.cpu().numpy()
+                    agg_set, ends, starts = agg_sets[c.label]
+                    ends.append(c.end)                     # windows close independently of ``save_every``
+                    starts.append(c.start)
+                    agg_set.reduce(c.states, c.table, c.window)
                     if c.label in apointers:
                         apointers[c.label].add(c.end, c.states, c.table)
                     if c.label in ascorers:
                         hook, asc = ascorers[c.label]
                         hook.window(c.times)               # the truth is aggregated over the same valid times
                         asc.add(c.end, c.states, c.table)
-                    if save:
-                        for p in products:
-                            da = DataArray(a["host"][p][w:w + 1], ["time", "channel", "lat", "lon"],
-                                           dict(time=[c.end], channel=c.fields, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
-                            name = product_model_name(gm.model_name, M, f"agg{c.label}-{p}")
-                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
-                            paths.append(save_forecast(da, name, c.start, c.end, gm.source_label, config=pcfg))
+                    if save:                               # one file per closed window, without the ``window_start`` coordinate
+                        paths += agg_set.save(c.window, [c.end], c.start, gm.source_label, cfg)
             if regridder is not None and (keep or rscorer is not None):
                 rstates, rtable = regridder.add(states, table)    # ONE launch: every channel of every member on the target grid
                 if rscorer is not None:
                     rscorer.add(time, rstates, rtable)
                 if keep:
-                    s = saved.index(k)
-                    if products:
-                        stats(rstates, rtable, 0, C * rhw, **{p: rdev_out[p] for p in products})
-                    for p in products:
-                        rhost[p][s] = rdev_out[p].cpu().numpy()
-                    for ch, thr in exceed.items():
-                        stats(rstates, rtable, names.index(ch) * rhw, rhw, exceed=rdev_ex[ch], thresholds=thr)
-                        rhost_ex[ch][s] = rdev_ex[ch].cpu().numpy()
-                    for ch, lev in quantiles.items():
-                        stats(rstates, rtable, names.index(ch) * rhw, rhw, quant=rdev_q[ch], levels=lev)
-                        rhost_q[ch][s] = rdev_q[ch].cpu().numpy()
-                    if keep_regridded:
-                        for m, st in enumerate(rstates):
-                            rhost_members[m, s] = st.cpu().numpy()
-            if keep:
-                s = saved.index(k)
-                times.append(time)
-                for ch, thr in exceed.items():
-                    stats(states, table, names.index(ch) * hw, hw, exceed=dev_ex[ch], thresholds=thr)
-                    host_ex[ch][s] = dev_ex[ch].cpu().numpy()
-                for ch, lev in quantiles.items():
-                    stats(states, table, names.index(ch) * hw, hw, quant=dev_q[ch], levels=lev)
-                    host_q[ch][s] = dev_q[ch].cpu().numpy()
-                for p in products:
-                    host[p][s] = dev_out[p].cpu().numpy()
-                if keep_members:
-                    for m, st in enumerate(states):
-                        host_members[m, s] = st.cpu().numpy()
-                if save and s >= 1:
-                    for p in products:
-                        da = DataArray(host[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
-                                       dict(time=times[s - 1:s + 1], channel=names, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
-                        name = product_model_name(gm.model_name, M, p)
-                        pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg      # one zarr store per product, appended along time
-                        paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
-                    if deriver is not None:
-                        for p in products:
-                            da = DataArray(dhost[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
-                                           dict(time=times[s - 1:s + 1], channel=dnames, lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon)))
-                            name = product_model_name(gm.model_name, M, f"derived-{p}")
-                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
-                            paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
-                    if regridder is not None:
-                        for p in products:
-                            da = DataArray(rhost[p][s - 1:s + 1], ["time", "channel", "lat", "lon"],
-                                           dict(time=times[s - 1:s + 1], channel=names, lat=regridder.lat_out, lon=regridder.lon_out))
-                            name = product_model_name(gm.model_name, M, f"regrid-{p}")
-                            pcfg = dict(cfg, forecast_id=f"{fid}/{name}") if zarr else cfg
-                            paths.append(save_forecast(da, name, times[s - 1], times[s], source, config=pcfg))
-                    source = "file"
+                    regrid_set.reduce(rstates, rtable, s)
+            if keep and save and s >= 1:                   # files of two entries: the step saved before and this one
+                for family_set in (raw_set, derived_set, regrid_set):
+                    if family_set is not None:
+                        paths += family_set.save(s - 1, times[s - 1:s + 1], times[s - 1], source, cfg)
+                source = "file"
             del states, table
     finally:
         for loop in loops:
@@ -676,81 +672,42 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 pass                                       # every delivered step was checked above, by member
         forget_resident(model)
 
-    grid = dict(lat=np.asarray(model.grid.lat), lon=np.asarray(model.grid.lon))
-
-    def labelled(arr, dim, labels):
-        da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **grid))
-        return da.sel(channel=list(channels)) if channels and dim == "channel" else da
-
     ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=plan.kind,
                            length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None,
                            breeding=None if bplan is None else bplan.as_dict(), breeding_growth=breeding_growth,
                            stochastic=None if splan is None else splan.as_dict())
     if scorer is not None:
-        ens.scores = scorer.result()
-        ens.scores.forecast_id = fid
+        ens.scores = _stamped(scorer, fid)
         if save:
-            from .common import OUTPUT_DIR
-            paths.append(ens.scores.save(cfg.get("output_dir") or OUTPUT_DIR))
+            _save_result(ens.scores, cfg, paths)
     if tracker is not None:
-        ens.tracks = tracker.result()
-        ens.tracks.forecast_id = fid
+        ens.tracks = _stamped(tracker, fid)
         if save:
-            from .common import OUTPUT_DIR
-            paths.append(ens.tracks.save(cfg.get("output_dir") or OUTPUT_DIR))
-    for p in products:
-        setattr(ens, p, labelled(host[p], "channel", names))
+            _save_result(ens.tracks, cfg, paths)
+    raw_set.fill(ens, times, channels)
     if deriver is not None:
-        def dlabelled(arr, dim, labels):
-            return DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **grid))
-        ens.derived = deriving.DerivedProducts(dnames, **{p: dlabelled(dhost[p], "channel", dnames) for p in products})
-        ens.derived.exceedance = {ch: dlabelled(dhost_ex[ch], "threshold", np.asarray(d_exceed[ch], np.float32)) for ch in d_exceed}
-        ens.derived.quantile = {ch: dlabelled(dhost_q[ch], "quantile", np.asarray(d_quant[ch], np.float64)) for ch in d_quant}
-        if keep_members:
-            ens.derived.members = DataArray(dhost_members, ["member", "time", "channel", "lat", "lon"],
-                                            dict(member=np.arange(M), time=times, channel=dnames, **grid))
+        ens.derived = deriving.DerivedProducts(dnames)
+        derived_set.fill(ens.derived, times)
         if dscorer is not None:
-            ens.derived.scores = dscorer.result()
-            ens.derived.scores.forecast_id = fid
+            ens.derived.scores = _stamped(dscorer, fid)
             ens.derived.dropped = dict(adapt.dropped)
     if regridder is not None:
-        rgrid = dict(lat=regridder.lat_out, lon=regridder.lon_out)
-
-        def rlabelled(arr, dim, labels):
-            da = DataArray(arr, ["time", dim, "lat", "lon"], dict(time=times, **{dim: labels}, **rgrid))
-            return da.sel(channel=list(channels)) if channels and dim == "channel" else da
-        ens.regridded = regrid.RegriddedProducts(rgrid["lat"], rgrid["lon"], regrid_method,
-                                                 **{p: rlabelled(rhost[p], "channel", names) for p in products})
-        ens.regridded.exceedance = {ch: rlabelled(rhost_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
-        ens.regridded.quantile = {ch: rlabelled(rhost_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
-        if keep_regridded:
-            ens.regridded.members = DataArray(rhost_members, ["member", "time", "channel", "lat", "lon"],
-                                              dict(member=np.arange(M), time=times, channel=names, **rgrid))
-            if channels:
-                ens.regridded.members = ens.regridded.members.sel(channel=list(channels))
+        ens.regridded = regrid.RegriddedProducts(regridder.lat_out, regridder.lon_out, regrid_method)
+        regrid_set.fill(ens.regridded, times, channels)
         if rscorer is not None:
-            ens.regridded.scores = rscorer.result()
-            ens.regridded.scores.forecast_id = fid
+            ens.regridded.scores = _stamped(rscorer, fid)
             ens.regridded.scores.grid = grid_label
     if aggregator is not None:
         for g in aggregator.plan.groups:
-            a = ahost[g.label]
-
-            def alabelled(arr, dim, labels):
-                return DataArray(arr, ["time", dim, "lat", "lon"], dict(time=a["ends"], **{dim: labels}, window_start=a["starts"], **grid))
-            prod = aggregate.AggregatedProducts(g.label, list(g.fields), **{p: alabelled(a["host"][p], "channel", g.fields) for p in products})
-            prod.exceedance = {ch: alabelled(a["host_ex"][ch], "threshold", np.asarray(a["ex"][ch], np.float32)) for ch in a["ex"]}
-            prod.quantile = {ch: alabelled(a["host_q"][ch], "quantile", np.asarray(a["qu"][ch], np.float64)) for ch in a["qu"]}
+            agg_set, ends, starts = agg_sets[g.label]
+            prod = aggregate.AggregatedProducts(g.label, list(g.fields))
+            agg_set.fill(prod, ends, window_start=starts)
             prod.incomplete = aggregator.incomplete.get(g.label)
             if g.label in apointers:
-                prod.points = apointers[g.label].result(f"{gm.model_name}-ens{M}-agg{g.label}", fid, window_start=a["starts"])
-            if keep_members:
-                prod.members = DataArray(a["members"], ["member", "time", "channel", "lat", "lon"],
-                                         dict(member=np.arange(M), time=a["ends"], channel=g.fields, window_start=a["starts"], **grid))
+                prod.points = apointers[g.label].result(f"{gm.model_name}-ens{M}-agg{g.label}", fid, window_start=starts)
             if g.label in ascorers:
                 hook, asc = ascorers[g.label]
-                prod.scores = asc.result()
-                prod.scores.forecast_id = fid
+                prod.scores = _stamped(asc, fid)
                 prod.dropped = dict(hook.dropped)
             ens.aggregated[g.label] = prod
     if scenarist is not None:
@@ -761,13 +718,5 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if pointer is not None:
         ens.points = pointer.result(f"{gm.model_name}-ens{M}", fid)
         if save:
-            from .common import OUTPUT_DIR
-            paths.append(ens.points.save(cfg.get("output_dir") or OUTPUT_DIR))
-    ens.exceedance = {ch: labelled(host_ex[ch], "threshold", np.asarray(exceed[ch], np.float32)) for ch in exceed}
-    ens.quantile = {ch: labelled(host_q[ch], "quantile", np.asarray(quantiles[ch], np.float64)) for ch in quantiles}
-    if keep_members:
-        ens.members = DataArray(host_members, ["member", "time", "channel", "lat", "lon"],
-                                dict(member=np.arange(M), time=times, channel=names, **grid))
-        if channels:
-            ens.members = ens.members.sel(channel=list(channels))
+            _save_result(ens.points, cfg, paths)
     return ens

@@ -165,6 +165,150 @@ def test_refusals():
         GraphcastModel.ensemble_forecast(object.__new__(GraphcastModel), T0)
 
 
+# ---- 4. the product set: the host half of every family of products, on torch-CPU tensors ---------------------------------------------- #
+FIELDS, GRID_LAT, GRID_LON = ["a", "b"], np.linspace(30.0, -30.0, 4), np.arange(8) * 45.0
+TIMES = [T0 + k * datetime.timedelta(hours=6) for k in range(3)]
+EXCEED, QUANT = {"b": [0.0, 0.5]}, {"a": [0.5]}
+
+
+@pytest.fixture
+def launches(monkeypatch):
+    """``ensemble.stats`` restated on torch-CPU tensors with tests/_ens_reference.stats; the list of (offset, n, outputs) it was asked for."""
+    calls = []
+
+    def stats(members, table, offset, n, mean=None, spread=None, min=None, max=None, exceed=None, thresholds=(), quant=None, levels=()):
+        r = R.stats(np.stack([m.reshape(-1)[offset:offset + n].numpy() for m in members]), thresholds, levels)
+        r["quant"] = np.stack([q for q, _ in r["quant"]]) if levels else None
+        out = dict(mean=mean, spread=spread, min=min, max=max, exceed=exceed, quant=quant)
+        given = sorted(k for k, t in out.items() if t is not None)
+        assert given, "a stats call with zero outputs"
+        for k in given:
+            out[k].reshape(-1).copy_(torch.from_numpy(np.asarray(r[k], np.float32).reshape(-1)))
+        calls.append((offset, n, given))
+    monkeypatch.setattr(E, "stats", stats)
+    return calls
+
+
+def _states(entry):
+    return list(torch.from_numpy(np.random.default_rng(entry).normal(size=(3, 2, 4, 8)).astype(np.float32)))
+
+
+def _set(products=("mean", "max"), exceed=EXCEED, quantiles=QUANT, keep_members=True, prefix="", always=()):
+    ps = E.ProductSet("toy", 3, products, "cpu", FIELDS, GRID_LAT, GRID_LON, 3, exceed, quantiles, keep_members, prefix, always)
+    for arr in (*ps.host.values(), *ps.host_ex.values(), *ps.host_q.values(), *([] if ps.members is None else [ps.members])):
+        arr[:] = -7.0                                          # a sentinel: what no reduce has written
+    return ps
+
+
+def _filled(**kw):
+    ps = _set(**kw)
+    for k in (2, 0, 1):
+        ps.reduce(_states(k), None, k)
+    return ps
+
+
+def _when(values):
+    return [np.datetime64(t, "s") for t in values]
+
+
+def test_product_set_reduces_into_its_slot(launches):
+    ps = _set(always=("mean",))
+    ps.reduce(_states(5), None, None)                          # the every-step launch: the always-outputs, nothing stored
+    assert launches == [(0, 64, ["mean"])]
+    assert all(np.all(a == -7.0) for a in (*ps.host.values(), *ps.host_ex.values(), *ps.host_q.values(), ps.members))
+    assert np.array_equal(ps.dev["mean"].numpy().reshape(-1), R.stats(torch.stack(_states(5)).reshape(3, -1).numpy())["mean"].astype(np.float32))
+    del launches[:]
+    for k in (2, 0, 1):                                        # any order: an entry goes where ``slot`` says
+        ps.reduce(_states(k), None, k)
+    assert launches == [(0, 64, ["max", "mean"]), (32, 32, ["exceed"]), (0, 32, ["quant"])] * 3
+    for k in range(3):
+        x = torch.stack(_states(k)).numpy()
+        ref = R.stats(x.reshape(3, -1))
+        assert np.array_equal(ps.host["mean"][k].reshape(-1), ref["mean"].astype(np.float32))
+        assert np.array_equal(ps.host["max"][k].reshape(-1), ref["max"])
+        assert np.array_equal(ps.host_ex["b"][k].reshape(2, -1), R.stats(x[:, 1].reshape(3, -1), thresholds=EXCEED["b"])["exceed"])
+        assert np.array_equal(ps.host_q["a"][k].reshape(-1), R.stats(x[:, 0].reshape(3, -1), levels=QUANT["a"])["quant"][0][0].astype(np.float32))
+        assert np.array_equal(ps.members[:, k], x)
+    assert ps.host["mean"].shape == (3, 2, 4, 8) and ps.host_ex["b"].shape == (3, 2, 4, 8) and ps.host_q["a"].shape == (3, 1, 4, 8)
+    assert ps.members.shape == (3, 3, 2, 4, 8) and sorted(ps.dev) == ["max", "mean"]
+
+
+def test_product_set_without_products_launches_no_empty_call(launches):
+    ps = _set(products=(), quantiles={}, keep_members=False)
+    ps.reduce(_states(0), None, None)
+    assert launches == [] and ps.members is None and ps.host == {} and ps.dev == {}
+    ps.reduce(_states(0), None, 1)
+    assert launches == [(32, 32, ["exceed"])] and np.all(ps.host_ex["b"][0] == -7.0) and not np.any(ps.host_ex["b"][1] == -7.0)
+
+
+def test_product_set_fills_a_result_with_labelled_arrays(launches):
+    from skyrim_amd.aggregate import AggregatedProducts
+    ps = _filled()
+    for channels, picked in ((None, [0, 1]), (["b"], [1])):    # raw and regridded select ``channels``; derived and aggregated pass none
+        ens = E.EnsembleForecast("toy", 3, 0, 1e-3)
+        ps.fill(ens, TIMES, channels)
+        assert ens.spread is None and ens.min is None
+        for p in ("mean", "max"):
+            da = getattr(ens, p)
+            assert da.dims == ("time", "channel", "lat", "lon") and list(da._coords) == ["time", "channel", "lat", "lon"]
+            assert da.channel.values.tolist() == [FIELDS[i] for i in picked] and np.array_equal(da.values, ps.host[p][:, picked])
+            assert _when(da.time.values) == _when(TIMES) and np.array_equal(da.lat.values, GRID_LAT) and np.array_equal(da.lon.values, GRID_LON)
+        ex, qu = ens.exceedance["b"], ens.quantile["a"]
+        assert list(ens.exceedance) == ["b"] and ex.dims == ("time", "threshold", "lat", "lon") and np.array_equal(ex.values, ps.host_ex["b"])
+        assert ex.threshold.values.dtype == np.float32 and ex.threshold.values.tolist() == [0.0, 0.5] and _when(ex.time.values) == _when(TIMES)
+        assert list(ens.quantile) == ["a"] and qu.dims == ("time", "quantile", "lat", "lon") and np.array_equal(qu.values, ps.host_q["a"])
+        assert qu._coords["quantile"].dtype == np.float64 and qu._coords["quantile"].tolist() == [0.5]
+        mem = ens.members
+        assert mem.dims == ("member", "time", "channel", "lat", "lon") and list(mem._coords) == ["member", "time", "channel", "lat", "lon"]
+        assert mem.member.values.tolist() == [0, 1, 2] and mem.channel.values.tolist() == [FIELDS[i] for i in picked]
+        assert np.array_equal(mem.values, ps.members[:, :, picked]) and _when(mem.time.values) == _when(TIMES)
+    # a window group: the time axis holds the window ends, ``window_start`` goes with it on every array
+    ends, starts = TIMES, [t - datetime.timedelta(hours=12) for t in TIMES]
+    prod = AggregatedProducts("12h", list(FIELDS))
+    ps.fill(prod, ends, window_start=starts)
+    for da in (prod.mean, prod.max, prod.exceedance["b"], prod.quantile["a"], prod.members):
+        assert _when(da.time.values) == _when(ends) and _when(da._coords["window_start"]) == _when(starts)
+        assert list(da._coords)[-3:] == ["window_start", "lat", "lon"]
+    assert prod.mean.channel.values.tolist() == FIELDS and np.array_equal(prod.members.values, ps.members)
+    # members only when they were kept
+    ens = E.EnsembleForecast("toy", 3, 0, 1e-3)
+    _filled(keep_members=False).fill(ens, TIMES)
+    assert ens.members is None and ens.mean is not None
+
+
+def test_product_set_saves_one_file_per_product(launches, monkeypatch):
+    import skyrim_amd.common as common
+    saved = []
+
+    def save_forecast(da, name, start, end, source, config=None):
+        saved.append((da, name, start, end, source, config))
+        return f"{config['forecast_id']}:{name}"
+    monkeypatch.setattr(common, "save_forecast", save_forecast)
+    nc, zarr = {"forecast_id": "F", "output_dir": "out"}, {"forecast_id": "F", "output_dir": "out", "file_type": "zarr"}
+    # the families of saved leads: two entries per file, the source handed in
+    for prefix in ("", "derived-", "regrid-"):
+        ps = _filled(prefix=prefix)
+        del saved[:]
+        assert ps.save(1, TIMES[1:3], TIMES[1], "gfs", nc) == [f"F:toy-ens3-{prefix}mean", f"F:toy-ens3-{prefix}max"]
+        assert ps.save(1, TIMES[1:3], TIMES[1], "file", zarr) == [f"F/toy-ens3-{prefix}{p}:toy-ens3-{prefix}{p}" for p in ("mean", "max")]
+        for n, (da, name, start, end, source, config) in enumerate(saved):
+            p = ("mean", "max")[n % 2]
+            assert name == f"toy-ens3-{prefix}{p}" and (start, end) == (TIMES[1], TIMES[2]) and source == ("gfs", "file")[n // 2]
+            assert da.dims == ("time", "channel", "lat", "lon") and list(da._coords) == ["time", "channel", "lat", "lon"]
+            assert _when(da.time.values) == _when(TIMES[1:3]) and da.channel.values.tolist() == FIELDS
+            assert np.array_equal(da.values, ps.host[p][1:3]) and np.array_equal(da.lat.values, GRID_LAT)
+            assert config is nc if n < 2 else config == dict(zarr, forecast_id=f"F/{name}")      # zarr: one store per product
+    # a window group: one entry per file, from the window's start to its end, no ``window_start`` coordinate
+    ps = _filled(prefix="agg12h-")
+    del saved[:]
+    start = TIMES[2] - datetime.timedelta(hours=12)
+    assert ps.save(2, [TIMES[2]], start, "gfs", nc) == ["F:toy-ens3-agg12h-mean", "F:toy-ens3-agg12h-max"]
+    for (da, name, *when, config), p in zip(saved, ("mean", "max")):
+        assert when == [start, TIMES[2], "gfs"] and list(da._coords) == ["time", "channel", "lat", "lon"]
+        assert da.shape == (1, 2, 4, 8) and np.array_equal(da.values, ps.host[p][2:3]) and _when(da.time.values) == _when([TIMES[2]])
+    assert _filled(products=()).save(1, TIMES[1:3], TIMES[1], "gfs", nc) == [] and len(saved) == 2
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

@@ -157,6 +157,70 @@ def test_save_writes_product_files(pangu, tmp_path, file_type):
         assert np.array_equal(back.isel(time=-1).values, ens.mean.values[2])
 
 
+def _stats_launches(monkeypatch, gm, **kw):
+    """[[(offset, n, names of the outputs given)] per step] of one ``ensemble_forecast``: every ``skyrim_amd.ensemble.stats`` call, still
+    made.  A step opens where the driver builds the member table of the raw states."""
+    from skyrim_amd import ensemble as E
+    real_stats, real_table = E.stats, E.member_table
+    state = len(gm.model.out_channel_names) * len(gm.model.grid.lat) * len(gm.model.grid.lon)
+    steps = []
+
+    def table(members):
+        if len(members) == kw["n_members"] and members[0].numel() == state:
+            steps.append([])
+        return real_table(members)
+
+    def spy(members, table, offset, n, mean=None, spread=None, min=None, max=None, exceed=None, thresholds=(), quant=None, levels=()):
+        out = dict(mean=mean, spread=spread, min=min, max=max, exceed=exceed, quant=quant)
+        steps[-1].append((offset, n, tuple(sorted(k for k, v in out.items() if v is not None))))
+        return real_stats(members, table, offset, n, thresholds=thresholds, levels=levels, **out)
+    monkeypatch.setattr(E, "member_table", table)
+    monkeypatch.setattr(E, "stats", spy)
+    gm.ensemble_forecast(T0, **kw)
+    monkeypatch.undo()
+    return steps
+
+
+def _expected_launches(n_steps, products, raw, stored):
+    """DESIGN.md 17, the launch rule.  Every step: one all-field launch for the raw set ``raw`` = (fields, hw, stored steps, exceed,
+    quantiles); it carries the mean and, at a stored step, the products.  Per stored entry of each set of ``stored`` (the same tuples):
+    one all-field launch when ``products`` is not empty, one per exceed channel and one per quantile channel; the raw set's all-field
+    launch is the one it has anyway."""
+    steps = []
+    for k in range(n_steps + 1):
+        fields, hw, at, _, _ = raw
+        step = [(0, len(fields) * hw, tuple(sorted(set(products if k in at else ()) | {"mean"})))]
+        for own, (fields, hw, at, exceed, quantiles) in enumerate([raw] + list(stored)):
+            if k not in at:
+                continue
+            if products and own:
+                step.append((0, len(fields) * hw, tuple(sorted(products))))
+            step += [(fields.index(ch) * hw, hw, ("exceed",)) for ch in exceed] + [(fields.index(ch) * hw, hw, ("quant",)) for ch in quantiles]
+        steps.append(sorted(step))
+    return steps
+
+
+def test_stats_launches_per_step(pangu, monkeypatch):
+    """How many ``skens_stats`` launches a lead time costs, pinned as multisets per step: 4 steps, every second one stored, a 12-hour
+    window that closes at steps 2 and 4."""
+    names = list(pangu.model.out_channel_names)
+    hw, rhw = 49 * 192, 13 * 24
+    kw = dict(n_steps=4, n_members=3, save_every=2, products=("mean", "spread"))
+    ex, qu = {"t2m": [280.0]}, {"msl": [0.5]}
+    saved, closes = (0, 2, 4), (2, 4)
+    cases = {
+        "A": (dict(kw, derived=["ws10m"], aggregates=["t2m:max:12h"], exceed=dict(ex, ws10m=[8.0], t2m_max_12h=[285.0]), quantiles=qu),
+              [(["ws10m"], hw, saved, ["ws10m"], []), (["t2m_max_12h"], hw, closes, ["t2m_max_12h"], [])]),
+        "B": (dict(kw, grid="15deg", exceed=ex, quantiles=qu), [(names, rhw, saved, list(ex), list(qu))]),
+        "C": (dict(kw, products=(), exceed=ex), []),
+    }
+    for case, (args, stored) in cases.items():
+        got = _stats_launches(monkeypatch, pangu, **args)
+        raw = (names, hw, saved, list(args["exceed"].keys() & set(names)), list(args.get("quantiles", {})))
+        want = _expected_launches(4, args["products"], raw, stored)
+        assert [sorted(s) for s in got] == want, case
+
+
 def test_ensemble_command_line(tmp_path):
     from click.testing import CliRunner
     from skyrim_amd.ensemble_cli import ensemble
