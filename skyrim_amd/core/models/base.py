@@ -119,7 +119,8 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          scenarios: dict | None = None, spectra: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
+                          scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None,
+                          breeding: dict | None = None, stochastic: dict | None = None,
                           aggregates: List[str] | None = None, derived_surface=None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
@@ -194,7 +195,13 @@ class GlobalModel:
         tropics, sh_mid, globe) and zonal wavenumber the power of the members, of their mean and of their spread and, with
         ``scores=True``, of the truth and of the errors of the mean and of the members.  Raw channels and fields of ``derived`` on the model's own grid; the
         number of longitudes must be 2^a 3^b 5^c.  The ``spectra.Spectra`` land in ``EnsembleForecast.spectra``.  ``spectra=None``
-        launches nothing."""
+        launches nothing.
+        ``objects={"ivt": {"above": [250.0], "min_area_km2": 2e5, "min_length_km": 2000.0, "min_elongation": 2.0}, "t2m": {"below":
+        [253.15]}, "connectivity": 8, "min_pixels": 4, "capacity": 1024}`` finds, at each saved lead time and in every member, the contiguous
+        regions where a raw channel or a field of ``derived`` is beyond a threshold (skyrim_amd/objects.py): labelled and
+        measured on the device, filtered on the host, with the fraction of members whose kept object covers each point; with
+        ``scores=True`` the truth goes through the same kernels and ``Objects.verify()`` compares.  The ``objects.Objects`` land in
+        ``EnsembleForecast.objects``.  ``objects=None`` launches nothing."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -217,6 +224,8 @@ class GlobalModel:
             extra["stochastic"] = stochastic
         if spectra is not None:
             extra["spectra"] = spectra
+        if objects is not None:
+            extra["objects"] = objects
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -232,6 +241,20 @@ class GlobalModel:
         (DLWP) is refused with ValueError before the device is touched."""
         from ... import tracks
         return tracks.track_model(self, start_time, n_steps=n_steps, config=config, save=save, save_config=save_config)
+
+    def object_forecast(self, start_time: datetime.datetime, n_steps: int = 4, objects: dict | None = None, derived: List[str] | None = None,
+                        truth=None, save: bool = False, save_config: dict | None = None):
+        """Weather objects of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/objects.py): the
+        contiguous regions where a channel, or a field of ``derived``, is at or above / at or below a threshold -- ``objects={"ivt":
+        {"above": [250.0], "min_area_km2": 2e5, "min_length_km": 2000.0, "min_elongation": 2.0}, "t2m": {"below": [253.15]},
+        "connectivity": 8, "min_pixels": 4, "capacity": 1024}``.  The model's TimeLoop is advanced and every state is labelled and measured
+        where it lies in HBM (with a global longitude circle an object may cross the date line; rows are not joined across the poles); only
+        128-byte records and one count plane per threshold cross to the host.  ``truth`` (the forms of ``verify``): its objects are found
+        by the same kernels and ``Objects.verify()`` matches them.  Returns ``objects.Objects``; ``save=True`` writes
+        ``{model}-objects.json`` and the count planes beside it.  A request that cannot be served is refused with ValueError before the
+        device is touched."""
+        from ... import objects as objecting
+        return objecting.objects_model(self, start_time, n_steps, objects, derived=derived, truth=truth, save=save, save_config=save_config)
 
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields: List[str] = (), save: bool = False,
                       save_config: dict | None = None, derived_surface=None):

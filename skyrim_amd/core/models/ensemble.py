@@ -120,6 +120,10 @@ class GlobalEnsemble:
         raise ValueError(f"track_cyclones tracks the forecast of ONE model; {self!r} is a multi-model ensemble -- track its saved "
                          "ensemble-mean files with skyrim_amd.tracks.track_prediction, or build Skyrim(<one model name>)")
 
+    def object_forecast(self, *args, **kwargs):
+        raise ValueError(f"object_forecast finds the objects of the forecast of ONE model; {self!r} is a multi-model ensemble -- use its "
+                         "saved ensemble-mean files with skyrim_amd.objects.objects_prediction, or build Skyrim(<one model name>)")
+
     def derive_fields(self, *args, **kwargs):
         raise ValueError(f"derive_fields derives from the forecast of ONE model; {self!r} is a multi-model ensemble -- derive from its saved "
                          "ensemble-mean files with skyrim_amd.derived.derive_prediction, or build Skyrim(<one model name>)")

@@ -133,6 +133,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator track_cyclones advances: "
                                   "track its forecast with skyrim_amd.tracks.track_prediction(forecast_or_saved_files)")
 
+    def object_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator object_forecast advances: "
+                                  "find the objects of its forecast with skyrim_amd.objects.objects_prediction(forecast_or_saved_files, objects)")
+
     def derive_fields(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
                                   "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")

@@ -73,6 +73,19 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.track_cyclones(start_time, n_steps=n_steps, **kwargs)
 
+    def object_forecast(self, start_time: datetime.datetime, n_steps: int = 4, objects=None, **kwargs):
+        """Weather objects -- the contiguous regions where a field is beyond a threshold: atmospheric rivers, gale areas, cold pools -- of
+        the single model's forecast as an ``objects.Objects`` (``GlobalModel.object_forecast`` has the arguments).
+        ``ensemble_forecast(..., objects={...})`` finds them in every member and gives their probability."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.object_forecast(start_time, n_steps=n_steps, objects=objects, **kwargs)
+
+    @staticmethod
+    def objects_prediction(pred, objects, device="cuda:0", **kwargs):
+        """Weather objects of a forecast that is already in memory or on disk (``objects.objects_prediction``)."""
+        from .. import objects as objecting
+        return objecting.objects_prediction(pred, objects, device=device, **kwargs)
+
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields=(), **kwargs):
         """Derived fields (wind speed, thickness, vorticity, divergence, vapour transport) of the single model's forecast as a
         DataArray(time, channel=fields, lat, lon) (``GlobalModel.derive_fields`` has the arguments).

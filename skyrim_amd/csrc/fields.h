@@ -1,4 +1,4 @@
-// What the product kernels (score, event, track, derive, thermo, regrid, agg, point, gram, breed, spec) share on the device: how a lane reads and
+// What the product kernels (score, event, track, derive, thermo, regrid, agg, point, gram, breed, spec, object) share on the device: how a lane reads and
 // writes the points of a member state, and the wave reductions.  Everything is __device__ __forceinline__ and leaves no call behind.
 // (ens_ops.hip is not among them: its load goes through a generic pointer.)
 #pragma once
@@ -88,6 +88,15 @@ __device__ __forceinline__ float wave_max(float v) {
         v = o > v ? o : v;
     }
     return v;
+}
+
+// the key (>= 0) that every lane with `on` holds, or -1 when they hold different keys or no lane is on: with a common key the wave
+// reduces over its lanes and ONE lane issues the atomic, where 64 lanes would otherwise queue on one address.  Every lane must call it
+__device__ __forceinline__ int wave_common(int key, bool on) {
+    const unsigned long long act = __ballot(on);
+    if (act == 0) return -1;
+    const int first = __shfl(key, __ffsll((long long)act) - 1);
+    return __ballot(on && key != first) == 0 ? uniform(first) : -1;
 }
 
 }  // namespace skfields

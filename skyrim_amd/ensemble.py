@@ -259,6 +259,7 @@ class EnsembleForecast:
     breeding: object = None      # the normalised ``breeding=`` request (cycles, norm, paired) or None
     breeding_growth: object = None      # (cycles, member, channel) float64 with ``breeding=``: breeding.Breeder.growth
     stochastic: object = None    # the normalised ``stochastic=`` request (stochastic.Plan.as_dict) or None
+    objects: object = None       # objects.Objects with ``objects={...}``
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -285,7 +286,7 @@ def scenario_std(model, names) -> np.ndarray:
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, breeding=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, breeding=None,
              stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
@@ -298,7 +299,8 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only.  ``breeding``:
     the dict of skyrim_amd/breeding.py (cycles, norm, paired); ``perturbation`` then names the seed.  ``stochastic``: the dict of
     skyrim_amd/stochastic.py (kind, amplitude, clip, additive_scale, tau_h, length_scale_km, alpha, lmax, channels).  ``spectra``: the dict
-    of skyrim_amd/spectra.py (channels, bands): raw channels and fields of ``derived`` on the model's own grid."""
+    of skyrim_amd/spectra.py (channels, bands): raw channels and fields of ``derived`` on the model's own grid.  ``objects``: the dict
+    of skyrim_amd/objects.py (thresholded channels or derived fields, their filters, connectivity, min_pixels, capacity)."""
     from . import noise
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -378,6 +380,9 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
         from . import spectra as spec
         other = [f for g in aplan.groups for f in g.fields] if aplan is not None else []
         spec.check_request(names + list(derived or []), model.grid.lat, model.grid.lon, n_members, spectra, other)
+    if objects is not None:                                 # planes, members, the grid's axes; raw channels and derived fields of the model's grid
+        from . import objects as objecting
+        objecting.check_request(names, model.grid.lat, model.grid.lon, n_members, objects, list(derived or []))
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
@@ -409,7 +414,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
@@ -423,7 +428,8 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                                                   point_channels=point_channels, point_method=point_method, scenarios=scenarios, spectra=spectra,
                                                   breeding=breeding, stochastic=stochastic, aggregates=aggregates, derived_surface=derived_surface,
                                                   derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
-                                                  length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels)
+                                                  length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels,
+                                                  objects=objects)
     keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
     plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
     bplan = None
@@ -531,6 +537,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         if der:
             dspectrist = spec.LeadSpectra(dnames, model.grid.lat, model.grid.lon, M, dict(spectra, channels=der), device=model.device,
                                           truth=dscorer is not None)
+    objecter = None
+    if objects is not None:                                # labelled threshold regions of every member (skyrim_amd/objects.py): raw channels
+        from . import objects as objecting                 # from the states, derived fields from the deriver's buffer
+        objecter = objecting.LeadObjects(names, model.grid.lat, model.grid.lon, M, objects, model.device, list(derived or []),
+                                         model_name=gm.model_name)
     hw = n_lat * n_lon
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
     dev = x0.device
@@ -624,7 +635,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
             if tracker is not None:
                 tracker.add(time, states, table)           # cyclone candidates of this lead time: only their records leave the device
             fold_derived = aggregator is not None and agg_derived and k >= 1
-            if deriver is not None and (keep or dscorer is not None or fold_derived):
+            if deriver is not None and (keep or dscorer is not None or fold_derived):      # (``objecter`` reads the derived planes of saved leads)
                 dstates, dtable = deriver.add(states, table)      # ONE launch: D derived planes per member, read below like raw channels
                 if dscorer is not None:
                     dscorer.add(time, dstates, dtable)
@@ -636,6 +647,11 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
                 scenarist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
             if spectrist is not None and keep:             # one launch, nc x nb x kinds x K doubles to the host
                 spectrist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
+            if objecter is not None and keep:              # label, attributes, probability: records and count planes leave the device
+                objecter.add(time, states, table, (dstates, dtable) if objecter.needs_derived else None,
+                             scorer.truth_state() if scorer is not None else None,
+                             dscorer.truth_state() if dscorer is not None else None,
+                             None if scorer is None else list(scorer.scored) + (list(dscorer.scored) if dscorer is not None else []))
             if pointer is not None and keep:               # the members where they lie: one launch per source buffer, only the values leave
                 pointer.add(time, states, table, (dstates, dtable) if pointer.needs_derived else None)
             if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
@@ -715,6 +731,10 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     if spectrist is not None or dspectrist is not None:
         parts = [s.result(f"{gm.model_name}-ens{M}", fid) for s in (spectrist, dspectrist) if s is not None]
         ens.spectra = spec.merge(parts, spectra["channels"])
+    if objecter is not None:
+        ens.objects = _stamped(objecter, fid)
+        if save:
+            _save_result(ens.objects, cfg, paths)
     if pointer is not None:
         ens.points = pointer.result(f"{gm.model_name}-ens{M}", fid)
         if save:

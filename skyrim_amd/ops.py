@@ -28,6 +28,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     zonal_spectra                                        (zonal power spectra of M states, their mean, spread and errors, include/skyrim_spec.h)
     breed_norms / breed_apply                            (the two passes of a breeding cycle over M states, include/skyrim_breed.h)
     stoch_coeffs / stoch_evolve / stoch_apply            (per-step stochastic perturbations: SPPT and additive, include/skyrim_stoch.h)
+    object_label / object_attributes / object_probability    (labelled threshold regions of M states, include/skyrim_object.h)
 """
 from __future__ import annotations
 
@@ -658,6 +659,35 @@ def _stoch_apply(xp, xn, r, y, gs, ga, lim: float, out, chan_stride: int) -> Non
     stochastic.apply(xp, xn, r, y, gs, ga, lim, out, chan_stride)
 
 
+# ---- weather objects ---------------------------------------------------------------------------------------------------------------------- #
+def _object_planes(channels, thresholds, directions, connectivity, scales):
+    if not len(channels) == len(thresholds) == len(directions) == len(connectivity) == len(scales):
+        raise ValueError("object planes: channels, thresholds, directions, connectivity and scales have one entry per plane")
+    return list(zip(channels, thresholds, directions, connectivity, scales))
+
+
+def _object_label(members, table, channels, thresholds, directions, connectivity, scales, periodic: bool, min_pixels: int, capacity: int,
+                  labels, ids, n_found, workspace) -> None:
+    """``labels``, ``ids``: int32 (M, P, H, W); ``n_found``: int32 (M, P); ``workspace``: objects.workspace_bytes(M, P, H, W) bytes."""
+    from . import objects
+    objects.label(list(members), table, _object_planes(channels, thresholds, directions, connectivity, scales), periodic, min_pixels, capacity,
+                  labels, ids, n_found, workspace)
+
+
+def _object_attributes(members, table, channels, thresholds, directions, connectivity, scales, capacity: int, labels, ids, n_found, row_tables,
+                       col_tables, records) -> None:
+    """``row_tables``: float64 (6, H); ``col_tables``: float64 (5, W); ``records``: uint8, (M, P, capacity) records of 128 bytes."""
+    from . import objects
+    objects.attributes(list(members), table, _object_planes(channels, thresholds, directions, connectivity, scales), capacity, labels, ids,
+                       n_found, row_tables, col_tables, records)
+
+
+def _object_probability(ids, keep, counts) -> None:
+    """``keep``: uint8 (M, P, capacity + 1); ``counts``: int32 (P, H, W)."""
+    from . import objects
+    objects.probability(ids, keep, counts)
+
+
 _SCHEMAS = [
     ("pangu_step(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_step),
     ("pangu_patch_embed(int ctx, Tensor x, Tensor(a!) out) -> ()", _pangu_patch_embed),
@@ -730,6 +760,11 @@ _SCHEMAS = [
      _stoch_evolve),
     ("stoch_apply(Tensor? xp, Tensor xn, Tensor? r, Tensor? y, Tensor? gs, Tensor? ga, float lim, Tensor(a!) out, int chan_stride) -> ()",
      _stoch_apply),
+    ("object_label(Tensor[] members, Tensor table, int[] channels, float[] thresholds, int[] directions, int[] connectivity, float[] scales, "
+     "bool periodic, int min_pixels, int capacity, Tensor(a!) labels, Tensor(b!) ids, Tensor(c!) n_found, Tensor(d!) workspace) -> ()", _object_label),
+    ("object_attributes(Tensor[] members, Tensor table, int[] channels, float[] thresholds, int[] directions, int[] connectivity, float[] scales, "
+     "int capacity, Tensor labels, Tensor ids, Tensor n_found, Tensor row_tables, Tensor col_tables, Tensor(a!) records) -> ()", _object_attributes),
+    ("object_probability(Tensor ids, Tensor keep, Tensor(a!) counts) -> ()", _object_probability),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
