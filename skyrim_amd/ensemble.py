@@ -6,23 +6,25 @@ Four layers:
   ``torch.ops.skyrim_hip.ens_perturb / ens_stats`` (skyrim_amd/ops.py);
 * ``ProductSet`` -- the products of one family of fields (raw, derived, regridded, one window group of aggregates): their buffers,
   the ``stats`` launches and copies of an entry, its files, its labelled arrays;
-* ``run`` -- what ``GlobalModel.ensemble_forecast`` does: the initial condition once, M members from ``ens_perturb`` (white noise) or
-  ``noise.Perturber`` (``perturbation="spherical"``: correlated fields, skyrim_amd/noise.py), with ``breeding=`` bred from those seeds
-  through the model itself (skyrim_amd/breeding.py), ONE TimeLoop
-  generator per member advanced step-major (all members one step, then the statistics of that lead time), so only the members'
-  current states are alive on the GPU; with ``stochastic=`` the members are held as states instead and every step of every member
-  but the control is perturbed (SPPT, additive noise: skyrim_amd/stochastic.py);
+* ``run`` -- what ``GlobalModel.ensemble_forecast`` does.  ``plan_request``: the refusals that need no device, the request normalised
+  once.  ``seed_members``: the initial condition once, M members from ``ens_perturb`` (white noise) or ``noise.Perturber``
+  (``perturbation="spherical"``, skyrim_amd/noise.py), with ``breeding=`` bred from those seeds through the model itself
+  (skyrim_amd/breeding.py).  ``Members``: ONE TimeLoop generator per member advanced step-major (all members one step, then that lead
+  time's statistics), so only the members' current states are alive on the GPU; with ``stochastic=`` the members are held as states
+  and every step of every member but the control is perturbed (skyrim_amd/stochastic.py).  ``stages``: what a lead time sets off;
 * ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
 
 Members sharded over ranks stay with ``skyrim_amd/pangu/ensemble.py``; multi-MODEL ensembles are ``core/models/ensemble.py``.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import datetime
 import functools
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, make_dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -212,17 +214,26 @@ def split_table(table, fields) -> tuple[dict, dict]:
     return {k: v for k, v in table.items() if k in fields}, {k: v for k, v in table.items() if k not in fields}
 
 
-def _stamped(maker, fid):
-    """``maker.result()`` with the forecast id on it."""
-    res = maker.result()
+def _per_family(table, fields_of) -> dict:
+    """``{family: its entries of table}`` for the ``{family: fields}`` of ``fields_of``; ``"raw"`` takes what none of them names."""
+    out = {}
+    for fam, fields in fields_of.items():
+        out[fam], table = split_table(table, fields)
+    return dict(out, raw=table)
+
+
+def _hang(res, fid, sink=None):
+    """``res`` with the forecast id on it; a ``sink`` = (save config, paths): written under the forecast's output directory, its path noted."""
     res.forecast_id = fid
+    if sink is not None:
+        from .common import OUTPUT_DIR
+        sink[1].append(res.save(sink[0].get("output_dir") or OUTPUT_DIR))
     return res
 
 
-def _save_result(res, cfg, paths) -> None:
-    """Write a result object under the forecast's output directory and note its path."""
-    from .common import OUTPUT_DIR
-    paths.append(res.save(cfg.get("output_dir") or OUTPUT_DIR))
+def _put(obj, name, value):
+    setattr(obj, name, value)
+    return value
 
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------- #
@@ -285,23 +296,30 @@ def scenario_std(model, names) -> np.ndarray:
     return std
 
 
-def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, breeding=None,
-             stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
-             perturb_channels=None):
-    """Every refusal that needs no device; returns (products, exceed, quantiles, saved step numbers) normalised.  ``derived``: the
-    derived fields asked for (skyrim_amd/derived.py); ``exceed`` and ``quantiles`` may then name them alongside the raw channels.
-    ``aggregates``: the time-window aggregates asked for (skyrim_amd/aggregate.py), of raw channels and derived fields on the model's own
-    grid; ``exceed``, ``quantiles`` and ``events`` may name them (``ws10m_max_24h``) as well.  ``grid`` / ``regrid_method``: the target grid of skyrim_amd/regrid.py the products are also made on.  ``events`` /
-    ``neighbourhoods_km``: the threshold events verified with the ``scores`` (skyrim_amd/events.py; ``event_request`` normalises them).
-    ``points`` / ``point_channels`` / ``point_method``: the places every member is sampled at (skyrim_amd/points.py), the raw channels and
-    derived fields sampled there (default: ``channels``, or all raw channels) and the interpolation.  ``scenarios``: the dict of
-    skyrim_amd/scenarios.py (channels, region, n_clusters, n_eofs, normalise): raw channels on the model's own grid only.  ``breeding``:
-    the dict of skyrim_amd/breeding.py (cycles, norm, paired); ``perturbation`` then names the seed.  ``stochastic``: the dict of
-    skyrim_amd/stochastic.py (kind, amplitude, clip, additive_scale, tau_h, length_scale_km, alpha, lmax, channels).  ``spectra``: the dict
-    of skyrim_amd/spectra.py (channels, bands): raw channels and fields of ``derived`` on the model's own grid.  ``objects``: the dict
-    of skyrim_amd/objects.py (thresholded channels or derived fields, their filters, connectivity, min_pixels, capacity)."""
-    from . import noise
+# ---- the request --------------------------------------------------------------------------------------------------------------------- #
+# A checked ``ensemble_forecast`` request (``plan_request``): everything ``run`` needs from it that the host can decide.  ``asked``: the
+# keywords as given, by name -- what a ``Lead*`` object normalises itself reaches it as it came; ``saved``: the saved step numbers;
+# ``names`` / ``derived``: the model's output channels and the derived fields ([]: none); ``exceed`` / ``quantiles`` / ``events``:
+# ``{family: {field: values}}`` with the families ``"raw"`` (the regridded channels share it), ``"derived"`` and ``"agg{label}"`` per window
+# group; ``radii``: the events' neighbourhoods, km; ``keep_members``: the raw, derived and aggregated ones; ``noise`` / ``breeding`` /
+# ``stochastic`` / ``aggregate``: the plans of those modules, or None; ``regrid``: ``regrid.Tables`` or None; ``points``: ``points.Points`` or
+# None; ``point_channels``: what is sampled there (``point_channels``, else ``channels``, else None = every raw channel).
+Plan = make_dataclass("Plan", "asked M products saved names derived exceed quantiles events radii keep_members keep_regridded noise breeding "
+                      "stochastic aggregate regrid points point_channels".split())
+
+
+def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
+                 neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None,
+                 breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative",
+                 perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None, perturb_scale=None) -> Plan:
+    """Every refusal that needs no device, in one fixed order, and the request normalised once: the ``Plan``.  The keywords are those of
+    ``GlobalModel.ensemble_forecast`` (core/models/base.py describes them).  ``exceed`` and ``quantiles`` may name raw channels, fields
+    of ``derived`` and aggregates (``ws10m_max_24h``), ``events`` too; ``scenarios`` takes raw channels, ``spectra`` and ``objects`` raw
+    channels and derived fields, all on the model's own grid.  ``perturb_scale``: the default of ``stochastic``'s ``additive_scale``,
+    which ``run`` passes and ``validate`` has not."""
+    asked = SimpleNamespace(**locals())
+    from . import aggregate, breeding as breed, derived as deriving, noise, objects as objecting, points as pointing, regrid
+    from . import scenarios as scen, spectra as spec, stochastic as stoch
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
         raise NotImplementedError("ensemble_forecast runs all members on one GPU; under a process group of more than one rank use "
@@ -316,22 +334,20 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     unknown = [p for p in products if p not in PRODUCTS]
     if unknown:
         raise ValueError(f"unknown products {unknown}; choose from {PRODUCTS}")
-    names = list(model.out_channel_names)
+    names, dnames = list(model.out_channel_names), list(derived or [])
     if derived is not None:
-        from . import derived as deriving
-        deriving.check_request(names, list(derived), model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None)
-    known = names + list(derived or [])
-    aplan = None
+        deriving.check_request(names, dnames, model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None)
+    known = names + dnames
+    aplan, groups = None, []
     if aggregates is not None:
-        from . import aggregate
         aplan = aggregate.check_request(known, aggregates, model.time_step, n_steps, model.grid.lat, model.grid.lon, n_members)
-        clash = [f for g in aplan.groups for f in g.fields if f in known]
+        groups = aplan.groups
+        clash = [f for g in groups for f in g.fields if f in known]
         if clash:
             raise ValueError(f"aggregates: {clash} are already channels of this forecast")
-        known = known + [f for g in aplan.groups for f in g.fields]
+        known = known + [f for g in groups for f in g.fields]
     tabs = None
     if grid is not None:
-        from . import regrid
         if derived is not None:
             raise ValueError("grid= together with derived= is not supported: derived fields are made on the model's own grid only "
                              "(DESIGN.md 22, out of scope)")
@@ -347,54 +363,59 @@ def validate(model, n_steps, n_members, seed, products, exceed, quantiles, chann
     for ch, vals in (quantiles or {}).items():
         for q in vals:
             quantile_position(q, int(n_members))
-    if events is not None:
-        event_request(events, neighbourhoods_km, exceed, known, n_members, scores)
+    # (``event_request`` rounds the thresholds of ``exceed`` to fp32 itself)
+    ev, radii = event_request(events, neighbourhoods_km, exceed, known, n_members, scores) if events is not None else ({}, [])
     missing = [c for c in (channels or []) if c not in names]
     if missing:
         raise ValueError(f"channels {missing} are not output channels of this model")
-    noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
-    if breeding is not None:                                # cycles, norm, keys; one history level, the same channels in and out
-        from . import breeding as breed
-        breed.plan(model, breeding)
-    if stochastic is not None:                              # kind, amplitudes, the pattern's spectrum and grid, a model that steps from one state
-        from . import stochastic as stoch
-        stoch.plan(model, stochastic)
+    nplan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)      # kind, length scale, lmax, grid, channels
+    bplan = breed.plan(model, breeding)                     # cycles, norm, keys; one history level, the same channels in and out
+    splan = stoch.plan(model, stochastic, perturb_scale)    # kind, amplitudes, the pattern's spectrum and grid, a model that steps from one state
     saved = list(range(0, n_steps + 1, save_every))
+    pts = None
+    point_channels = point_channels if point_channels is not None else (list(channels) if channels else None)
     if points is not None:                                  # the points, their channels, a bilinear point outside the source rows, the host limit
-        from . import points as pointing
         pts = pointing.Points(points)
-        picked, raw, der = pointing._sources(names, derived, point_channels if point_channels is not None else (list(channels) if channels else None))
-        for nm, ch in ((names, raw), (list(derived or []), der)):
+        picked, raw, der = pointing._sources(names, derived, point_channels)
+        for nm, ch in ((names, raw), (dnames, der)):
             if ch:
                 pointing.check_request(nm, model.grid.lat, model.grid.lon, n_members, pts, ch, point_method, len(saved))
         pointing.host_limit(n_members, len(saved), len(picked), len(pts))
-        for g in (aplan.groups if aplan is not None else []):
+        for g in groups:
             pointing.check_request(g.fields, model.grid.lat, model.grid.lon, n_members, pts, None, point_method, max(g.n_windows, 1))
+    a_fields = [f for g in groups for f in g.fields]
     if scenarios is not None:                               # raw channels of the model's grid only; names of other products are refused by name
-        from . import scenarios as scen
-        other = list(derived or []) + ([f for g in aplan.groups for f in g.fields] if aplan is not None else [])
-        req = scen.check_request(names, model.grid.lat, model.grid.lon, n_members, scenarios, scores, other)
-        if req["normalise"] == "std":
+        if scen.check_request(names, model.grid.lat, model.grid.lon, n_members, scenarios, scores, dnames + a_fields)["normalise"] == "std":
             channel_std(model)                              # NotImplementedError for a model without per-channel sigmas
     if spectra is not None:                                 # raw channels and derived fields of the model's grid; aggregates are refused by name
-        from . import spectra as spec
-        other = [f for g in aplan.groups for f in g.fields] if aplan is not None else []
-        spec.check_request(names + list(derived or []), model.grid.lat, model.grid.lon, n_members, spectra, other)
+        spec.check_request(names + dnames, model.grid.lat, model.grid.lon, n_members, spectra, a_fields)
     if objects is not None:                                 # planes, members, the grid's axes; raw channels and derived fields of the model's grid
-        from . import objects as objecting
-        objecting.check_request(names, model.grid.lat, model.grid.lon, n_members, objects, list(derived or []))
+        objecting.check_request(names, model.grid.lat, model.grid.lon, n_members, objects, dnames)
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
-        planes = len(saved) * (len(names) + len(derived or [])) + (0 if aplan is None else sum(g.n_windows * len(g.fields) for g in aplan.groups))
+        planes = len(saved) * (len(names) + len(dnames)) + sum(g.n_windows * len(g.fields) for g in groups)
         need = 0 if keep_members == "regridded" else int(n_members) * planes * len(model.grid.lat) * len(model.grid.lon) * 4
         if tabs is not None:                                # the regridded members are checked at the size they have
             need += int(n_members) * len(saved) * len(names) * tabs.lat.size * tabs.lon.size * 4
         if need > _PINNED_LIMIT:
             raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
                              f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every")
-    return (products, {k: [float(np.float32(v)) for v in vs] for k, vs in (exceed or {}).items()},
-            {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}, saved)
+    fields_of = dict({"derived": dnames} if dnames else {}, **{f"agg{g.label}": g.fields for g in groups})
+    exceed = {k: [float(np.float32(v)) for v in vs] for k, vs in (exceed or {}).items()}
+    quantiles = {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}
+    return Plan(asked, int(n_members), products, saved, names, dnames, _per_family(exceed, fields_of), _per_family(quantiles, fields_of),
+                _per_family(ev, fields_of), radii, bool(keep_members) and keep_members != "regridded", bool(keep_members) and grid is not None,
+                nplan, bplan, splan, aplan, tabs, pts, point_channels)
+
+
+def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, breeding=None,
+             stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             perturb_channels=None):
+    """Every refusal that needs no device (``plan_request``); returns (products, exceed, quantiles, saved step numbers) normalised."""
+    p = plan_request(**locals())
+    return (p.products, *({k: v for part in t.values() for k, v in part.items()} for t in (p.exceed, p.quantiles)), p.saved)
 
 
 def event_request(events, neighbourhoods_km, exceed, known, n_members, scores) -> tuple[dict, list]:
@@ -410,6 +431,250 @@ def event_request(events, neighbourhoods_km, exceed, known, n_members, scores) -
     return eventing.check_request(known, events, neighbourhoods_km, n_members, "an output channel of this model or one of the derived fields")
 
 
+# ---- the members --------------------------------------------------------------------------------------------------------------------- #
+def seed_members(model, p: Plan, x0, std, perturb_scale, start_time) -> tuple[list, object]:
+    """(the M member states seeded from the initial condition ``x0``, ``Breeder.growth`` or None): white noise (``perturb``) or spherical
+    fields (``noise.Perturber``), with ``breeding=`` bred through the model (skyrim_amd/breeding.py).  ``std``: ``channel_std(model)``."""
+    from . import breeding as breed, noise
+    from .leads import forget_resident
+    hw, seed, sigma_all = len(model.grid.lat) * len(model.grid.lon), int(p.asked.seed), std      # (breeding normalises with every channel's own sigma)
+    if p.noise.channel_mask is not None and p.noise.kind == "white":
+        std = torch.where(torch.from_numpy(p.noise.channel_mask).to(x0.device), std, torch.zeros_like(std))       # amplitude exactly 0 elsewhere
+    spherical = noise.Perturber(p.noise, x0, std, perturb_scale, seed) if p.noise.kind == "spherical" else None
+
+    def seed_member(m, xm):
+        if spherical is not None:
+            spherical.member(m, xm)
+        else:
+            perturb(x0, std, xm, hw, perturb_scale, seed, m)
+    if p.breeding is not None:
+        breeder = breed.Breeder(model, p.breeding, x0, sigma_all, perturb_scale, seed, start_time, seed_member, mask=p.noise.channel_mask)
+        breeder.run(p.M)
+        forget_resident(model, closed=False)
+        return [breeder.member(m) for m in range(p.M)], breeder.growth
+    states = [torch.empty_like(x0) for _ in range(p.M)]
+    for m, xm in enumerate(states):
+        seed_member(m, xm)
+    return states, None
+
+
+class Members:
+    """The M members of one forecast behind ``advance(k) -> (valid time, their states (C, H, W) of lead k)``, the leads in order from 0.
+    Without a ``stepper`` every member is its own TimeLoop generator ``model(start_time, x_m)`` and a lead is one ``next`` of each, in
+    member order; with one (``stochastic.Stepper``) the members are held as states, and lead k >= 1 of a member is the model's own lead 1
+    from its state before (``breeding.step_once``), perturbed in place by ``stepper.advance``.  Only the members' current states are kept."""
+
+    def __init__(self, model, start_time, seeds, stepper=None):
+        self.model, self.start_time, self.stepper = model, start_time, stepper
+        self.loops = [model(start_time, x) for x in seeds] if stepper is None else []
+        self.current = [] if stepper is None else list(seeds)
+
+    def advance(self, k: int) -> tuple:
+        if self.stepper is None:
+            states = []
+            for m, loop in enumerate(self.loops):
+                try:
+                    time, out, _ = next(loop)
+                except FloatingPointError as e:
+                    raise FloatingPointError(f"ensemble member {m}, step {k}: {e}") from e
+                states.append((out[0] if out.dim() == 4 else out).contiguous())
+            return time, states
+        from .breeding import step_once
+        time = self.start_time + k * self.model.time_step
+        for m, xp in enumerate(self.current if k >= 1 else ()):
+            xn = step_once(self.model, time - self.model.time_step, xp, f"ensemble member {m}, step {k}")
+            self.stepper.advance(k, m, xp[0, 0], xn)       # in place on xn; member 0 is left as the model made it
+            self.current[m] = xn.reshape(xp.shape)
+        return time, [x[0, 0] for x in self.current]
+
+    def close(self) -> None:
+        """Close every generator, also after one of them raises: a ``FloatingPointError`` of a loop's own guard is dropped (every delivered
+        step was checked, by member), the first other error is raised once all are closed."""
+        first = None
+        for loop in self.loops:
+            try:
+                loop.close()
+            except FloatingPointError:
+                pass
+            except Exception as e:
+                first = first or e
+        if first is not None:
+            raise first
+
+
+# ---- families and stages ------------------------------------------------------------------------------------------------------------- #
+class Family:
+    """One family of fields in the driver: raw channels, derived fields, regridded channels or the aggregates of one window group.
+    ``make()``: its ``ProductSet`` (``products``), made once the members are seeded; ``hang(ens)``: the object its results go on (``ens``,
+    ``DerivedProducts``, ``RegriddedProducts``, ``AggregatedProducts``), put in its place; ``scorer``: its ``LeadScorer`` or None, the truth
+    adapter in it; ``points``: a window group's ``LeadPoints``; ``select``: the channels to cut to; ``grid``: the target grid's label."""
+
+    def __init__(self, make, hang, scorer=None, points=None, select=None, grid=None, windows=False):
+        self.make, self.hang, self.scorer, self.points, self.select, self.grid = make, hang, scorer, points, select, grid
+        self.products, self.times, self.starts = None, [], [] if windows else None
+
+    def score(self, time, states, table, window=None):
+        """The scores of this lead; returns the truth they were made against as a device state, None without scores.  ``window``: the
+        valid times of the window that closes, which the truth is aggregated over."""
+        if self.scorer is None:
+            return None
+        if window is not None:
+            self.scorer.adapt.window(window)
+        self.scorer.add(time, states, table)               # the same states and table: one more read of the members, one of the truth
+        return self.scorer.truth_state()
+
+    def reduce(self, time, states, table, slot, start=None) -> None:
+        """Entry ``slot`` of the products (None: only what the set computes at every lead), then a window group's points."""
+        if slot is not None:
+            self.times.append(time)
+            if start is not None:
+                self.starts.append(start)
+        self.products.reduce(states, table, slot)
+        if self.points is not None:
+            self.points.add(time, states, table)
+
+    def lead(self, time, states, table, slot):
+        """What a lead time is to a family whose states are made for it: the scores, then the products."""
+        self.score(time, states, table)
+        self.reduce(time, states, table, slot)
+
+    def fill(self, ens, fid, sink=None) -> None:
+        """The labelled arrays, ``points``, ``scores``, the scores' ``grid`` and ``dropped`` on the family's object, where they apply."""
+        target, ps = self.hang(ens), self.products
+        ps.fill(target, self.times, self.select, window_start=self.starts)
+        if self.points is not None:
+            target.points = self.points.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid, window_start=self.starts)
+        if self.scorer is not None:
+            target.scores = _hang(self.scorer.result(), fid, sink)
+            if self.grid is not None:
+                target.scores.grid = self.grid
+            if hasattr(self.scorer.adapt, "dropped"):
+                target.dropped = dict(self.scorer.adapt.dropped)
+
+
+_saved = lambda L: L.slot is not None                      # noqa: E731
+Stage = collections.namedtuple("Stage", "add due finish", defaults=(None, _saved, None))
+
+
+def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, tracks=False, track_config=None) -> tuple[list, list]:
+    """(the stages of a lead time, the families: raw, derived, regridded, then the window groups).  THE place a product is wired in: its
+    ``Lead*`` object is made here, in the order the refusals of these objects have, with the checks that need the truth, and it gets one
+    ``Stage`` in the list at the end, whose order is the order of the launches of a lead (DESIGN.md 17 has the rules it keeps):
+    ``add(L)`` is called where ``due(L)`` (default: at saved leads), ``finish(ens, fid, sink)`` once after the last lead.  ``L``, the record of
+    a lead: ``k``, ``time``, ``slot`` (the entry of a saved lead, else None), ``states``, ``table``, ``sink`` (where files go) and, set by the
+    stages before, ``truth`` (the raw scorer's truth state), ``derived`` = (states, table) of the deriver, ``dtruth``."""
+    from . import aggregate, derived as deriving, objects as objecting, points as pointing, regrid, scenarios as scen, spectra as spec
+    from . import tracks as tracking, verify
+    model, a, M, names, dnames, dev, n_saved = gm.model, p.asked, p.M, p.names, p.derived, gm.model.device, len(p.saved)
+    lat, lon, label = model.grid.lat, model.grid.lon, f"{gm.model_name}-ens{M}"
+    groups = p.aggregate.groups if p.aggregate is not None else []
+    wants = lambda asked, family: [c for c in asked.get("channels") or [] if (c in names) == (family == "raw")]      # noqa: E731
+
+    def products(fields, la, lo, entries, family, keep, prefix="", always=()):
+        return functools.partial(ProductSet, gm.model_name, M, p.products, dev, fields, la, lo, entries, p.exceed.get(family, {}),
+                                 p.quantiles.get(family, {}), keep, prefix, always)
+
+    def scorer(fields, la, lo, src, channels, family, adapt=None):
+        ev = p.events.get(family)                          # names of derived fields and aggregates go to their family's scorer
+        return verify.LeadScorer(gm.model_name, fields, la, lo, M, src, climatology, channels, device=dev, adapt=adapt,
+                                 **(dict(events=ev, neighbourhoods_km=p.radii) if ev else {})) if scores else None
+    aggregator = aggregate.LeadAggregator(names, lat, lon, M, p.aggregate.requests, start_time, model.time_step, device=dev,
+                                          n_steps=a.n_steps, derived=dnames) if groups else None
+    raw = Family(products(names, lat, lon, n_saved, "raw", p.keep_members, always=("mean",)), lambda ens: ens,
+                 scorer(names, lat, lon, verify.default_truth(gm) if truth is None and scores else truth, a.channels, "raw"), select=a.channels)
+    if scores:                                             # (refusals of the request come before anything touches the device)
+        truth = raw.scorer.truth.src
+        if a.scenarios is not None:                        # the truth is a column of the Gram matrix: it must hold the scenario channels
+            scen.check_scored(a.scenarios.get("channels") or [], raw.scorer.scored)
+        if a.spectra is not None:                          # truth, error_mean and error_member need the truth of every spectrum channel
+            spec.check_scored(wants(a.spectra, "raw"), raw.scorer.scored)
+    tracker = tracking.LeadTracker(gm.model_name, names, lat, lon, M, track_config, device=dev) if tracks else None
+    deriver = derived = truth_deriver = None
+    if dnames:                                             # derived fields (skyrim_amd/derived.py): their own products, labelled with their names
+        deriver = deriving.LeadDeriver(names, lat, lon, M, dnames, device=dev, surface=a.derived_surface)
+        # what every truth of these fields shares with the forecast: its levels, its thermodynamic columns, its kind of humidity, its surface mask
+        truth_deriver = functools.partial(deriving.TruthDeriver, dnames, lat, lon, device=dev, levels=deriver.plan.levels or None,
+                                          column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=a.derived_surface)
+        derived = Family(products(dnames, lat, lon, n_saved, "derived", p.keep_members, "derived-"),
+                         lambda ens: _put(ens, "derived", deriving.DerivedProducts(dnames)),
+                         scorer(dnames, lat, lon, truth, None, "derived", truth_deriver() if scores else None))
+        if scores and a.spectra is not None:
+            spec.check_scored(wants(a.spectra, "derived"), derived.scorer.scored)
+    windowed = {}                                          # per window group: one entry per complete window, scored against the same
+    for g in groups:                                       # aggregates of the truth
+        hook = aggregate.TruthAggregator(g.requests, lat, lon, start_time, model.time_step, device=dev,
+                                         inner=truth_deriver and truth_deriver()) if scores else None
+        windowed[g.label] = Family(products(g.fields, lat, lon, g.n_windows, f"agg{g.label}", p.keep_members, f"agg{g.label}-"),
+                                   lambda ens, g=g: ens.aggregated.setdefault(g.label, aggregate.AggregatedProducts(
+                                       g.label, list(g.fields), incomplete=p.aggregate.incomplete.get(g.label))),
+                                   scorer(g.fields, lat, lon, truth, None, f"agg{g.label}", hook), windows=True)
+    regridder = regridded = None
+    if a.grid is not None:                                 # the same products on the target grid (skyrim_amd/regrid.py)
+        regridder = regrid.LeadRegridder(names, lat, lon, M, a.grid, a.regrid_method, device=dev)
+        hook = regrid.TruthRegridder(lat, lon, a.grid, a.regrid_method, device=dev) if scores else None
+        regridded = Family(products(names, regridder.lat_out, regridder.lon_out, n_saved, "raw", p.keep_regridded, "regrid-"),
+                           lambda ens: _put(ens, "regridded", regrid.RegriddedProducts(regridder.lat_out, regridder.lon_out, a.regrid_method)),
+                           scorer(names, regridder.lat_out, regridder.lon_out, truth, a.channels, "raw", hook), select=a.channels,
+                           grid=regrid.grid_label(a.grid))
+    # every member at the points (skyrim_amd/points.py): raw channels and derived fields at each saved lead, a window group when a window closes
+    pointer = pointing.LeadPoints(names, lat, lon, M, p.points, p.point_channels, a.point_method, dev, dnames, n_saved) if p.points is not None else None
+    for g in groups if p.points is not None else ():
+        windowed[g.label].points = pointing.LeadPoints(g.fields, lat, lon, M, p.points, None, a.point_method, dev, (), max(g.n_windows, 1))
+    # clusters, EOFs and the energy score of the members (skyrim_amd/scenarios.py)
+    scenarist = scen.LeadScenarios(names, lat, lon, M, a.scenarios, device=dev, truth=scores, std=scenario_std(model, names) if a.scenarios.get(
+        "normalise") == "std" else None) if a.scenarios is not None else None
+    spectrists = {}                                        # zonal power spectra of members, mean, spread and errors (skyrim_amd/spectra.py):
+    for family, own in (("raw", names), ("derived", dnames)) if a.spectra is not None else ():      # raw channels from the states, derived
+        if wants(a.spectra, family):                       # fields from the deriver's buffer
+            spectrists[family] = spec.LeadSpectra(own, lat, lon, M, dict(a.spectra, channels=wants(a.spectra, family)), device=dev, truth=scores)
+    # labelled threshold regions of every member (skyrim_amd/objects.py): raw channels from the states, derived fields from the deriver's buffer
+    objecter = objecting.LeadObjects(names, lat, lon, M, a.objects, dev, dnames, model_name=gm.model_name) if a.objects is not None else None
+    truth_names = list(raw.scorer.scored) + (list(derived.scorer.scored) if derived is not None else []) if scores else None
+
+    def raw_lead(L):                                       # first at every lead: a non-finite member makes the mean non-finite, one flag to read
+        raw.reduce(L.time, L.states, L.table, L.slot)
+        if not bool(torch.isfinite(raw.products.dev["mean"]).all().item()):
+            bad = [m for m, st in enumerate(L.states) if not bool(torch.isfinite(st).all().item())]
+            raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {L.k}")
+        L.truth = raw.score(L.time, L.states, L.table)
+
+    def derive(L):                                         # ONE launch: D derived planes per member, read below like raw channels
+        L.derived = deriver.add(L.states, L.table)
+        L.dtruth = derived.score(L.time, *L.derived)
+
+    def close_windows(L):                                  # windows close independently of ``save_every``
+        for c in aggregator.add(L.k, L.time, L.states, L.table, L.derived):
+            windowed[c.label].reduce(c.end, c.states, c.table, c.window, c.start)
+            windowed[c.label].score(c.end, c.states, c.table, c.times)
+            if L.sink is not None:                         # one file per closed window, without the ``window_start`` coordinate
+                L.sink[1].extend(windowed[c.label].products.save(c.window, [c.end], c.start, gm.source_label, L.sink[0]))
+
+    def hung(name, result, saved=True):                    # a ``finish``: the result on ``ens`` and, where it always was, in a file
+        return lambda ens, fid, sink: _put(ens, name, _hang(result(fid), fid, sink if saved else None))
+    folds_derived = bool(groups) and any(r.channel in dnames for r in p.aggregate.requests)
+    every = lambda L: True                                 # noqa: E731
+    todo = [                                               # (wanted?, the stage) in the order of a lead time
+        (True, Stage(raw_lead, every, raw.fill)),
+        (tracker, Stage(lambda L: tracker.add(L.time, L.states, L.table), every, hung("tracks", lambda fid: tracker.result()))),      # (a track needs every lead)
+        (deriver, Stage(derive, lambda L: _saved(L) or derived.scorer is not None or (folds_derived and L.k >= 1))),
+        (spectrists.get("derived"), Stage(lambda L: spectrists["derived"].add(L.time, *L.derived, L.dtruth))),
+        (deriver, Stage(lambda L: derived.reduce(L.time, *L.derived, L.slot), finish=lambda ens, fid, sink: derived.fill(ens, fid))),
+        (scenarist, Stage(lambda L: scenarist.add(L.time, L.states, L.table, L.truth),
+                          finish=hung("scenarios", lambda fid: scenarist.result(label, fid), False))),
+        (spectrists.get("raw"), Stage(lambda L: spectrists["raw"].add(L.time, L.states, L.table, L.truth))),
+        (spectrists, Stage(finish=hung("spectra", lambda fid: spec.merge([s.result(label, fid) for s in spectrists.values()], a.spectra["channels"]),
+                                       False))),
+        (objecter, Stage(lambda L: objecter.add(L.time, L.states, L.table, L.derived, L.truth, L.dtruth, truth_names),
+                         finish=hung("objects", lambda fid: objecter.result()))),
+        (pointer, Stage(lambda L: pointer.add(L.time, L.states, L.table, L.derived), finish=hung("points", lambda fid: pointer.result(label, fid)))),
+        (aggregator, Stage(close_windows, lambda L: L.k >= 1,                  # (step 0, the initial state, belongs to no window)
+                           lambda ens, fid, sink: [group.fill(ens, fid) for group in windowed.values()])),
+        (regridder, Stage(lambda L: regridded.lead(L.time, *regridder.add(L.states, L.table), L.slot),     # ONE launch: all channels, all members
+                          lambda L: _saved(L) or regridded.scorer is not None, lambda ens, fid, sink: regridded.fill(ens, fid))),
+    ]
+    return [stage for wanted, stage in todo if wanted], [f for f in (raw, derived, regridded) if f is not None] + list(windowed.values())
+
+
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
@@ -417,326 +682,61 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
-    """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description)."""
-    from . import noise
+    """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description): the plan of the request, the stages of a
+    lead time, the seeded members, then lead by lead every stage that is due."""
     from .common import save_config_with_id
     from .datasource import get_initial_condition_for_model
     from .leads import forget_resident
+    from .stochastic import Stepper
     model = gm.model
-    products, exceed, quantiles, saved = validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every,
-                                                  keep_members, events=events, neighbourhoods_km=neighbourhoods_km, scores=scores, points=points,
-                                                  point_channels=point_channels, point_method=point_method, scenarios=scenarios, spectra=spectra,
-                                                  breeding=breeding, stochastic=stochastic, aggregates=aggregates, derived_surface=derived_surface,
-                                                  derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
-                                                  length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels,
-                                                  objects=objects)
-    keep_regridded, keep_members = bool(keep_members) and grid is not None, bool(keep_members) and keep_members != "regridded"
-    plan = noise.plan(model, perturbation, length_scale_km, alpha, lmax, perturb_channels)
-    bplan = None
-    if breeding is not None:
-        from . import breeding as breed
-        bplan = breed.plan(model, breeding)
-    splan = None
-    if stochastic is not None:
-        from . import stochastic as stoch
-        splan = stoch.plan(model, stochastic, perturb_scale)
-    M = int(n_members)
-    names = list(model.out_channel_names)
-    n_lat, n_lon = len(model.grid.lat), len(model.grid.lon)
-    scorer = None
-    ev = d_ev = {}                                         # keyword arguments of the raw / regridded and of the derived scorer
-    aggregator, a_events, a_radii = None, {}, []
-    if aggregates is not None:                             # time-window aggregates (skyrim_amd/aggregate.py): names of aggregates in
-        from . import aggregate                            # ``exceed``, ``quantiles`` and ``events`` go to their window group
-        aggregator = aggregate.LeadAggregator(names, model.grid.lat, model.grid.lon, M, aggregates, start_time, model.time_step,
-                                              device=model.device, n_steps=n_steps, derived=list(derived or []))
-        a_fields = [f for g in aggregator.plan.groups for f in g.fields]
-        (a_exceed, exceed), (a_quant, quantiles) = split_table(exceed, a_fields), split_table(quantiles, a_fields)
-    if events is not None:                                 # names of derived fields go to the derived scorer, as those of ``exceed`` do
-        known = names + list(derived or []) + (a_fields if aggregator is not None else [])
-        events, radii = event_request(events, neighbourhoods_km, dict(exceed, **a_exceed) if aggregator is not None else exceed, known, M, scores)
-        if aggregator is not None:
-            (a_events, events), a_radii = split_table(events, a_fields), radii
-        raw, der = split_table(events, names)
-        ev = dict(events=raw, neighbourhoods_km=radii) if raw else {}
-        d_ev = dict(events=der, neighbourhoods_km=radii) if der else {}
-    if scores:                                             # (refusals of the request come before anything touches the device)
-        from . import verify
-        scorer = verify.LeadScorer(gm.model_name, names, model.grid.lat, model.grid.lon, M, verify.default_truth(gm) if truth is None else truth,
-                                   climatology, channels, device=model.device, **ev)
-        if scenarios is not None:                          # the truth is a column of the Gram matrix: it must hold the scenario channels
-            from . import scenarios as scen
-            scen.check_scored(scenarios.get("channels") or [], scorer.scored)
-        if spectra is not None:                            # truth, error_mean and error_member need the truth of every spectrum channel
-            from . import spectra as spec
-            spec.check_scored([c for c in spectra.get("channels") or [] if c in names], scorer.scored)
-    tracker = None
-    if tracks:
-        from . import tracks as tracking
-        tracker = tracking.LeadTracker(gm.model_name, names, model.grid.lat, model.grid.lon, M, track_config, device=model.device)
-    deriver = dscorer = adapt = None
-    if derived is not None:                                # derived fields (skyrim_amd/derived.py): their own products, labelled with their names
-        from . import derived as deriving
-        dnames = list(derived)
-        deriver = deriving.LeadDeriver(names, model.grid.lat, model.grid.lon, M, dnames, device=model.device, surface=derived_surface)
-        # what every truth of these fields shares with the forecast: its thermodynamic columns, its kind of humidity and its surface mask
-        thermal = dict(column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=derived_surface)
-        (d_exceed, exceed), (d_quant, quantiles) = split_table(exceed, dnames), split_table(quantiles, dnames)
-        if scores:
-            adapt = deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device, levels=deriver.plan.levels or None,
-                                          **thermal)
-            dscorer = verify.LeadScorer(gm.model_name, dnames, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology, None,
-                                        device=model.device, adapt=adapt, **d_ev)
-            if spectra is not None:
-                spec.check_scored([c for c in spectra.get("channels") or [] if c in dnames], dscorer.scored)
-    ascorers = {}
-    if aggregator is not None and scores:                  # one scorer per window group, against the same aggregates of the truth
-        for g in aggregator.plan.groups:
-            inner = None if derived is None else deriving.TruthDeriver(dnames, model.grid.lat, model.grid.lon, device=model.device,
-                                                                       levels=deriver.plan.levels or None, **thermal)
-            hook = aggregate.TruthAggregator(g.requests, model.grid.lat, model.grid.lon, start_time, model.time_step, device=model.device,
-                                             inner=inner)
-            g_ev = split_table(a_events, g.fields)[0]
-            ascorers[g.label] = (hook, verify.LeadScorer(gm.model_name, g.fields, model.grid.lat, model.grid.lon, M, scorer.truth.src, climatology,
-                                                         None, device=model.device, adapt=hook,
-                                                         **(dict(events=g_ev, neighbourhoods_km=a_radii) if g_ev else {})))
-    regridder = rscorer = None
-    if grid is not None:                                   # the same products on the target grid (skyrim_amd/regrid.py)
-        from . import regrid
-        regridder = regrid.LeadRegridder(names, model.grid.lat, model.grid.lon, M, grid, regrid_method, device=model.device)
-        grid_label = regrid.grid_label(grid)
-        if scores:
-            rscorer = verify.LeadScorer(gm.model_name, names, regridder.lat_out, regridder.lon_out, M, scorer.truth.src, climatology, channels,
-                                        device=model.device,
-                                        adapt=regrid.TruthRegridder(model.grid.lat, model.grid.lon, grid, regrid_method, device=model.device),
-                                        **ev)
-    pointer, apointers = None, {}
-    if points is not None:                                 # every member at the points (skyrim_amd/points.py): raw channels and derived fields
-        from . import points as pointing                   # at each saved lead time, each aggregate group when a window closes
-        pts = pointing.Points(points)
-        pointer = pointing.LeadPoints(names, model.grid.lat, model.grid.lon, M, pts, point_channels if point_channels is not None else
-                                      (list(channels) if channels else None), point_method, model.device, list(derived or []), len(saved))
-        if aggregator is not None:
-            apointers = {g.label: pointing.LeadPoints(g.fields, model.grid.lat, model.grid.lon, M, pts, None, point_method, model.device, (),
-                                                      max(g.n_windows, 1)) for g in aggregator.plan.groups}
-    scenarist = None
-    if scenarios is not None:                              # clusters, EOFs and the energy score of the members (skyrim_amd/scenarios.py)
-        from . import scenarios as scen
-        sigma = None
-        if scenarios.get("normalise") == "std":
-            sigma = scenario_std(model, names)
-        scenarist = scen.LeadScenarios(names, model.grid.lat, model.grid.lon, M, scenarios, device=model.device, truth=scorer is not None,
-                                       std=sigma)
-    spectrist = dspectrist = None
-    if spectra is not None:                                # zonal power spectra of members, mean, spread and errors (skyrim_amd/spectra.py):
-        from . import spectra as spec                      # raw channels from the states, derived fields from the deriver's buffer
-        raw, der = ([c for c in spectra["channels"] if (c in names) == own] for own in (True, False))
-        if raw:
-            spectrist = spec.LeadSpectra(names, model.grid.lat, model.grid.lon, M, dict(spectra, channels=raw), device=model.device,
-                                         truth=scorer is not None)
-        if der:
-            dspectrist = spec.LeadSpectra(dnames, model.grid.lat, model.grid.lon, M, dict(spectra, channels=der), device=model.device,
-                                          truth=dscorer is not None)
-    objecter = None
-    if objects is not None:                                # labelled threshold regions of every member (skyrim_amd/objects.py): raw channels
-        from . import objects as objecting                 # from the states, derived fields from the deriver's buffer
-        objecter = objecting.LeadObjects(names, model.grid.lat, model.grid.lon, M, objects, model.device, list(derived or []),
-                                         model_name=gm.model_name)
-    hw = n_lat * n_lon
+    p = plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=events,
+                     neighbourhoods_km=neighbourhoods_km, scores=scores, points=points, point_channels=point_channels, point_method=point_method,
+                     scenarios=scenarios, spectra=spectra, objects=objects, breeding=breeding, stochastic=stochastic, aggregates=aggregates,
+                     derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
+                     length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels, perturb_scale=perturb_scale)
+    todo, families = stages(gm, p, start_time, truth, climatology, scores, tracks, track_config)
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
-    dev = x0.device
-    if dev.type != "cuda":
+    if x0.device.type != "cuda":
         raise RuntimeError("ensemble_forecast makes and reduces its members with HIP kernels: the model must be on a GPU")
     forget_resident(model, closed=False)                   # the interleaved loops below are not a state a later rollout continues from
     std = channel_std(model)
     if std.numel() != x0.shape[2]:
         raise ValueError(f"channel_std holds {std.numel()} values for {x0.shape[2]} input channels")
     cfg = save_config_with_id(save_config)
-    fid = cfg["forecast_id"]
-
-    sigma_all = std                                        # (breeding normalises with every channel's own sigma)
-    if plan.channel_mask is not None and plan.kind == "white":
-        std = torch.where(torch.from_numpy(plan.channel_mask).to(dev), std, torch.zeros_like(std))        # amplitude exactly 0 elsewhere
-    spherical = noise.Perturber(plan, x0, std, float(perturb_scale), int(seed)) if plan.kind == "spherical" else None
-
-    def seed_member(m, xm):
-        if spherical is not None:
-            spherical.member(m, xm)
-        else:
-            perturb(x0, std, xm, hw, float(perturb_scale), int(seed), m)
-
-    breeder = None
-    if bplan is not None:                                  # the seeds bred through the model (skyrim_amd/breeding.py): they replace the seeds
-        breeder = breed.Breeder(model, bplan, x0, sigma_all, float(perturb_scale), int(seed), start_time, seed_member, mask=plan.channel_mask)
-        breeder.run(M)
-        forget_resident(model, closed=False)
-    loops, current, stepper = [], [], None
-    if splan is not None:                                  # per-step perturbations (skyrim_amd/stochastic.py): the members are held as states,
-        from .breeding import step_once                    # each lead is the model's own lead 1 from the perturbed state before it
-        stepper = stoch.Stepper(splan, dev, x0.shape[2:], sigma_all, M, int(seed), float(perturb_scale))
-    for m in range(M):
-        if breeder is not None:
-            xm = breeder.member(m)
-        else:
-            xm = torch.empty_like(x0)
-            seed_member(m, xm)
-        if stepper is not None:
-            current.append(xm)
-        else:
-            loops.append(model(start_time, xm))
-        del xm
-    breeding_growth = None if breeder is None else breeder.growth
-    del x0, spherical, breeder, sigma_all                  # (with them the work buffers of one member's synthesis and of the cycle)
-    times, paths, source = [], [], gm.source_label
-    lat, lon, n_saved = model.grid.lat, model.grid.lon, len(saved)
-    family = functools.partial(ProductSet, gm.model_name, M, products, dev)
-    raw_set = family(names, lat, lon, n_saved, exceed, quantiles, keep_members, always=("mean",))
-    derived_set = regrid_set = None
-    agg_sets = {}                                          # {window label: (its set, the ends of its closed windows, their starts)}
-    if deriver is not None:
-        derived_set = family(dnames, lat, lon, n_saved, d_exceed, d_quant, keep_members, "derived-")
-    if aggregator is not None:                             # per window group: one entry per complete window
-        for g in aggregator.plan.groups:
-            own = [split_table(t, g.fields)[0] for t in (a_exceed, a_quant)]
-            agg_sets[g.label] = (family(g.fields, lat, lon, g.n_windows, *own, keep_members, f"agg{g.label}-"), [], [])
-        agg_derived = any(r.channel in (derived or []) for r in aggregator.plan.requests)
-    if regridder is not None:
-        regrid_set = family(names, regridder.lat_out, regridder.lon_out, n_saved, exceed, quantiles, keep_regridded, "regrid-")
+    fid, paths, source = cfg["forecast_id"], [], gm.source_label
+    sink = (cfg, paths) if save else None                  # where the stages write
+    seeds, growth = seed_members(model, p, x0, std, float(perturb_scale), start_time)
+    # per-step perturbations (skyrim_amd/stochastic.py): the members are held as states, each lead the model's own lead 1 from the perturbed one before
+    stepper = Stepper(p.stochastic, x0.device, x0.shape[2:], std, p.M, int(seed), float(perturb_scale)) if p.stochastic is not None else None
+    members = Members(model, start_time, seeds, stepper)
+    del x0, seeds                                          # (only the members' current states stay alive on the GPU)
+    for family in families:
+        family.products = family.make()
+    stored = [f for f in families if f.starts is None]     # raw, derived, regridded: their entries are the saved leads
     try:
         for k in range(n_steps + 1):
-            states, time = [], None
-            for m, loop in enumerate(loops):
-                try:
-                    time, out, _ = next(loop)
-                except FloatingPointError as e:
-                    raise FloatingPointError(f"ensemble member {m}, step {k}: {e}") from e
-                states.append((out[0] if out.dim() == 4 else out).contiguous())
-            if stepper is not None:
-                time = start_time + k * model.time_step
-                for m in range(M):
-                    if k >= 1:
-                        xp = current[m]
-                        xn = step_once(model, time - model.time_step, xp, f"ensemble member {m}, step {k}")
-                        stepper.advance(k, m, xp[0, 0], xn)           # in place on xn; member 0 is left as the model made it
-                        current[m] = xn.reshape(xp.shape)
-                        del xp, xn
-                    states.append(current[m][0, 0])
-            table = member_table(states)
-            keep = k in saved
-            s = saved.index(k) if keep else None
-            raw_set.reduce(states, table, s)               # every step: a non-finite member makes the mean non-finite, one flag to read
-            if not bool(torch.isfinite(raw_set.dev["mean"]).all().item()):
-                bad = [m for m, st in enumerate(states) if not bool(torch.isfinite(st).all().item())]
-                raise FloatingPointError(f"non-finite values in ensemble member(s) {bad} after step {k}")
-            if keep:
-                times.append(time)
-            if scorer is not None:
-                scorer.add(time, states, table)            # the same states and table: one more read of the members, one of the truth
-            if tracker is not None:
-                tracker.add(time, states, table)           # cyclone candidates of this lead time: only their records leave the device
-            fold_derived = aggregator is not None and agg_derived and k >= 1
-            if deriver is not None and (keep or dscorer is not None or fold_derived):      # (``objecter`` reads the derived planes of saved leads)
-                dstates, dtable = deriver.add(states, table)      # ONE launch: D derived planes per member, read below like raw channels
-                if dscorer is not None:
-                    dscorer.add(time, dstates, dtable)
-                if dspectrist is not None and keep:        # the derived planes are (D, H, W) states with a member table of their own
-                    dspectrist.add(time, dstates, dtable, dscorer.truth_state() if dscorer is not None else None)
-                if keep:
-                    derived_set.reduce(dstates, dtable, s)
-            if scenarist is not None and keep:             # one Gram launch, its M' x M' doubles to the host, cluster means, EOF patterns
-                scenarist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
-            if spectrist is not None and keep:             # one launch, nc x nb x kinds x K doubles to the host
-                spectrist.add(time, states, table, scorer.truth_state() if scorer is not None else None)
-            if objecter is not None and keep:              # label, attributes, probability: records and count planes leave the device
-                objecter.add(time, states, table, (dstates, dtable) if objecter.needs_derived else None,
-                             scorer.truth_state() if scorer is not None else None,
-                             dscorer.truth_state() if dscorer is not None else None,
-                             None if scorer is None else list(scorer.scored) + (list(dscorer.scored) if dscorer is not None else []))
-            if pointer is not None and keep:               # the members where they lie: one launch per source buffer, only the values leave
-                pointer.add(time, states, table, (dstates, dtable) if pointer.needs_derived else None)
-            if aggregator is not None and k >= 1:          # (step 0, the initial state, belongs to no window)
-                for c in aggregator.add(k, time, states, table, (dstates, dtable) if fold_derived else None):
-                    agg_set, ends, starts = agg_sets[c.label]
-                    ends.append(c.end)                     # windows close independently of ``save_every``
-                    starts.append(c.start)
-                    agg_set.reduce(c.states, c.table, c.window)
-                    if c.label in apointers:
-                        apointers[c.label].add(c.end, c.states, c.table)
-                    if c.label in ascorers:
-                        hook, asc = ascorers[c.label]
-                        hook.window(c.times)               # the truth is aggregated over the same valid times
-                        asc.add(c.end, c.states, c.table)
-                    if save:                               # one file per closed window, without the ``window_start`` coordinate
-                        paths += agg_set.save(c.window, [c.end], c.start, gm.source_label, cfg)
-            if regridder is not None and (keep or rscorer is not None):
-                rstates, rtable = regridder.add(states, table)    # ONE launch: every channel of every member on the target grid
-                if rscorer is not None:
-                    rscorer.add(time, rstates, rtable)
-                if keep:
-                    regrid_set.reduce(rstates, rtable, s)
-            if keep and save and s >= 1:                   # files of two entries: the step saved before and this one
-                for family_set in (raw_set, derived_set, regrid_set):
-                    if family_set is not None:
-                        paths += family_set.save(s - 1, times[s - 1:s + 1], times[s - 1], source, cfg)
+            time, states = members.advance(k)
+            s = p.saved.index(k) if k in p.saved else None
+            lead = SimpleNamespace(k=k, time=time, slot=s, states=states, table=member_table(states), sink=sink, truth=None, derived=None, dtruth=None)
+            for stage in todo:
+                if stage.add is not None and stage.due(lead):
+                    stage.add(lead)
+            if save and s:                                 # from the second saved step on: files of two entries, the step saved before and this one
+                for family in stored:
+                    paths += family.products.save(s - 1, family.times[s - 1:s + 1], family.times[s - 1], source, cfg)
                 source = "file"
-            del states, table
+            del lead, states
     finally:
-        for loop in loops:
-            try:
-                loop.close()
-            except FloatingPointError:
-                pass                                       # every delivered step was checked above, by member
-        forget_resident(model)
+        try:
+            members.close()
+        finally:
+            forget_resident(model)
 
-    ens = EnsembleForecast(gm.model_name, M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=plan.kind,
-                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=plan.lmax if plan.kind == "spherical" else None,
-                           breeding=None if bplan is None else bplan.as_dict(), breeding_growth=breeding_growth,
-                           stochastic=None if splan is None else splan.as_dict())
-    if scorer is not None:
-        ens.scores = _stamped(scorer, fid)
-        if save:
-            _save_result(ens.scores, cfg, paths)
-    if tracker is not None:
-        ens.tracks = _stamped(tracker, fid)
-        if save:
-            _save_result(ens.tracks, cfg, paths)
-    raw_set.fill(ens, times, channels)
-    if deriver is not None:
-        ens.derived = deriving.DerivedProducts(dnames)
-        derived_set.fill(ens.derived, times)
-        if dscorer is not None:
-            ens.derived.scores = _stamped(dscorer, fid)
-            ens.derived.dropped = dict(adapt.dropped)
-    if regridder is not None:
-        ens.regridded = regrid.RegriddedProducts(regridder.lat_out, regridder.lon_out, regrid_method)
-        regrid_set.fill(ens.regridded, times, channels)
-        if rscorer is not None:
-            ens.regridded.scores = _stamped(rscorer, fid)
-            ens.regridded.scores.grid = grid_label
-    if aggregator is not None:
-        for g in aggregator.plan.groups:
-            agg_set, ends, starts = agg_sets[g.label]
-            prod = aggregate.AggregatedProducts(g.label, list(g.fields))
-            agg_set.fill(prod, ends, window_start=starts)
-            prod.incomplete = aggregator.incomplete.get(g.label)
-            if g.label in apointers:
-                prod.points = apointers[g.label].result(f"{gm.model_name}-ens{M}-agg{g.label}", fid, window_start=starts)
-            if g.label in ascorers:
-                hook, asc = ascorers[g.label]
-                prod.scores = _stamped(asc, fid)
-                prod.dropped = dict(hook.dropped)
-            ens.aggregated[g.label] = prod
-    if scenarist is not None:
-        ens.scenarios = scenarist.result(f"{gm.model_name}-ens{M}", fid)
-    if spectrist is not None or dspectrist is not None:
-        parts = [s.result(f"{gm.model_name}-ens{M}", fid) for s in (spectrist, dspectrist) if s is not None]
-        ens.spectra = spec.merge(parts, spectra["channels"])
-    if objecter is not None:
-        ens.objects = _stamped(objecter, fid)
-        if save:
-            _save_result(ens.objects, cfg, paths)
-    if pointer is not None:
-        ens.points = pointer.result(f"{gm.model_name}-ens{M}", fid)
-        if save:
-            _save_result(ens.points, cfg, paths)
+    ens = EnsembleForecast(gm.model_name, p.M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=p.noise.kind,
+                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=p.noise.lmax if p.noise.kind == "spherical" else None,
+                           breeding=None if p.breeding is None else p.breeding.as_dict(), breeding_growth=growth,
+                           stochastic=None if p.stochastic is None else p.stochastic.as_dict())
+    for stage in todo:
+        if stage.finish is not None:
+            stage.finish(ens, fid, sink)
     return ens

@@ -357,3 +357,64 @@ def test_command_lines():
     assert set(e) - set(f) == {"members", "perturb_scale", "seed"}
     assert e["members"].opts == ["--members", "-n"] and e["members"].default == 10
     assert e["perturb_scale"].default == 1e-3 and e["seed"].default == 0
+
+
+# ---- 5. the member source: one generator per member behind ``advance`` / ``close`` ------------------------------------------------------ #
+class _Fake:
+    """A CPU "model": ``model(time, x)`` is a generator of (time, out, None) whose state at lead k is ``x + k``; ``fail`` = (the first
+    element of the seed that fails, the lead it fails at); ``on_close``: what the generator of the seed ``on_close[0]`` raises when closed."""
+    time_step = datetime.timedelta(hours=6)
+
+    def __init__(self, fail=None, on_close=None):
+        self.fail, self.on_close, self.closed = fail, on_close, []
+
+    def __call__(self, time, x):
+        who = int(x.flatten()[0])
+        try:
+            for k in range(100):
+                if self.fail == (who, k):
+                    raise FloatingPointError("non-finite values after the step")
+                yield time + k * self.time_step, (x + k).reshape(1, 2, 3, 4), None
+        finally:
+            self.closed.append(who)
+            if self.on_close is not None and self.on_close[0] == who:
+                raise self.on_close[1]
+
+
+def _seeds(M=3):
+    return [torch.full((1, 1, 2, 3, 4), float(10 * m)) for m in range(M)]
+
+
+def test_member_source_advances_all_members_in_order():
+    model = _Fake()
+    members = E.Members(model, T0, _seeds())
+    for k in range(3):
+        time, states = members.advance(k)
+        assert time == T0 + k * model.time_step and len(states) == 3
+        for m, st in enumerate(states):
+            assert st.shape == (2, 3, 4) and st.is_contiguous() and torch.equal(st, torch.full((2, 3, 4), 10.0 * m + k))
+    members.close()
+    assert model.closed == [0, 10, 20]
+
+
+def test_member_source_names_the_member_and_step_that_failed():
+    members = E.Members(_Fake(fail=(20, 1)), T0, _seeds())
+    members.advance(0)
+    with pytest.raises(FloatingPointError, match=r"^ensemble member 2, step 1: non-finite values after the step$"):
+        members.advance(1)
+    members.close()
+
+
+@pytest.mark.parametrize("error", [FloatingPointError("a pending check"), RuntimeError("a loop that will not close")])
+def test_member_source_closes_every_loop_when_one_raises(error):
+    """The second generator raises when it is closed: the third is closed all the same.  A loop's own pending non-finite check is
+    dropped (every delivered step was checked by member); anything else comes out once every loop is closed."""
+    model = _Fake(on_close=(10, error))
+    members = E.Members(model, T0, _seeds())
+    members.advance(0)
+    if isinstance(error, FloatingPointError):
+        members.close()
+    else:
+        with pytest.raises(RuntimeError, match="will not close"):
+            members.close()
+    assert model.closed == [0, 10, 20]

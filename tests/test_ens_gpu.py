@@ -221,6 +221,51 @@ def test_stats_launches_per_step(pangu, monkeypatch):
         assert [sorted(s) for s in got] == want, case
 
 
+LAUNCH_KW = dict(n_members=3, n_steps=4, save_every=2, products=("mean", "spread"))
+LAUNCH_REQUESTS = {
+    # everything that combines: every family but the regridded one, every per-lead consumer
+    "A": dict(LAUNCH_KW, exceed={"t2m": [280.0], "ws10m": [8.0], "t2m_max_12h": [285.0]}, quantiles={"msl": [0.5]}, derived=["ws10m"],
+              aggregates=["t2m:max:12h"], scores=True, events=True, neighbourhoods_km=[500.0], tracks=True,
+              track_config=dict(lat_max=60.0, r_msl_km=1700.0, r_vort_km=1000.0, r_wind_km=1300.0, r_core_km=1100.0),   # radii for 3.75 degrees
+              points={"node": (45.0, 30.0), "Istanbul": (41.01, 28.98)}, scenarios={"channels": ["z500"], "n_clusters": 2, "n_eofs": 2},
+              spectra={"channels": ["t2m", "ws10m"]}, objects={"msl": {"below": [101000.0]}, "ws10m": {"above": [8.0]}}),
+    # the regridded family, scored, its members kept
+    "B": dict(LAUNCH_KW, grid="15deg", scores=True, keep_members="regridded", exceed={"t2m": [280.0]}, quantiles={"msl": [0.5]}),
+    # members held as states: bred seeds, every step perturbed
+    "C": dict(LAUNCH_KW, breeding={"cycles": 2}, stochastic={"kind": "both"}),
+}
+LAUNCH_GOLDEN = Path(__file__).parent / "golden" / "ens_launch_sequence.json"
+
+
+def launch_sequence(monkeypatch, gm, **kw) -> list:
+    """The ``what`` of every C-ABI call of one ``ensemble_forecast``, in order: every binding reports its return code through
+    ``skyrim_amd.native.check``, the model's own steps included.  The request runs once before the recorded run, so that the tables a
+    process makes once (transform twiddles, prepared spectral weights) exist whatever ran before."""
+    from skyrim_amd import native
+    real, seen = native.check, []
+
+    def spy(code, what, lib=None):
+        seen.append(what)
+        return real(code, what, lib)
+    gm.ensemble_forecast(T0, **kw)
+    monkeypatch.setattr(native, "check", spy)
+    gm.ensemble_forecast(T0, **kw)
+    monkeypatch.undo()
+    return seen
+
+
+@pytest.mark.parametrize("case", sorted(LAUNCH_REQUESTS))
+def test_launch_sequence_is_the_recorded_one(pangu, monkeypatch, case):
+    """The driver is host code around fixed launches: which entry points it calls, and in which order, is
+    ``golden/ens_launch_sequence.json``, recorded with ``launch_sequence`` before the driver was rebuilt around its plan, member source,
+    families and consumers.  A reordering of consumers, a launch made twice or one left out shows here by name."""
+    import json
+    want = json.loads(LAUNCH_GOLDEN.read_text())[case]
+    got = launch_sequence(monkeypatch, pangu, **LAUNCH_REQUESTS[case])
+    first = next((i for i, (a, b) in enumerate(zip(got, want)) if a != b), min(len(got), len(want)))
+    assert got == want, f"request {case}: {len(got)} calls for {len(want)} recorded; first difference at call {first}: {got[first:first + 3]} for {want[first:first + 3]}"
+
+
 def test_ensemble_command_line(tmp_path):
     from click.testing import CliRunner
     from skyrim_amd.ensemble_cli import ensemble
