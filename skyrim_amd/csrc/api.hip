@@ -131,7 +131,7 @@ struct Engine : IEngine {
     bool rt_qkv = false;                    // row-tile QKV kernel (rowtile.hip)
     bool fused_block = false;               // proj + LayerNorm + residual + MLP as one kernel (fused_block.hip); mlp_mode 1: the split GEMMs
     bool fused_qa = true;                   // QKV + attention as ONE kernel, q / k / v in registers (attention.hip; SKP_SPLIT_ATTN=1: the two launches)
-    int plan2 = 0;                          // bit l: layer l + 1 runs proj / fc1 / fc2 with TWO terms (weights as one fp16 plane, fused_block2.hip)
+    int plan2 = 0;                          // bit l: layer l + 1 runs proj / fc1 / fc2 with TWO terms (weights as one fp16 plane, proj_mlp2_kernel in fused_block.hip)
     bool two_term(int layer) const { return (plan2 >> layer) & 1; }
     bool qkv_one(int layer) const { return rt_qkv && ((plan2 >> (4 + layer)) & 1); }   // QKV with ONE term (stream hi plane x weight hi plane)
     bool block_one(int layer) const { return (plan2 >> (8 + layer)) & 1; }             // proj / fc1 / fc2 with ONE term (activation hi plane x weight hi plane)

@@ -172,7 +172,7 @@ __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
 }
 __device__ __forceinline__ float gelu_erf(float x) { return gelu_erf2((f32x2){x, x}).x; }
 // The same polynomial in Estrin form: 4 + 2 + 1 FMAs in three levels instead of a chain of 7 dependent ones.  Where the evaluation is
-// spliced between MFMAs (fused_block2.hip) the dependent v_pk_fma chain of the Horner form costs a wait state per link; the Estrin
+// spliced between MFMAs (fused_block.hip) the dependent v_pk_fma chain of the Horner form costs a wait state per link; the Estrin
 // form leaves the scheduler independent work at every level.  Same coefficients; the results differ by fp32 rounding only.
 __device__ __forceinline__ f32x2 gelu_erf2e(f32x2 x) {
     f32x2 a;

@@ -1,4 +1,4 @@
-// The register-resident MLP of the block kernels (fused_block.hip, fused_block2.hip), and the weight preparation it needs:
+// The register-resident MLP of the block kernels (fused_block.hip), and the weight preparation it needs:
 //
 //     x += LayerNorm(norm2)( fc2( GELU( fc1(x) ) ) )   in place on the residual planes.
 //
@@ -43,7 +43,7 @@
 namespace skp {
 
 // ---- prepare: fp32 master weights -> fragment-order hi/lo planes ---------------------------------------------------------------- //
-//   (planes = 1: the hi plane only, blocks [(j KS + ks) 2 + n] and [j CF + c] -- fused_block2.hip)
+//   (planes = 1: the hi plane only, blocks [(j KS + ks) 2 + n] and [j CF + c] -- proj_mlp2_kernel)
 //   w1f[((j KS + ks) 2 + n) 2 + plane][lane][e] = fc1.weight[32 j + 16 n + (lane & 15)][32 ks + 8 (lane >> 4) + e]
 //   w2f[(j CF + c) 2 + plane][lane][e]          = fc2.weight[perm8_col(16 c + (lane & 15))][32 j + 16 (e >> 2) + 4 (lane >> 4) + (e & 3)]
 template <class T>

@@ -25,7 +25,7 @@ struct BlockW {
     LinW<T> qkv, proj, fc1, fc2;
     const T *w1f, *w2f;      // fc1 / fc2 in the fused MLP's fragment order (prep_mlp_weights: the block kernel, fused_block.hip), or null
     const T *projf, *qkvf;   // proj / qkv in the row-tile fragment order (prep_rowtile_weights: fused_block.hip / rowtile.hip), or null
-    const T *projh, *w1h, *w2h;   // proj / fc1 / fc2 in fragment order, HI PLANE ONLY: the two-term block kernel (fused_block2.hip), or null
+    const T *projh, *w1h, *w2h;   // proj / fc1 / fc2 in fragment order, HI PLANE ONLY: the two-term block kernel (proj_mlp2_kernel, fused_block.hip), or null
     const T* qkvh;                // qkv in fragment order, hi plane only: the one-term QKV of the term plan, or null
     const float *qkv_b, *proj_b, *fc1_b, *fc2_b, *n1_g, *n1_b, *n2_g, *n2_b;
     const f16* bias_cmp;     // [types][heads][144][24] compact, w reversed (+ shifted-window mask on odd blocks): the attention kernels
@@ -97,7 +97,7 @@ template <class T> hipError_t prep_rowtile_weights(const float* w, T* wf, int N,
 hipError_t op_qkv_attention(const Geom&, const BlockW<f16>&, const int* widx, int res, const f16* Xs, const Work<PrecF16x3>&, hipStream_t, int out_planes);
 // proj + LayerNorm + residual + MLP + LayerNorm + residual in one kernel (fused_block.hip): weights from prep_rowtile_weights / prep_mlp_weights
 template <class P> hipError_t op_proj_mlp_fused(const Geom&, const BlockW<typename P::T>&, const int* winv, int res, typename P::T* Xs, const Work<P>&, hipStream_t);
-// the same with the weights as ONE fp16 plane: two MFMA terms, or -- `one` -- a single term (activation operands as one fp16 plane too) (fused_block2.hip)
+// the same with the weights as ONE fp16 plane: two MFMA terms, or -- `one` -- a single term (activation operands as one fp16 plane too) (proj_mlp2_kernel, fused_block.hip)
 hipError_t op_proj_mlp2(const Geom&, const BlockW<f16>&, const int* winv, int res, f16* Xs, const Work<PrecF16x3>&, hipStream_t, int one = 0);
 template <class T, int NPL> hipError_t split_planes(const float* x, T* planes, long long plane, long long n, int C, hipStream_t);
 template <class T> hipError_t merge_planes(const T* planes, long long plane, float* x, long long n, int C, hipStream_t);

@@ -17,7 +17,7 @@
 // 32 bp + 8 (lane >> 4) + [0..7]: exactly an input fragment of the NEXT pair, so TAIL chains two pairs without leaving registers.
 // Activations are [C][HW] fp32 (pixels contiguous): a fragment is fetched with 8 dword loads per lane (16 consecutive pixels
 // of 4 x 8 channels per instruction) and stored the same way.  HW must be a multiple of 16.  gfx950 only.
-#include "gemm_dma.h"
+#include "blockrow.h"
 #include "moments.h"
 #include "../../include/skyrim_sfno.h"
 
@@ -145,20 +145,8 @@ __device__ __forceinline__ void run_pair(const v8 (&xh)[S::FM][KS], const v8 (&x
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        // bias + GELU + hi/lo split: the lane's hidden units 16 n + 4 g + r of the chunk are k-slots 4 n + r of the contracting layer
         uint4 hh[FM], hl[FM];
-        {
-            const float4 bb0 = *reinterpret_cast<const float4*>(b1 + j * 32 + 4 * g), bb1 = *reinterpret_cast<const float4*>(b1 + j * 32 + 16 + 4 * g);
-#pragma unroll
-            for (int t = 0; t < FM; ++t) {
-                const f32x2 a0 = gelu_erf2(f32x2{hacc[t][0][0] + bb0.x, hacc[t][0][1] + bb0.y}), a1 = gelu_erf2(f32x2{hacc[t][0][2] + bb0.z, hacc[t][0][3] + bb0.w});
-                const f32x2 a2 = gelu_erf2(f32x2{hacc[t][1][0] + bb1.x, hacc[t][1][1] + bb1.y}), a3 = gelu_erf2(f32x2{hacc[t][1][2] + bb1.z, hacc[t][1][3] + bb1.w});
-                const float v[8] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y, a3.x, a3.y};
-                uint4 o[2];
-                split8<f16, 2>(v, o);
-                hh[t] = o[0]; hl[t] = o[1];
-            }
-        }
+        blk_gelu_split<f16, FM>(hacc, b1, j, g, hh, hl);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                               // W2 block j landed; every wave is done with W1 block j
         if (j + 1 < NCH) dma_blocks<W1_BLK, S::NWAVES>(w1f + ((long long)(j + 1) * W1_BLK << 9), ldsA, wave, lane);

@@ -517,7 +517,7 @@ def test_fused_mlp_kernel_matches_the_two_gemm_path_and_the_oracle(toy, ref):
 
 @pytest.mark.parametrize("plan", [0x00, 0x05, 0x0A, 0x0F, 0xF0, 0xFF])
 def test_per_layer_term_plan(toy, ref, plan):
-    """skpangu_config.term_plan: bit l = layer l + 1 runs proj / fc1 / fc2 with two MFMA terms (csrc/fused_block2.hip), bit 4 + l its QKV
+    """skpangu_config.term_plan: bit l = layer l + 1 runs proj / fc1 / fc2 with two MFMA terms (proj_mlp2_kernel, csrc/fused_block.hip), bit 4 + l its QKV
     with one.  Every plan stays inside the bar; a layer that keeps its lo planes is bit-identical to the three-term engine's block, a layer
     that drops them is not; the error grows with the number of rounded weight sets."""
     from skyrim_amd.pangu.engine import PanguEngine
@@ -658,7 +658,7 @@ def test_compensated_rounding_of_the_one_plane_weights(toy, ref):
 
 def test_one_term_block_gemms_in_the_coarse_layers(toy, ref):
     """Term-plan bits 8-11 (include/skyrim_pangu.h): proj / fc1 / fc2 of a layer with ONE MFMA term -- the activation operands too as their
-    fp16 hi plane (csrc/fused_block2.hip, ONE).  "f16x1m" = f16x2m with layers 2 / 3 (12 of 16 blocks) in that form.  With the weights
+    fp16 hi plane (csrc/fused_block.hip, ONE).  "f16x1m" = f16x2m with layers 2 / 3 (12 of 16 blocks) in that form.  With the weights
     fitted to the rounded operands (rounding="compensated") the step stays near the three-term error; the oracle emulation of exactly
     this plan: 1.3e-4 against 6.5e-5."""
     from skyrim_amd.pangu.engine import PanguEngine, TERM_PLANS

@@ -17,9 +17,9 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not
 
 @pytest.fixture(scope="module")
 def resources():
-    """{mangled kernel name: {"vgprs", "scratch", "occupancy"}} of fused_block2.hip and attention.hip"""
+    """{mangled kernel name: {"vgprs", "scratch", "occupancy"}} of fused_block.hip and attention.hip"""
     out = {}
-    for f in ("fused_block2", "attention"):
+    for f in ("fused_block", "attention"):
         r = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-c", f"{f}.hip", "-o", "/dev/null",
                             "-Rpass-analysis=kernel-resource-usage"], cwd=CSRC, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
@@ -47,6 +47,16 @@ def _one(resources, *parts):
 def test_block_kernel_uses_no_scratch_at_two_waves_per_simd(resources, shape):
     r = _one(resources, "proj_mlp2_kernel", f"Blk2ShapeI{shape}")
     assert r["scratch"] == 0, r
+    assert r["occupancy"] == 2 and r["vgprs"] <= 256, r
+
+
+# <T, C, FM, NWAVES, WPE> of the three-term kernel (bf16x3, term_plan 0, the load-time guard's fall-back) and its scratch before it was
+# put on the two-term kernel's ring and stages (docs/experiments.md, "Pangu block kernels on shared stages"): sharing code may not add to it
+@pytest.mark.parametrize("shape, cap", [("IDF16bNS_10BlockShapeILi192ELi2ELi4ELi2E", 396), ("IDF16bNS_10BlockShapeILi384ELi1ELi8ELi2E", 396),
+                                        ("IDF16_NS_10BlockShapeILi192ELi2ELi4ELi2E", 396), ("IDF16_NS_10BlockShapeILi384ELi1ELi8ELi2E", 444)])
+def test_three_term_block_kernel_scratch_stays_at_or_below_its_figure(resources, shape, cap):
+    r = _one(resources, "proj_mlp_kernel", shape)
+    assert r["scratch"] <= cap, r
     assert r["occupancy"] == 2 and r["vgprs"] <= 256, r
 
 

@@ -1,5 +1,5 @@
-// Timing + checksum harness for the row-tile block kernel (csrc/fused_block2.hip) on synthetic buffers, no Python:
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I skyrim_amd/csrc [-DBLOCK_SRC='"path/to/other/fused_block2.hip"'] tools/micro/block_probe.hip -o tools/micro/block_probe
+// Timing + checksum harness for the row-tile block kernel (proj_mlp2_kernel of csrc/fused_block.hip) on synthetic buffers, no Python:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I skyrim_amd/csrc [-DBLOCK_SRC='"path/to/other/fused_block.hip"'] tools/micro/block_probe.hip -o tools/micro/block_probe
 //   tools/micro/block_probe [iters]
 // Prints ms per launch and a bit-level checksum of the stream after ONE launch on a fixed input (two builds of the same arithmetic agree).
 #include <cstdio>
@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 #ifndef BLOCK_SRC
-#define BLOCK_SRC "../../skyrim_amd/csrc/fused_block2.hip"
+#define BLOCK_SRC "../../skyrim_amd/csrc/fused_block.hip"
 #endif
 #include BLOCK_SRC
 
@@ -46,9 +46,9 @@ static void run(const char* name, int C, int M, int iters) {
     for (int i = 0; i < M; ++i) hi[i] = (int)((((long long)(i / 12) * 7919) % (M / 12)) * 12 + i % 12);   // runs of 12 consecutive rows, like the window table's
     hipMemcpy(winv, hi.data(), (size_t)M * 4, hipMemcpyHostToDevice);
     // proj_b, g1, e1, b1 (4C), b2, g2, e2
-    Block2Args<f16> a{ao, plane, M, xs, plane, winv, pw, w1, w2, fb, fb + C, fb + 2 * C, fb + 3 * C, fb + 7 * C, fb + 8 * C, fb + 9 * C, 1e-5f};
+    BlockArgs<f16> a{ao, plane, M, xs, plane, winv, pw, w1, w2, fb, fb + C, fb + 2 * C, fb + 3 * C, fb + 7 * C, fb + 8 * C, fb + 9 * C, 1e-5f};
     hipMemcpy(xs, xs0, 2 * plane * 2, hipMemcpyDeviceToDevice);
-    hipError_t e = launch_blk2<f16, S>(a, 0);
+    hipError_t e = launch_rows<proj_mlp2_kernel<f16, S>, S>(a, 0);
     hipDeviceSynchronize();
     std::vector<uint16_t> o((size_t)2 * plane);
     hipMemcpy(o.data(), xs, 2 * plane * 2, hipMemcpyDeviceToHost);
@@ -61,9 +61,9 @@ static void run(const char* name, int C, int M, int iters) {
     }
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 2; ++i) launch_blk2<f16, S>(a, 0);
+    for (int i = 0; i < 2; ++i) launch_rows<proj_mlp2_kernel<f16, S>, S>(a, 0);
     hipEventRecord(e0);
-    for (int i = 0; i < iters; ++i) launch_blk2<f16, S>(a, 0);
+    for (int i = 0; i < iters; ++i) launch_rows<proj_mlp2_kernel<f16, S>, S>(a, 0);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms = 0;

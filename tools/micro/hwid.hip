@@ -1,6 +1,6 @@
 // Where do the waves of a workgroup land?  Every wave records HW_REG_HW_ID / HW_REG_XCC_ID and s_memtime at its start:
 //   hipcc --offload-arch=gfx950 -O2 tools/micro/hwid.hip -o tools/micro/hwid && tools/micro/hwid <threads per block> <blocks> <lds bytes>
-// Output per block: XCC, SE, CU and the SIMD of each wave -- the pairing of waves on a SIMD that fused_block2.hip's skew relies on,
+// Output per block: XCC, SE, CU and the SIMD of each wave -- the pairing of waves on a SIMD that fused_block.hip's two-term kernel relies on,
 // and the block -> CU order that decides which two workgroups share a CU.
 #include <hip/hip_runtime.h>
 #include <cstdio>
