@@ -496,6 +496,7 @@ class AggregatedProducts:
     dropped: dict = field(default_factory=dict)
     incomplete: object = None
     points: object = None        # points.PointForecast of the group's fields with ``points=...``
+    extremes: object = None      # extremes.Extremes of the group's fields with ``extremes={...}``, the slice chosen by each window's end
 
 
 def _labelled(arr, fields, ends, starts, lat, lon):

@@ -119,7 +119,7 @@ class GlobalModel:
                           save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
-                          scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None,
+                          scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None, extremes: dict | None = None,
                           breeding: dict | None = None, stochastic: dict | None = None,
                           aggregates: List[str] | None = None, derived_surface=None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
@@ -201,7 +201,12 @@ class GlobalModel:
         regions where a raw channel or a field of ``derived`` is beyond a threshold (skyrim_amd/objects.py): labelled and
         measured on the device, filtered on the host, with the fraction of members whose kept object covers each point; with
         ``scores=True`` the truth goes through the same kernels and ``Objects.verify()`` compares.  The ``objects.Objects`` land in
-        ``EnsembleForecast.objects``.  ``objects=None`` launches nothing."""
+        ``EnsembleForecast.objects``.  ``objects=None`` launches nothing.  ``extremes={"climate": Climate or path, "fields": [...], "efi": True,
+        "sot": [0.9, 0.1], "above": [0.95, 0.99], "below": [0.05], "floor": {"mucape": 0.0}}`` compares the members with a quantile climate
+        (skyrim_amd/climate.py) where they lie in HBM: the Extreme Forecast Index, the Shift of Tails and the fraction of members
+        beyond a climate percentile of raw channels and derived fields at the saved leads (``EnsembleForecast.extremes``) and of aggregates
+        when their window closes (``EnsembleForecast.aggregated[label].extremes``, the slice of the climate chosen by the window's end).
+        ``extremes=None`` launches nothing."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -226,6 +231,8 @@ class GlobalModel:
             extra["spectra"] = spectra
         if objects is not None:
             extra["objects"] = objects
+        if extremes is not None:
+            extra["extremes"] = extremes
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,
@@ -255,6 +262,19 @@ class GlobalModel:
         device is touched."""
         from ... import objects as objecting
         return objecting.objects_model(self, start_time, n_steps, objects, derived=derived, truth=truth, save=save, save_config=save_config)
+
+    def extremes_forecast(self, start_time: datetime.datetime, n_steps: int = 4, extremes: dict | None = None, derived: List[str] | None = None,
+                          save: bool = False, save_config: dict | None = None):
+        """The deterministic forecast at the lead times 0 .. ``n_steps`` against a quantile climate (skyrim_amd/extremes.py).
+        ``extremes``: the dict of ``ensemble_forecast(extremes=...)``; its fields are raw channels and fields of ``derived``.  One state is an
+        ensemble of one: the EFI is defined (and steps between -1 and 1 as the state crosses the climate's levels), the tail odds are 0 or 1,
+        a SOT is refused.  The model's TimeLoop is advanced and every state is compared where it lies in HBM; only the index planes cross
+        to the host.  Returns an ``extremes.Extremes``; ``save=True`` writes its files under the forecast id directory.  A request that
+        cannot be served is refused with ValueError before the device is touched."""
+        from ... import extremes as extreming
+        if extremes is None:
+            raise ValueError('extremes_forecast needs extremes: {"climate": Climate or path, "fields": [...], ...}')
+        return extreming.extremes_model(self, start_time, n_steps, extremes, derived=derived, save=save, save_config=save_config)
 
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields: List[str] = (), save: bool = False,
                       save_config: dict | None = None, derived_surface=None):

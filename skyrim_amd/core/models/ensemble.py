@@ -124,6 +124,10 @@ class GlobalEnsemble:
         raise ValueError(f"object_forecast finds the objects of the forecast of ONE model; {self!r} is a multi-model ensemble -- use its "
                          "saved ensemble-mean files with skyrim_amd.objects.objects_prediction, or build Skyrim(<one model name>)")
 
+    def extremes_forecast(self, *args, **kwargs):
+        raise ValueError(f"extremes_forecast compares the forecast of ONE model with a climate; {self!r} is a multi-model ensemble -- use its "
+                         "saved ensemble-mean files with skyrim_amd.extremes.extremes_prediction, or build Skyrim(<one model name>)")
+
     def derive_fields(self, *args, **kwargs):
         raise ValueError(f"derive_fields derives from the forecast of ONE model; {self!r} is a multi-model ensemble -- derive from its saved "
                          "ensemble-mean files with skyrim_amd.derived.derive_prediction, or build Skyrim(<one model name>)")

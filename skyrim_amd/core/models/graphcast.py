@@ -137,6 +137,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator object_forecast advances: "
                                   "find the objects of its forecast with skyrim_amd.objects.objects_prediction(forecast_or_saved_files, objects)")
 
+    def extremes_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator extremes_forecast advances: "
+                                  "compare its forecast with skyrim_amd.extremes.extremes_prediction(forecast_or_saved_files, extremes)")
+
     def derive_fields(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
                                   "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")

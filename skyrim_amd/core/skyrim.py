@@ -86,6 +86,19 @@ class Skyrim:
         from .. import objects as objecting
         return objecting.objects_prediction(pred, objects, device=device, **kwargs)
 
+    def extremes_forecast(self, start_time: datetime.datetime, n_steps: int = 4, extremes=None, **kwargs):
+        """The single model's forecast against a quantile climate -- the Extreme Forecast Index and the odds of leaving a climate
+        percentile -- as an ``extremes.Extremes`` (``GlobalModel.extremes_forecast`` has the arguments).
+        ``ensemble_forecast(..., extremes={...})`` compares every member and adds the Shift of Tails."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.extremes_forecast(start_time, n_steps=n_steps, extremes=extremes, **kwargs)
+
+    @staticmethod
+    def extremes_prediction(pred, extremes, derived=None, device="cuda:0"):
+        """The same for a forecast that is already in memory or on disk (``extremes.extremes_prediction``)."""
+        from .. import extremes as extreming
+        return extreming.extremes_prediction(pred, extremes, derived=derived, device=device)
+
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields=(), **kwargs):
         """Derived fields (wind speed, thickness, vorticity, divergence, vapour transport) of the single model's forecast as a
         DataArray(time, channel=fields, lat, lon) (``GlobalModel.derive_fields`` has the arguments).

@@ -271,6 +271,7 @@ class EnsembleForecast:
     breeding_growth: object = None      # (cycles, member, channel) float64 with ``breeding=``: breeding.Breeder.growth
     stochastic: object = None    # the normalised ``stochastic=`` request (stochastic.Plan.as_dict) or None
     objects: object = None       # objects.Objects with ``objects={...}``
+    extremes: object = None      # extremes.Extremes with ``extremes={...}``: raw channels and derived fields at the saved leads
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -303,14 +304,15 @@ def scenario_std(model, names) -> np.ndarray:
 # ``{family: {field: values}}`` with the families ``"raw"`` (the regridded channels share it), ``"derived"`` and ``"agg{label}"`` per window
 # group; ``radii``: the events' neighbourhoods, km; ``keep_members``: the raw, derived and aggregated ones; ``noise`` / ``breeding`` /
 # ``stochastic`` / ``aggregate``: the plans of those modules, or None; ``regrid``: ``regrid.Tables`` or None; ``points``: ``points.Points`` or
-# None; ``point_channels``: what is sampled there (``point_channels``, else ``channels``, else None = every raw channel).
+# None; ``point_channels``: what is sampled there (``point_channels``, else ``channels``, else None = every raw channel); ``extremes``: the
+# checked ``extremes.Request`` or None.
 Plan = make_dataclass("Plan", "asked M products saved names derived exceed quantiles events radii keep_members keep_regridded noise breeding "
-                      "stochastic aggregate regrid points point_channels".split())
+                      "stochastic aggregate regrid points point_channels extremes".split())
 
 
 def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
                  neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None,
-                 breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative",
+                 extremes=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative",
                  perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None, perturb_scale=None) -> Plan:
     """Every refusal that needs no device, in one fixed order, and the request normalised once: the ``Plan``.  The keywords are those of
     ``GlobalModel.ensemble_forecast`` (core/models/base.py describes them).  ``exceed`` and ``quantiles`` may name raw channels, fields
@@ -318,7 +320,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
     channels and derived fields, all on the model's own grid.  ``perturb_scale``: the default of ``stochastic``'s ``additive_scale``,
     which ``run`` passes and ``validate`` has not."""
     asked = SimpleNamespace(**locals())
-    from . import aggregate, breeding as breed, derived as deriving, noise, objects as objecting, points as pointing, regrid
+    from . import aggregate, breeding as breed, derived as deriving, extremes as extreming, noise, objects as objecting, points as pointing, regrid
     from . import scenarios as scen, spectra as spec, stochastic as stoch
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
@@ -391,6 +393,9 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
         spec.check_request(names + dnames, model.grid.lat, model.grid.lon, n_members, spectra, a_fields)
     if objects is not None:                                 # planes, members, the grid's axes; raw channels and derived fields of the model's grid
         objecting.check_request(names, model.grid.lat, model.grid.lon, n_members, objects, dnames)
+    xreq = None
+    if extremes is not None:                                # the climate, its fields and levels; raw channels, derived fields and aggregates of the model's grid
+        xreq = extreming.check_request(names, model.grid.lat, model.grid.lon, n_members, extremes, dnames, a_fields)
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
@@ -406,11 +411,11 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
     quantiles = {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}
     return Plan(asked, int(n_members), products, saved, names, dnames, _per_family(exceed, fields_of), _per_family(quantiles, fields_of),
                 _per_family(ev, fields_of), radii, bool(keep_members) and keep_members != "regridded", bool(keep_members) and grid is not None,
-                nplan, bplan, splan, aplan, tabs, pts, point_channels)
+                nplan, bplan, splan, aplan, tabs, pts, point_channels, xreq)
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, breeding=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, extremes=None, breeding=None,
              stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device (``plan_request``); returns (products, exceed, quantiles, saved step numbers) normalised."""
@@ -511,6 +516,7 @@ class Family:
 
     def __init__(self, make, hang, scorer=None, points=None, select=None, grid=None, windows=False):
         self.make, self.hang, self.scorer, self.points, self.select, self.grid = make, hang, scorer, points, select, grid
+        self.extremes = None                                # a window group's ``LeadExtremes``
         self.products, self.times, self.starts = None, [], [] if windows else None
 
     def score(self, time, states, table, window=None):
@@ -532,18 +538,23 @@ class Family:
         self.products.reduce(states, table, slot)
         if self.points is not None:
             self.points.add(time, states, table)
+        if self.extremes is not None and slot is not None:  # the slice of the climate is chosen by ``time``, a window's end
+            self.extremes.add(time, states, table)
 
     def lead(self, time, states, table, slot):
         """What a lead time is to a family whose states are made for it: the scores, then the products."""
         self.score(time, states, table)
         self.reduce(time, states, table, slot)
 
-    def fill(self, ens, fid, sink=None) -> None:
+    def fill(self, ens, fid, sink=None, xsink=None) -> None:
         """The labelled arrays, ``points``, ``scores``, the scores' ``grid`` and ``dropped`` on the family's object, where they apply."""
         target, ps = self.hang(ens), self.products
         ps.fill(target, self.times, self.select, window_start=self.starts)
         if self.points is not None:
             target.points = self.points.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid, window_start=self.starts)
+        if self.extremes is not None:
+            target.extremes = _hang(self.extremes.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid, window_start=self.starts),
+                                    fid, xsink)
         if self.scorer is not None:
             target.scores = _hang(self.scorer.result(), fid, sink)
             if self.grid is not None:
@@ -563,7 +574,8 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     ``add(L)`` is called where ``due(L)`` (default: at saved leads), ``finish(ens, fid, sink)`` once after the last lead.  ``L``, the record of
     a lead: ``k``, ``time``, ``slot`` (the entry of a saved lead, else None), ``states``, ``table``, ``sink`` (where files go) and, set by the
     stages before, ``truth`` (the raw scorer's truth state), ``derived`` = (states, table) of the deriver, ``dtruth``."""
-    from . import aggregate, derived as deriving, objects as objecting, points as pointing, regrid, scenarios as scen, spectra as spec
+    from . import aggregate, derived as deriving, extremes as extreming, objects as objecting, points as pointing, regrid, scenarios as scen
+    from . import spectra as spec
     from . import tracks as tracking, verify
     model, a, M, names, dnames, dev, n_saved = gm.model, p.asked, p.M, p.names, p.derived, gm.model.device, len(p.saved)
     lat, lon, label = model.grid.lat, model.grid.lon, f"{gm.model_name}-ens{M}"
@@ -620,6 +632,14 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     pointer = pointing.LeadPoints(names, lat, lon, M, p.points, p.point_channels, a.point_method, dev, dnames, n_saved) if p.points is not None else None
     for g in groups if p.points is not None else ():
         windowed[g.label].points = pointing.LeadPoints(g.fields, lat, lon, M, p.points, None, a.point_method, dev, (), max(g.n_windows, 1))
+    # EFI, SOT and tail odds against a quantile climate (skyrim_amd/extremes.py): raw channels and derived fields at each saved lead, a window
+    # group's fields when a window closes
+    x = p.extremes
+    extremist = extreming.LeadExtremes(names, lat, lon, M, x, dev, dnames) if x is not None and any(f in names + dnames for f in x.fields) else None
+    for g in groups if x is not None else ():
+        mine = [f for f in x.fields if f in g.fields]
+        if mine:
+            windowed[g.label].extremes = extreming.LeadExtremes(g.fields, lat, lon, M, x, dev, (), mine)
     # clusters, EOFs and the energy score of the members (skyrim_amd/scenarios.py)
     scenarist = scen.LeadScenarios(names, lat, lon, M, a.scenarios, device=dev, truth=scores, std=scenario_std(model, names) if a.scenarios.get(
         "normalise") == "std" else None) if a.scenarios is not None else None
@@ -667,8 +687,9 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
         (objecter, Stage(lambda L: objecter.add(L.time, L.states, L.table, L.derived, L.truth, L.dtruth, truth_names),
                          finish=hung("objects", lambda fid: objecter.result()))),
         (pointer, Stage(lambda L: pointer.add(L.time, L.states, L.table, L.derived), finish=hung("points", lambda fid: pointer.result(label, fid)))),
+        (extremist, Stage(lambda L: extremist.add(L.time, L.states, L.table, L.derived), finish=hung("extremes", lambda fid: extremist.result(label, fid)))),
         (aggregator, Stage(close_windows, lambda L: L.k >= 1,                  # (step 0, the initial state, belongs to no window)
-                           lambda ens, fid, sink: [group.fill(ens, fid) for group in windowed.values()])),
+                           lambda ens, fid, sink: [group.fill(ens, fid, xsink=sink) for group in windowed.values()])),
         (regridder, Stage(lambda L: regridded.lead(L.time, *regridder.add(L.states, L.table), L.slot),     # ONE launch: all channels, all members
                           lambda L: _saved(L) or regridded.scorer is not None, lambda ens, fid, sink: regridded.fill(ens, fid))),
     ]
@@ -679,7 +700,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description): the plan of the request, the stages of a
@@ -691,7 +712,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     model = gm.model
     p = plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=events,
                      neighbourhoods_km=neighbourhoods_km, scores=scores, points=points, point_channels=point_channels, point_method=point_method,
-                     scenarios=scenarios, spectra=spectra, objects=objects, breeding=breeding, stochastic=stochastic, aggregates=aggregates,
+                     scenarios=scenarios, spectra=spectra, objects=objects, extremes=extremes, breeding=breeding, stochastic=stochastic, aggregates=aggregates,
                      derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
                      length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels, perturb_scale=perturb_scale)
     todo, families = stages(gm, p, start_time, truth, climatology, scores, tracks, track_config)

@@ -29,6 +29,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     breed_norms / breed_apply                            (the two passes of a breeding cycle over M states, include/skyrim_breed.h)
     stoch_coeffs / stoch_evolve / stoch_apply            (per-step stochastic perturbations: SPPT and additive, include/skyrim_stoch.h)
     object_label / object_attributes / object_probability    (labelled threshold regions of M states, include/skyrim_object.h)
+    clim_extremes / clim_quantiles                       (EFI, SOT and tail odds of M states against a quantile climate; the climate from N samples, include/skyrim_clim.h)
 """
 from __future__ import annotations
 
@@ -583,6 +584,22 @@ def _agg_update(members, table, program, params, stamp: float, acc) -> None:
     aggregate.run(list(members), table, aggregate.decode(program, params), acc, stamp)
 
 
+# ---- climate-relative extremes ---------------------------------------------------------------------------------------------------------- #
+def _clim_extremes(members, table, channels, clim, levels, floor, sot_index, sot_frac, sot_ref, sot_base, prob_level, prob_below, efi, sot,
+                   prob) -> None:
+    """``clim``: (nf, Q, H, W); ``levels``: the Q probability levels; the four ``sot_*`` lists hold one entry per SOT request
+    (climate.sot_request), ``prob_level`` / ``prob_below`` one per tail-odds request; include/skyrim_clim.h has the arithmetic."""
+    from . import climate
+    climate.run_extremes(list(members), table, list(channels), clim, list(levels), list(floor) or None,
+                         list(zip(sot_index, sot_frac, sot_ref, sot_base)), list(zip(prob_level, prob_below)), efi, sot, prob)
+
+
+def _clim_quantiles(samples, table, channels, levels, clim) -> None:
+    """``clim``: (nf, Q, H, W), the ``levels`` (numpy's "linear" method) of the listed channels over the N samples."""
+    from . import climate
+    climate.run_quantiles(list(samples), table, list(channels), list(levels), clim)
+
+
 # ---- point extraction ------------------------------------------------------------------------------------------------------------------- #
 def _point_gather(members, table, channels, records, out) -> None:
     """``records``: points.device_records(...), int32 (P, 8); ``out``: (M, len(channels), P) or (M, stride >= len(channels) P)."""
@@ -765,6 +782,10 @@ _SCHEMAS = [
     ("object_attributes(Tensor[] members, Tensor table, int[] channels, float[] thresholds, int[] directions, int[] connectivity, float[] scales, "
      "int capacity, Tensor labels, Tensor ids, Tensor n_found, Tensor row_tables, Tensor col_tables, Tensor(a!) records) -> ()", _object_attributes),
     ("object_probability(Tensor ids, Tensor keep, Tensor(a!) counts) -> ()", _object_probability),
+    ("clim_extremes(Tensor[] members, Tensor table, int[] channels, Tensor clim, float[] levels, float[] floor, int[] sot_index, "
+     "float[] sot_frac, int[] sot_ref, int[] sot_base, int[] prob_level, bool[] prob_below, Tensor(a!)? efi, Tensor(b!)? sot, "
+     "Tensor(c!)? prob) -> ()", _clim_extremes),
+    ("clim_quantiles(Tensor[] samples, Tensor table, int[] channels, float[] levels, Tensor(a!) clim) -> ()", _clim_quantiles),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
