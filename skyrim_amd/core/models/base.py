@@ -120,7 +120,7 @@ class GlobalModel:
                           tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(),
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
                           scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None, extremes: dict | None = None,
-                          breeding: dict | None = None, stochastic: dict | None = None,
+                          archive: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
                           aggregates: List[str] | None = None, derived_surface=None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
@@ -206,7 +206,13 @@ class GlobalModel:
         (skyrim_amd/climate.py) where they lie in HBM: the Extreme Forecast Index, the Shift of Tails and the fraction of members
         beyond a climate percentile of raw channels and derived fields at the saved leads (``EnsembleForecast.extremes``) and of aggregates
         when their window closes (``EnsembleForecast.aggregated[label].extremes``, the slice of the climate chosen by the window's end).
-        ``extremes=None`` launches nothing."""
+        ``extremes=None`` launches nothing.  ``archive={"packing": "int16" | "float32", "channels": [...] | None, "dir": None}`` writes the
+        members themselves (skyrim_amd/archive.py): at each saved lead every member's listed channels (None: all) are
+        quantised plane by plane to 16-bit codes in the file's byte order on the device (``"float32"``: byte-swapped, lossless) and written
+        by threads of their own, one netCDF file per (member, lead) under ``<output_dir>/<forecast_id>/members/`` (or ``"dir"``) with a
+        ``manifest.json``; it needs ``save=True`` or a ``"dir"``.  ``EnsembleForecast.archive`` is the ``archive.MemberArchive``, whose
+        ``replay(**request)`` later runs every product that only reads states on the files, without the model.  ``archive=None`` launches
+        nothing."""
         from ... import ensemble
         extra = dict(tracks=True, track_config=track_config) if tracks else {}
         if events is not None:
@@ -233,6 +239,8 @@ class GlobalModel:
             extra["objects"] = objects
         if extremes is not None:
             extra["extremes"] = extremes
+        if archive is not None:
+            extra["archive"] = archive
         return ensemble.run(self, start_time, n_steps=n_steps, n_members=n_members, perturb_scale=perturb_scale, seed=seed, products=products,
                             exceed=exceed, quantiles=quantiles, channels=channels, save_every=save_every, keep_members=keep_members,
                             save=save, save_config=save_config, truth=truth, climatology=climatology, scores=scores,

@@ -43,6 +43,14 @@ class Skyrim:
         start_time = start_time.replace(second=0, microsecond=0)
         return self.model.ensemble_forecast(start_time, n_steps=n_steps, n_members=n_members, **kwargs)
 
+    @staticmethod
+    def open_archive(directory):
+        """The members ``ensemble_forecast(..., archive={...})`` wrote under ``directory`` as an ``archive.MemberArchive``: ``info()``,
+        ``member(m, k)``, ``states(k, device)`` and ``replay(**request)``, which makes the products of ``ensemble_forecast`` from the
+        files without running the model."""
+        from .. import archive
+        return archive.open(directory)
+
     def verify(self, start_time: datetime.datetime, n_steps: int = 4, **kwargs):
         """Scores of the single model's forecast against a truth at every lead time (``GlobalModel.verify`` has the arguments):
         bias, MAE, RMSE, CRPS and ACC per channel as a ``verify.Scores``.  ``ensemble_forecast(..., scores=True)`` scores an ensemble."""

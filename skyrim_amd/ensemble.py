@@ -12,6 +12,8 @@ Four layers:
   (skyrim_amd/breeding.py).  ``Members``: ONE TimeLoop generator per member advanced step-major (all members one step, then that lead
   time's statistics), so only the members' current states are alive on the GPU; with ``stochastic=`` the members are held as states
   and every step of every member but the control is perturbed (skyrim_amd/stochastic.py).  ``stages``: what a lead time sets off;
+  ``drive``: the leads of any member source with ``advance(k)`` and ``close()`` -- ``Members``, or the files of a forecast that was
+  written down (``archive.ArchiveMembers``, skyrim_amd/archive.py);
 * ``EnsembleForecast`` -- the labelled products, and their files in the layout of every other forecast of this package.
 
 Members sharded over ranks stay with ``skyrim_amd/pangu/ensemble.py``; multi-MODEL ensembles are ``core/models/ensemble.py``.
@@ -272,6 +274,7 @@ class EnsembleForecast:
     stochastic: object = None    # the normalised ``stochastic=`` request (stochastic.Plan.as_dict) or None
     objects: object = None       # objects.Objects with ``objects={...}``
     extremes: object = None      # extremes.Extremes with ``extremes={...}``: raw channels and derived fields at the saved leads
+    archive: object = None       # archive.MemberArchive with ``archive={...}``: the members themselves, one file per (member, saved lead)
 
 
 def product_model_name(model_name: str, n_members: int, product: str) -> str:
@@ -305,23 +308,24 @@ def scenario_std(model, names) -> np.ndarray:
 # group; ``radii``: the events' neighbourhoods, km; ``keep_members``: the raw, derived and aggregated ones; ``noise`` / ``breeding`` /
 # ``stochastic`` / ``aggregate``: the plans of those modules, or None; ``regrid``: ``regrid.Tables`` or None; ``points``: ``points.Points`` or
 # None; ``point_channels``: what is sampled there (``point_channels``, else ``channels``, else None = every raw channel); ``extremes``: the
-# checked ``extremes.Request`` or None.
+# checked ``extremes.Request`` or None; ``archive``: the checked ``archive=`` request (``archive.check_request``) or None.
 Plan = make_dataclass("Plan", "asked M products saved names derived exceed quantiles events radii keep_members keep_regridded noise breeding "
-                      "stochastic aggregate regrid points point_channels extremes".split())
+                      "stochastic aggregate regrid points point_channels extremes archive".split())
 
 
 def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
                  neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None,
-                 extremes=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative",
-                 perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None, perturb_scale=None) -> Plan:
+                 extremes=None, archive=None, save=False, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None,
+                 regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None,
+                 perturb_scale=None) -> Plan:
     """Every refusal that needs no device, in one fixed order, and the request normalised once: the ``Plan``.  The keywords are those of
     ``GlobalModel.ensemble_forecast`` (core/models/base.py describes them).  ``exceed`` and ``quantiles`` may name raw channels, fields
     of ``derived`` and aggregates (``ws10m_max_24h``), ``events`` too; ``scenarios`` takes raw channels, ``spectra`` and ``objects`` raw
     channels and derived fields, all on the model's own grid.  ``perturb_scale``: the default of ``stochastic``'s ``additive_scale``,
     which ``run`` passes and ``validate`` has not."""
     asked = SimpleNamespace(**locals())
-    from . import aggregate, breeding as breed, derived as deriving, extremes as extreming, noise, objects as objecting, points as pointing, regrid
-    from . import scenarios as scen, spectra as spec, stochastic as stoch
+    from . import aggregate, archive as archiving, breeding as breed, derived as deriving, extremes as extreming, noise, objects as objecting
+    from . import points as pointing, regrid, scenarios as scen, spectra as spec, stochastic as stoch
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
         raise NotImplementedError("ensemble_forecast runs all members on one GPU; under a process group of more than one rank use "
@@ -396,6 +400,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
     xreq = None
     if extremes is not None:                                # the climate, its fields and levels; raw channels, derived fields and aggregates of the model's grid
         xreq = extreming.check_request(names, model.grid.lat, model.grid.lon, n_members, extremes, dnames, a_fields)
+    areq = archiving.check_request(names, archive, save) if archive is not None else None      # the packing, its channels, somewhere to write
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
@@ -405,18 +410,19 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
             need += int(n_members) * len(saved) * len(names) * tabs.lat.size * tabs.lon.size * 4
         if need > _PINNED_LIMIT:
             raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
-                             f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every")
+                             f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every -- or archive={{...}}, which writes "
+                             "the members to files as they are made and replays them later (skyrim_amd/archive.py)")
     fields_of = dict({"derived": dnames} if dnames else {}, **{f"agg{g.label}": g.fields for g in groups})
     exceed = {k: [float(np.float32(v)) for v in vs] for k, vs in (exceed or {}).items()}
     quantiles = {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}
     return Plan(asked, int(n_members), products, saved, names, dnames, _per_family(exceed, fields_of), _per_family(quantiles, fields_of),
                 _per_family(ev, fields_of), radii, bool(keep_members) and keep_members != "regridded", bool(keep_members) and grid is not None,
-                nplan, bplan, splan, aplan, tabs, pts, point_channels, xreq)
+                nplan, bplan, splan, aplan, tabs, pts, point_channels, xreq, areq)
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
-             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, extremes=None, breeding=None,
-             stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None,
+             save=False, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device (``plan_request``); returns (products, exceed, quantiles, saved step numbers) normalised."""
     p = plan_request(**locals())
@@ -564,17 +570,19 @@ class Family:
 
 
 _saved = lambda L: L.slot is not None                      # noqa: E731
-Stage = collections.namedtuple("Stage", "add due finish", defaults=(None, _saved, None))
+Stage = collections.namedtuple("Stage", "add due finish close", defaults=(None, _saved, None, None))
 
 
 def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, tracks=False, track_config=None) -> tuple[list, list]:
     """(the stages of a lead time, the families: raw, derived, regridded, then the window groups).  THE place a product is wired in: its
     ``Lead*`` object is made here, in the order the refusals of these objects have, with the checks that need the truth, and it gets one
     ``Stage`` in the list at the end, whose order is the order of the launches of a lead (DESIGN.md 17 has the rules it keeps):
-    ``add(L)`` is called where ``due(L)`` (default: at saved leads), ``finish(ens, fid, sink)`` once after the last lead.  ``L``, the record of
+    ``add(L)`` is called where ``due(L)`` (default: at saved leads), ``finish(ens, fid, sink)`` once after the last lead, ``close()`` when
+    the leads are over, also after an error (a stage with threads or files of its own).  ``L``, the record of
     a lead: ``k``, ``time``, ``slot`` (the entry of a saved lead, else None), ``states``, ``table``, ``sink`` (where files go) and, set by the
     stages before, ``truth`` (the raw scorer's truth state), ``derived`` = (states, table) of the deriver, ``dtruth``."""
-    from . import aggregate, derived as deriving, extremes as extreming, objects as objecting, points as pointing, regrid, scenarios as scen
+    from . import aggregate, archive as archiving, derived as deriving, extremes as extreming, objects as objecting, points as pointing, regrid
+    from . import scenarios as scen
     from . import spectra as spec
     from . import tracks as tracking, verify
     model, a, M, names, dnames, dev, n_saved = gm.model, p.asked, p.M, p.names, p.derived, gm.model.device, len(p.saved)
@@ -650,6 +658,8 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     # labelled threshold regions of every member (skyrim_amd/objects.py): raw channels from the states, derived fields from the deriver's buffer
     objecter = objecting.LeadObjects(names, lat, lon, M, a.objects, dev, dnames, model_name=gm.model_name) if a.objects is not None else None
     truth_names = list(raw.scorer.scored) + (list(derived.scorer.scored) if derived is not None else []) if scores else None
+    # the members themselves, packed on the device and written by threads of their own (skyrim_amd/archive.py)
+    archiver = archiving.LeadArchive(gm, p, start_time) if p.archive is not None else None
 
     def raw_lead(L):                                       # first at every lead: a non-finite member makes the mean non-finite, one flag to read
         raw.reduce(L.time, L.states, L.table, L.slot)
@@ -675,6 +685,7 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     every = lambda L: True                                 # noqa: E731
     todo = [                                               # (wanted?, the stage) in the order of a lead time
         (True, Stage(raw_lead, every, raw.fill)),
+        (archiver, Stage(lambda L: archiver.add(L), finish=lambda ens, fid, sink: archiver.finish(ens), close=lambda: archiver.close())),
         (tracker, Stage(lambda L: tracker.add(L.time, L.states, L.table), every, hung("tracks", lambda fid: tracker.result()))),      # (a track needs every lead)
         (deriver, Stage(derive, lambda L: _saved(L) or derived.scorer is not None or (folds_derived and L.k >= 1))),
         (spectrists.get("derived"), Stage(lambda L: spectrists["derived"].add(L.time, *L.derived, L.dtruth))),
@@ -700,20 +711,19 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description): the plan of the request, the stages of a
-    lead time, the seeded members, then lead by lead every stage that is due."""
-    from .common import save_config_with_id
+    lead time, the seeded members (the member source), then ``drive``: lead by lead every stage that is due."""
     from .datasource import get_initial_condition_for_model
     from .leads import forget_resident
     from .stochastic import Stepper
     model = gm.model
     p = plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=events,
                      neighbourhoods_km=neighbourhoods_km, scores=scores, points=points, point_channels=point_channels, point_method=point_method,
-                     scenarios=scenarios, spectra=spectra, objects=objects, extremes=extremes, breeding=breeding, stochastic=stochastic, aggregates=aggregates,
-                     derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
+                     scenarios=scenarios, spectra=spectra, objects=objects, extremes=extremes, archive=archive, save=save, breeding=breeding, stochastic=stochastic,
+                     aggregates=aggregates, derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
                      length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels, perturb_scale=perturb_scale)
     todo, families = stages(gm, p, start_time, truth, climatology, scores, tracks, track_config)
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()
@@ -723,14 +733,25 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     std = channel_std(model)
     if std.numel() != x0.shape[2]:
         raise ValueError(f"channel_std holds {std.numel()} values for {x0.shape[2]} input channels")
-    cfg = save_config_with_id(save_config)
-    fid, paths, source = cfg["forecast_id"], [], gm.source_label
-    sink = (cfg, paths) if save else None                  # where the stages write
     seeds, growth = seed_members(model, p, x0, std, float(perturb_scale), start_time)
     # per-step perturbations (skyrim_amd/stochastic.py): the members are held as states, each lead the model's own lead 1 from the perturbed one before
     stepper = Stepper(p.stochastic, x0.device, x0.shape[2:], std, p.M, int(seed), float(perturb_scale)) if p.stochastic is not None else None
     members = Members(model, start_time, seeds, stepper)
     del x0, seeds                                          # (only the members' current states stay alive on the GPU)
+    return drive(gm, p, todo, families, members, n_steps, save, save_config, float(perturb_scale), growth)
+
+
+def drive(gm, p: Plan, todo, families, members, n_steps, save, save_config, perturb_scale, growth=None) -> EnsembleForecast:
+    """The leads of a forecast from a member source: ``members.advance(k) -> (valid time, M states)`` in order from 0 and
+    ``members.close()`` -- the stepping ``Members`` of ``run``, or the files of a forecast that was written down
+    (``archive.ArchiveMembers``).  Lead by lead every stage of ``todo`` that is due, the files of ``save``, then what the stages hang on
+    the ``EnsembleForecast``."""
+    from .common import save_config_with_id
+    from .leads import forget_resident
+    model, seed = gm.model, p.asked.seed
+    cfg = save_config_with_id(save_config)
+    fid, paths, source = cfg["forecast_id"], [], gm.source_label
+    sink = (cfg, paths) if save else None                  # where the stages write
     for family in families:
         family.products = family.make()
     stored = [f for f in families if f.starts is None]     # raw, derived, regridded: their entries are the saved leads
@@ -751,10 +772,15 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         try:
             members.close()
         finally:
-            forget_resident(model)
+            try:
+                for stage in todo:
+                    if stage.close is not None:
+                        stage.close()
+            finally:
+                forget_resident(model)
 
     ens = EnsembleForecast(gm.model_name, p.M, int(seed), float(perturb_scale), paths=paths, forecast_id=fid, perturbation=p.noise.kind,
-                           length_scale_km=float(length_scale_km), alpha=float(alpha), lmax=p.noise.lmax if p.noise.kind == "spherical" else None,
+                           length_scale_km=float(p.asked.length_scale_km), alpha=float(p.asked.alpha), lmax=p.noise.lmax if p.noise.kind == "spherical" else None,
                            breeding=None if p.breeding is None else p.breeding.as_dict(), breeding_growth=growth,
                            stochastic=None if p.stochastic is None else p.stochastic.as_dict())
     for stage in todo:

@@ -45,16 +45,19 @@ class Coordinate:
 
 
 class DataArray:
-    def __init__(self, data, dims: Iterable[str], coords: dict[str, Any] | None = None, name: str | None = None, ready=None, image=None):
+    def __init__(self, data, dims: Iterable[str], coords: dict[str, Any] | None = None, name: str | None = None, ready=None, image=None, packed=None):
         """``ready``: a callable that returns once ``data`` holds its final contents (run_basic_inference hands over a pinned host
         buffer whose device-to-host copy may still be in flight, with the copy's event wait as ``ready``).  It is called the first
         time ``values`` is read -- shape, dims and coordinates never wait -- so a prediction fed straight back into the next step
         (``rollout``) lets its copy overlap that step; whoever reads the numbers (the save thread, the caller) waits first.
         ``image``: the same numbers as a big-endian host image (deliver.BigEndianImage) for the netCDF writer, which then never reads
-        ``values``; it belongs to this object and this array only -- assigning ``values`` drops it, derived arrays do not inherit it."""
+        ``values``; it belongs to this object and this array only -- assigning ``values`` drops it, derived arrays do not inherit it.
+        ``packed``: ``data`` are 16-bit codes, the ``>i2`` view of a packed image (ncio.PackedImage) that carries their table; the netCDF
+        writer then writes a packed file.  The same ownership rule holds."""
         self._values = np.asarray(data)
         self._ready = ready
         self._image = image
+        self._packed = packed
         self.dims = tuple(dims)
         if len(self.dims) != self._values.ndim:
             raise ValueError(f"{len(self.dims)} dims for a {self._values.ndim}-d array")
@@ -76,7 +79,12 @@ class DataArray:
 
     @values.setter
     def values(self, v):
-        self._values, self._ready, self._image = np.asarray(v), None, None
+        self._values, self._ready, self._image, self._packed = np.asarray(v), None, None, None
+
+    @property
+    def packed(self):
+        """The packed image of an array of 16-bit codes (ncio.PackedImage) or None."""
+        return self.__dict__.get("_packed")
 
     # -- basic accessors --------------------------------------------------- #
     @property
@@ -243,13 +251,16 @@ def concat(arrays: list[DataArray], dim: str) -> DataArray:
     return DataArray(np.stack([a.values for a in arrays], axis=0), (dim,) + first.dims, coords, first.name)
 
 
-def open_dataarray(path) -> DataArray:
+def open_dataarray(path, raw: bool = False) -> DataArray:
+    """``raw``: the codes and the table of a packed netCDF file (ncio.read_dataarray_netcdf3) instead of the decoded float32."""
     p = Path(path)
     if p.is_dir():
+        if raw:
+            raise ValueError(f"{p} is a zarr store: only netCDF files are packed")
         from .zarrio import read_dataarray_zarr
         return read_dataarray_zarr(p)
     from .ncio import read_dataarray_netcdf3
-    return read_dataarray_netcdf3(p)
+    return read_dataarray_netcdf3(p, raw=raw)
 
 
 def as_xarray(da: DataArray):

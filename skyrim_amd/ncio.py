@@ -13,6 +13,52 @@ from __future__ import annotations
 import numpy as np
 
 UNNAMED = "__xarray_dataarray_variable__"
+PACKING_ATTR, PACKING, PACK_FILL = "skyrim_packing", "linear16", -32768      # the global attribute that marks a packed file; its _FillValue
+PACK_TABLES = ("scale_factor", "add_offset")                                  # double (time, channel): the table of a packed file
+
+
+class PackedImage:
+    """The payload of a packed DataArray as the file wants it (include/skyrim_pack.h): ``image``, the big-endian int16 codes
+    of an array of ``shape`` as bytes (a uint8 array, e.g. over pinned host memory whose copy may still be in flight: ``wait`` returns once
+    it has landed), and the table ``scale`` / ``offset``, one entry per plane of the two leading dims.  ``values`` is the ``>i2`` view of the
+    image a DataArray carries; the writer uses the image only while the DataArray still carries that very view."""
+
+    def __init__(self, image, shape, scale, offset, wait=None):
+        self.image = (image if isinstance(image, np.ndarray) else np.frombuffer(image, np.uint8)).reshape(-1).view(np.uint8)
+        self.shape = tuple(int(n) for n in shape)
+        if len(self.shape) < 2 or self.image.size != 2 * int(np.prod(self.shape)):
+            raise ValueError(f"packed image of {self.image.size} bytes for int16 codes of shape {self.shape}")
+        self.scale = np.ascontiguousarray(scale, np.float64).reshape(self.shape[:2])
+        self.offset = np.ascontiguousarray(offset, np.float64).reshape(self.shape[:2])
+        self.values = self.image.view(">i2").reshape(self.shape)
+        self._wait = wait
+
+    def wait(self) -> None:
+        if self._wait is not None:
+            self._wait()
+            self._wait = None
+
+    def segments(self) -> list:
+        """The bytes of the payload in file order (after ``wait``)."""
+        self.wait()
+        return [memoryview(self.image)]
+
+    def mirrors(self, values: np.ndarray) -> bool:
+        return values is self.values
+
+    def decode(self) -> np.ndarray:
+        """float32 of ``shape``: x' = fl32(fl(fl(double(code) scale) + offset)), the quiet NaN 0x7FC00000 for the code -32768."""
+        self.wait()
+        return decode_packed(self.values, self.scale, self.offset)
+
+
+def decode_packed(codes: np.ndarray, scale: np.ndarray, offset: np.ndarray) -> np.ndarray:
+    """The formula of include/skyrim_pack.h on the host: ``scale`` and ``offset`` hold one double per plane of the two leading dims."""
+    codes = np.asarray(codes)
+    bc = scale.shape + (1,) * (codes.ndim - scale.ndim)
+    out = (codes.astype(np.float64) * scale.reshape(bc) + offset.reshape(bc)).astype(np.float32)
+    out.view(np.uint32)[codes == PACK_FILL] = 0x7FC00000
+    return out
 
 
 def _encode_time(vals: np.ndarray):
@@ -112,6 +158,9 @@ def write_dataarray_netcdf3(da, path, fast_threshold: int | None = None):
     The fast path leans on scipy internals (``_write_var_data``, ``_begin``, ``_pack_begin``, ``_vsize``): it writes to ``<path>.part`` and
     renames on success; if those internals are gone (AttributeError / a size that does not add up) the partial file is removed and scipy's
     plain writer takes over; an I/O error (ENOSPC ...) removes the partial file and is raised -- never a valid header over a garbage payload."""
+    packed = _packed_of(da)
+    if packed is not None:
+        return _write_packed(da, path, packed)
     image = _image_of(da)
     payload0 = da.__dict__["_values"] if image is not None else da.values      # (with an image nobody waits for, or fills, the native array)
     thr = FAST_PAYLOAD_BYTES if fast_threshold is None else fast_threshold
@@ -153,6 +202,36 @@ def _image_of(da):
     return image
 
 
+def _packed_of(da):
+    """The packed image a DataArray carries (``PackedImage``), if it still mirrors the codes ``da`` holds."""
+    packed, raw = da.__dict__.get("_packed"), da.__dict__.get("_values")
+    if packed is None or raw is None or not packed.mirrors(raw):
+        return None
+    return packed
+
+
+def _write_packed(da, path, packed):
+    """A packed array: header, coordinates and the two table variables are scipy's own, the payload is the image, handed to
+    ``pwrite`` untouched, into the hole scipy's writer leaves for it -- byte-identical to scipy writing the same int16 codes itself, the
+    padding of an odd count included (tests/test_pack_cpu.py).  ``<path>.part`` and a rename, as for float32; if scipy's internals are
+    gone its plain writer takes over."""
+    import os
+    part = f"{os.fspath(path)}.part"
+    try:
+        _write_netcdf3(da, part, True, packed, packed)
+    except (AttributeError, _FastPathMismatch):
+        _unlink(part)
+        try:
+            _write_netcdf3(da, part, False, None, packed)
+        except BaseException:
+            _unlink(part)
+            raise
+    except BaseException:
+        _unlink(part)
+        raise
+    os.replace(part, os.fspath(path))
+
+
 def _image_payload_write(path, offset: int, image):
     """The payload is already in the file's byte order in (pinned) host memory: one pwrite loop.  Writes to one file serialise on its
     inode whatever the thread count, so there is nothing to split; the throughput of a rollout comes from its files being written side
@@ -169,9 +248,11 @@ def _image_payload_write(path, offset: int, image):
         os.close(fd)
 
 
-def _write_netcdf3(da, path, fast: bool, image=None):
+def _write_netcdf3(da, path, fast: bool, image=None, packed=None):
     from scipy.io import netcdf_file
-    payload0 = da.__dict__["_values"] if image is not None else da.values
+    if packed is not None:
+        packed.wait()
+    payload0 = da.__dict__["_values"] if (image is not None or packed is not None) else da.values
     pname = da.name or UNNAMED
     hole = {}
 
@@ -185,6 +266,10 @@ def _write_netcdf3(da, path, fast: bool, image=None):
             self._pack_begin(begin)
             self.fp.seek(begin + var._vsize)             # leave a hole of the variable's size; whatever scipy writes next starts behind it
             hole["begin"], hole["vsize"] = begin, var._vsize
+            count = var.data.size * var.data.itemsize
+            if count != var._vsize:                      # an odd number of 16-bit codes: scipy's own padding behind the hole's payload
+                self.fp.seek(begin + count)
+                self._write_var_padding(var, var._vsize - count)
 
     with (_File if fast else netcdf_file)(str(path), "w", version=2) as f:
         for d, n in zip(da.dims, da.shape):
@@ -218,8 +303,14 @@ def _write_netcdf3(da, path, fast: bool, image=None):
         coord_names = " ".join(k for k in da._coords if k not in da.dims)
         if coord_names:
             v.coordinates = coord_names
+        if packed is not None:
+            v._FillValue = np.array(PACK_FILL, np.int16)
+            for tname, tab in zip(PACK_TABLES, (packed.scale, packed.offset)):
+                tv = f.createVariable(tname, "d", da.dims[:2])
+                tv[...] = tab
+            setattr(f, PACKING_ATTR, PACKING)
     if fast:
-        if hole.get("vsize") != payload0.nbytes:
+        if hole.get("vsize") != (payload0.nbytes + 3) // 4 * 4:
             raise _FastPathMismatch(f"payload hole {hole} does not match {payload0.nbytes} bytes")
         if image is not None:
             _image_payload_write(path, hole["begin"], image)
@@ -227,11 +318,34 @@ def _write_netcdf3(da, path, fast: bool, image=None):
             _parallel_payload_write(path, hole["begin"], payload0)
 
 
-def read_dataarray_netcdf3(path):
+def read_payload_netcdf3(path) -> np.ndarray:
+    """The one data variable of ``path`` in the byte order of the file (``>f4`` for a float32 file, ``>i2`` codes for a packed one): what
+    goes to the device as it is and is swapped or unpacked there (skyrim_amd/archive.py)."""
+    from scipy.io import netcdf_file
+    with netcdf_file(str(path), "r", mmap=False) as f:
+        tables = PACK_TABLES if getattr(f, PACKING_ATTR, None) is not None else ()
+        dimnames = set(f.dimensions)
+        data_vars = [n for n in f.variables if n not in tables and n not in dimnames and len(f.variables[n].dimensions) > 1
+                     and not (f.variables[n].typecode() == "c" and len(f.variables[n].dimensions) == 2)]
+        if len(data_vars) != 1:
+            raise ValueError(f"expected exactly one data variable in {path}, found {data_vars}")
+        return np.array(f.variables[data_vars[0]][...])
+
+
+def read_dataarray_netcdf3(path, raw: bool = False):
+    """``raw``: a packed file (global attribute ``skyrim_packing = "linear16"``) gives its int16 codes as they are, with the
+    image and the table in ``.packed`` (a ``PackedImage``), instead of the decoded float32; a file without the marker is refused."""
     from scipy.io import netcdf_file
     from .labeled import DataArray
     with netcdf_file(str(path), "r", mmap=False) as f:
-        names = list(f.variables)
+        marker = getattr(f, PACKING_ATTR, None)
+        marker = marker.decode() if isinstance(marker, bytes) else marker
+        if marker is not None and marker != PACKING:
+            raise ValueError(f"{path}: unknown packing {marker!r} (this package reads {PACKING!r})")
+        if raw and marker is None:
+            raise ValueError(f"{path} is not a packed file (no global attribute {PACKING_ATTR})")
+        tables = PACK_TABLES if marker is not None else ()
+        names = [n for n in f.variables if n not in tables]
         dimnames = set(f.dimensions)
         data_vars = [n for n in names if n not in dimnames and len(f.variables[n].dimensions) > 1
                      and not (f.variables[n].typecode() == "c" and len(f.variables[n].dimensions) == 2)]
@@ -250,4 +364,13 @@ def read_dataarray_netcdf3(path):
                 vals = _decode_time(vals, v.units.decode() if isinstance(v.units, bytes) else v.units)
             coords[n] = vals
         name = None if data_vars[0] == UNNAMED else data_vars[0]
+        if marker is not None:
+            if var.typecode() != "h" or any(t not in f.variables or f.variables[t].dimensions != var.dimensions[:2] for t in tables):
+                raise ValueError(f"{path}: a packed file holds a short variable and double {tables} over its two leading dims")
+            scale, offset = (_native(np.array(f.variables[t][...])).astype(np.float64) for t in tables)
+            codes = np.ascontiguousarray(np.array(var[...]), ">i2")
+            if not raw:
+                return DataArray(decode_packed(codes, scale, offset), var.dimensions, coords, name)
+            img = PackedImage(codes.reshape(-1).view(np.uint8), codes.shape, scale, offset)
+            return DataArray(img.values, var.dimensions, coords, name, packed=img)
         return DataArray(_native(np.array(var[...])), var.dimensions, coords, name)

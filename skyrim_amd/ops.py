@@ -30,6 +30,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     stoch_coeffs / stoch_evolve / stoch_apply            (per-step stochastic perturbations: SPPT and additive, include/skyrim_stoch.h)
     object_label / object_attributes / object_probability    (labelled threshold regions of M states, include/skyrim_object.h)
     clim_extremes / clim_quantiles                       (EFI, SOT and tail odds of M states against a quantile climate; the climate from N samples, include/skyrim_clim.h)
+    pack_range / pack_quantize / pack_unpack             (M states as 16-bit big-endian codes with a per-plane table, and the way back, include/skyrim_pack.h)
 """
 from __future__ import annotations
 
@@ -600,6 +601,25 @@ def _clim_quantiles(samples, table, channels, levels, clim) -> None:
     climate.run_quantiles(list(samples), table, list(channels), list(levels), clim)
 
 
+# ---- packed member archives -------------------------------------------------------------------------------------------------------------- #
+def _pack_range(members, table, channels, tab, workspace) -> None:
+    """``tab``: archive.new_table(M, nc, device), the records of the listed channels; ``workspace``: uint8, archive.workspace_bytes."""
+    from . import archive
+    archive.run_range(list(members), table, list(channels), tab, workspace)
+
+
+def _pack_quantize(members, table, channels, tab, out, member_stride_bytes) -> None:
+    """``out``: uint8, the big-endian codes of member m from byte m * member_stride_bytes (even, >= 2 nc H W)."""
+    from . import archive
+    archive.run_quantize(list(members), table, list(channels), tab, out, member_stride_bytes)
+
+
+def _pack_unpack(codes, tab, out) -> None:
+    """``codes``: uint8, the big-endian image of (nc, H, W) codes; ``tab``: its nc records; ``out``: float32 (nc, H, W)."""
+    from . import archive
+    archive.run_unpack(codes, tab, out)
+
+
 # ---- point extraction ------------------------------------------------------------------------------------------------------------------- #
 def _point_gather(members, table, channels, records, out) -> None:
     """``records``: points.device_records(...), int32 (P, 8); ``out``: (M, len(channels), P) or (M, stride >= len(channels) P)."""
@@ -786,6 +806,9 @@ _SCHEMAS = [
      "float[] sot_frac, int[] sot_ref, int[] sot_base, int[] prob_level, bool[] prob_below, Tensor(a!)? efi, Tensor(b!)? sot, "
      "Tensor(c!)? prob) -> ()", _clim_extremes),
     ("clim_quantiles(Tensor[] samples, Tensor table, int[] channels, float[] levels, Tensor(a!) clim) -> ()", _clim_quantiles),
+    ("pack_range(Tensor[] members, Tensor table, int[] channels, Tensor(a!) tab, Tensor(b!) workspace) -> ()", _pack_range),
+    ("pack_quantize(Tensor[] members, Tensor table, int[] channels, Tensor tab, Tensor(a!) out, int member_stride_bytes) -> ()", _pack_quantize),
+    ("pack_unpack(Tensor codes, Tensor tab, Tensor(a!) out) -> ()", _pack_unpack),
 ]
 OP_NAMES = [s.split("(", 1)[0] for s, _ in _SCHEMAS]
 
