@@ -121,7 +121,7 @@ class GlobalModel:
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
                           scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None, extremes: dict | None = None,
                           archive: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
-                          aggregates: List[str] | None = None, derived_surface=None,
+                          aggregates: List[str] | None = None, vertical: dict | None = None, derived_surface=None,
                           derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
@@ -143,7 +143,9 @@ class GlobalModel:
         ``EnsembleForecast.tracks``.  ``derived=[...]`` names derived fields (``ws10m``, ``ws100m``, ``ws<level>``, ``thk<a>_<b>``, ``vo<X>``,
         ``div<X>``, ``ivt``, ``ivtu``, ``ivtv``, ``iwv``: skyrim_amd/derived.py; and the column thermodynamics ``td<level>``,
         ``thetae<level>``, ``kx``, ``tt``, ``zdeg0``, ``sbcape``, ``mucape``, ``muli`` ... of DESIGN.md 30, with ``derived_surface=`` the (lat, lon) surface
-        geopotential that masks the levels below the ground -- without it they are treated as air) that are formed from every member on the device at
+        geopotential that masks the levels below the ground -- without it they are treated as air; and the fields on chosen surfaces
+        ``<field>@<surface>`` of DESIGN.md 34 -- ``ws@100magl``, ``t@1500m``, ``z@-10C``, ``u@320K``, ``ws@875hPa`` -- with ``derived_surface=`` also the
+        ground of ``@<Z>magl`` and ``vertical={"outside": "nan" | "nearest"}`` what they are where the surface does not cross the column) that are formed from every member on the device at
         each lead time; the same ``products`` of them, ``exceed`` / ``quantiles`` under their names and, with ``scores=True``, their scores land
         in ``EnsembleForecast.derived``.  ``grid=`` names a target grid (``"1.5deg"`` or a float, ``(lat, lon)`` arrays, or
         ``dict(region=(lat_s, lat_n, lon_w, lon_e), res=...)``: skyrim_amd/regrid.py) every member is also put on at each lead
@@ -221,6 +223,8 @@ class GlobalModel:
             extra["derived"] = derived
         if derived_surface is not None:
             extra["derived_surface"] = derived_surface
+        if vertical is not None:
+            extra["vertical"] = vertical
         if grid is not None:
             extra.update(grid=grid, regrid_method=regrid_method)
         if aggregates is not None:
@@ -285,16 +289,17 @@ class GlobalModel:
         return extreming.extremes_model(self, start_time, n_steps, extremes, derived=derived, save=save, save_config=save_config)
 
     def derive_fields(self, start_time: datetime.datetime, n_steps: int = 4, fields: List[str] = (), save: bool = False,
-                      save_config: dict | None = None, derived_surface=None):
+                      save_config: dict | None = None, derived_surface=None, vertical: dict | None = None):
         """Derived fields of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/derived.py): wind speed
         (``ws10m``, ``ws100m``, ``ws<level>``), thickness (``thk<a>_<b>``), vorticity and divergence (``vo<X>``, ``div<X>``) and the column
         integrals ``ivt``, ``ivtu``, ``ivtv``, ``iwv``, and the column thermodynamics of DESIGN.md 30 (``td<level>``, ``thetae<level>``, ``kx``,
         ``tt``, ``zdeg0``, ``sbcape``, ``mucape``, ``muli`` ...; ``derived_surface``: the (lat, lon) surface geopotential that masks the levels
-        below the ground -- without it they are treated as air).  The model's TimeLoop is advanced and every state is derived where it lies in HBM; only
+        below the ground -- without it they are treated as air), and the fields on chosen surfaces of DESIGN.md 34 (``ws@100magl``, ``t@1500m``,
+        ``z@-10C``, ``u@320K``, ``ws@875hPa``; ``vertical={"outside": "nan" | "nearest"}``).  The model's TimeLoop is advanced and every state is derived where it lies in HBM; only
         the derived planes cross to the host.  Returns DataArray(time, channel=fields, lat, lon); ``save=True`` writes it as the forecast of
         ``{model}-derived``.  A field whose input channels the model lacks is refused with ValueError before the device is touched."""
         from ... import derived
-        return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config, surface=derived_surface)
+        return derived.derive_model(self, start_time, n_steps, list(fields), save=save, save_config=save_config, surface=derived_surface, vertical=vertical)
 
     def aggregate_forecast(self, start_time: datetime.datetime, n_steps: int = 4, aggregates: List[str] = (), derived: List[str] | None = None,
                            save: bool = False, save_config: dict | None = None):

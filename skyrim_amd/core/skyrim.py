@@ -147,10 +147,10 @@ class Skyrim:
         return regrid.regrid_prediction(pred, grid, method, device=device, **kwargs)
 
     @staticmethod
-    def derive_prediction(pred, fields, device="cuda:0", derived_surface=None):
+    def derive_prediction(pred, fields, device="cuda:0", derived_surface=None, vertical=None):
         """Derived fields of a forecast that is already in memory or on disk (``derived.derive_prediction``)."""
         from .. import derived
-        return derived.derive_prediction(pred, fields, device=device, surface=derived_surface)
+        return derived.derive_prediction(pred, fields, device=device, surface=derived_surface, vertical=vertical)
 
     @staticmethod
     def track_prediction(pred, config=None, device="cuda:0", **kwargs):

@@ -9,7 +9,9 @@ Layers:
 * the catalogue: ``plan`` resolves user-facing names (``ws10m``, ``thk500_1000``, ``vo850``, ``div850``, ``ivt`` ...) against a model's
   channels into a program of ops, ``row_table`` makes the row coefficients of vorticity and divergence in float64.  The names of column
   thermodynamics (``td850``, ``thetae850``, ``kx``, ``zdeg0``, ``mucape`` ...: DESIGN.md 30) resolve into ops of libskyrim_thermo.so
-  (skyrim_amd/thermo.py), which write into the same buffer; a request that names none of them never loads that library;
+  (skyrim_amd/thermo.py), which write into the same buffer; a request that names none of them never loads that library.  The names
+  ``<field>@<surface>`` (``ws@100magl``, ``t@1500m``, ``z@-10C``, ``u@320K``, ``ws@875hPa``: DESIGN.md 34) resolve into ops of
+  libskyrim_vert.so (skyrim_amd/vertical.py) in the same way;
 * the drivers: ``LeadDeriver`` (what ``ensemble.run`` calls at every lead time with ``derived=[...]``), ``TruthDeriver`` (the hook that
   lets ``verify.LeadScorer`` score derived fields against a truth of raw channels), ``derive_model`` (``GlobalModel.derive_fields``)
   and ``derive_prediction`` for forecasts that are already on disk.
@@ -226,7 +228,8 @@ class Plan:
     derived field reads; ``rowc / edges``: the row table when vorticity or divergence is asked for; ``levels / weights``: the pressure
     levels (hPa) and float64 trapezoid weights of the column integrals, when asked for.  ``thermo_ops``: the program of
     libskyrim_thermo.so (``thermo.Op``), whose slots are numbered with those of ``ops``; ``moisture``: "q" or "r", what they read;
-    ``column``: {"parcel" / "freeze": the pressure levels (hPa, bottom-up) of their columns}."""
+    ``column``: {"parcel" / "freeze" / "vert": the pressure levels (hPa, bottom-up) of their columns}.  ``vert_ops``: the program of
+    libskyrim_vert.so (``vertical.Op``) for the names ``<field>@<surface>``, its slots numbered with the others."""
     fields: list
     ops: list
     inputs: dict
@@ -237,6 +240,7 @@ class Plan:
     thermo_ops: list = field(default_factory=list)
     moisture: str | None = None
     column: dict = field(default_factory=dict)
+    vert_ops: list = field(default_factory=list)
 
 
 def column_weights(levels) -> np.ndarray:
@@ -388,6 +392,122 @@ def _thermo_plan(out: Plan, names, requests, surface: bool, column) -> None:
         raise ValueError(f"derived: {len(out.thermo_ops)} thermodynamic ops for {[n for _, n in requests]}; one call holds {thermo.MAX_OPS}")
 
 
+# ---- fields on chosen surfaces --------------------------------------------------------------------------------------------- #
+VERT_LEVEL_FIELDS = ("z", "q", "r", "t", "u", "v")             # a level variable the model carries
+VERT_KNOWN = ("<field>@<surface> (field: z, q, r, t, u, v, ws, theta or p; surface: <P>hPa, <Z>m above sea level, <Z>magl above the ground, "
+              "<theta>K or <T>C)")
+_VERT_NAME = re.compile(r"(z|q|r|t|u|v|ws|theta|p)@(-?\d+(?:\.\d+)?)(hPa|magl|m|K|C)")
+_VERT_UNITS = {"hPa": "P", "m": "Z", "magl": "Z_AGL", "K": "THETA", "C": "T"}
+NODE_HEIGHT_M = {"u10m": 10.0, "v10m": 10.0, "t2m": 2.0}       # the surface channels that serve as the node of a column above the ground
+
+
+def _parse_vert(name: str):
+    """(field, coordinate kind as the name of ``vertical``'s constant, value in the surface's own unit) of ``<field>@<surface>``, or None"""
+    m = _VERT_NAME.fullmatch(name)
+    if not m:
+        return None
+    return m.group(1), _VERT_UNITS[m.group(3)], float(m.group(2))
+
+
+def vertical_options(vertical) -> int:
+    """``vertical={"outside": "nan" | "nearest"}`` -> ``vertical.NAN`` / ``vertical.NEAREST``"""
+    from . import vertical as V
+    opts = dict(vertical or {})
+    unknown = [k for k in opts if k != "outside"]
+    if unknown:
+        raise ValueError(f"vertical: unknown keys {unknown}; it takes \"outside\"")
+    outside = opts.get("outside", "nan")
+    if outside not in ("nan", "nearest"):
+        raise ValueError(f"vertical: outside is \"nan\" or \"nearest\", not {outside!r}")
+    return V.NEAREST if outside == "nearest" else V.NAN
+
+
+def vert_inputs(name: str, names, surface: bool, column=None) -> dict:
+    """What ``<field>@<surface>`` reads, every refusal of such a name a ValueError: dict(field, coord, value, levels, c, z, a, b, node,
+    raw) -- the channel NAMES of the coordinate, the mask, the field's components and its surface node, and all of them in ``raw``."""
+    fld, coord, value = _parse_vert(name)
+    names = list(names)
+    if fld == "p" and coord == "P":
+        raise ValueError(f"derived: {name!r} is the pressure on a pressure surface: the constant {value:g} hPa")
+    if (fld, coord) in (("theta", "THETA"), ("t", "T")):
+        raise ValueError(f"derived: {name!r} is {'theta on an isentrope' if fld == 'theta' else 't on an isotherm'}: a constant")
+    if coord in ("Z", "Z_AGL", "THETA") and not value > 0:
+        raise ValueError(f"derived: {name!r}: a {'potential temperature' if coord == 'THETA' else 'height'} must be positive")
+    if coord == "Z_AGL" and not surface:
+        raise ValueError(f"derived: {name!r} is a height above the ground: it needs the surface geopotential, derived_surface=")
+    letters = {"ws": "uv", "theta": "t", "p": ""}.get(fld, fld)
+    coord_letters = {"P": "", "Z": "z", "Z_AGL": "z", "THETA": "t", "T": "t"}[coord]
+    mask_letters = "z" if surface and coord in ("THETA", "T") else ""
+    for x in letters:
+        if not any(re.fullmatch(x + r"\d+", n) for n in names):
+            raise ValueError(f"derived: {name!r} needs the level variable {x!r} ({x}<level>), which this model lacks")
+    need = "".join(dict.fromkeys(coord_letters + mask_letters + letters))
+    levels = thermo_levels(names, need, repr(name), (column or {}).get("vert"))
+    if coord == "P" and not levels[-1] <= value <= levels[0]:
+        raise ValueError(f"derived: {name!r}: {value:g} hPa lies outside the column {levels[0]} .. {levels[-1]} hPa of this model")
+    on = lambda x: [f"{x}{l}" for l in levels]                  # noqa: E731
+    node = []
+    if coord == "Z_AGL":
+        if fld in ("u", "v") and f"{fld}10m" in names:
+            node = [f"{fld}10m"]
+        elif fld == "ws" and "u10m" in names and "v10m" in names:
+            node = ["u10m", "v10m"]
+        elif fld == "t" and "t2m" in names:
+            node = ["t2m"]
+        elif fld == "z":
+            node = ["zs"]
+    out = dict(field=fld, coord=coord, value=value, levels=levels, c=on(coord_letters) if coord_letters else [],
+               z=on("z") if mask_letters else [], a=on(letters[0]) if letters else [], b=on("v") if fld == "ws" else [], node=node)
+    out["raw"] = list(dict.fromkeys(out["c"] + out["z"] + out["a"] + out["b"] + [c for c in node if c != "zs"]))
+    return out
+
+
+def _vert_plan(out: Plan, names, requests, surface: bool, column, outside: int) -> None:
+    """The vert ops of ``requests`` = [(slot, name)]: fields on the same coordinate kind and column share an op, up to the targets and
+    fields one op holds; beyond them they go to further ops."""
+    from . import vertical as V
+    names = list(names)
+    ch = names.index
+    groups = []                                                 # dict(key, coord, levels, c, z, targets: [fp32], fields: {field key: [Field parts, {target: slot}]})
+    for slot, name in requests:
+        r = vert_inputs(name, names, surface, column)
+        out.inputs[name] = r["raw"]
+        out.column.setdefault("vert", r["levels"])
+        coord = getattr(V, r["coord"])
+        target = V.target_value(coord, r["value"])
+        key = (coord, tuple(r["levels"]))
+        kind = {"ws": V.SPEED, "theta": V.THETA_F, "p": V.PRESSURE}.get(r["field"], V.PLAIN)
+        g = None
+        for cand in groups:
+            if cand["key"] != key:
+                continue
+            if (target in cand["targets"] or len(cand["targets"]) < V.MAX_TARGETS) and (r["field"] in cand["fields"] or len(cand["fields"]) < V.MAX_FIELDS):
+                g = cand
+                break
+        if g is None:
+            g = dict(key=key, coord=coord, levels=r["levels"], c=tuple(ch(c) for c in r["c"]), z=(), targets=[], fields={})
+            groups.append(g)
+        if r["z"]:
+            g["z"] = tuple(ch(c) for c in r["z"])
+        if target not in g["targets"]:
+            g["targets"].append(target)
+        if r["field"] not in g["fields"]:
+            node, gh = (V.NODE_NONE, V.NODE_NONE), 0.0
+            if r["node"] == ["zs"]:
+                node = (V.NODE_ZS, V.NODE_NONE)
+            elif r["node"]:
+                node = (ch(r["node"][0]), ch(r["node"][1]) if len(r["node"]) > 1 else V.NODE_NONE)
+                gh = float(np.float32(V.GRAVITY * NODE_HEIGHT_M[r["node"][0]]))
+            g["fields"][r["field"]] = (kind, tuple(ch(c) for c in r["a"]), tuple(ch(c) for c in r["b"]), node, gh, {})
+        g["fields"][r["field"]][5][target] = slot
+    for g in groups:
+        fields = tuple(V.Field(kind, a, b, tuple(slots.get(t, -1) for t in g["targets"]), node, gh)
+                       for kind, a, b, node, gh, slots in g["fields"].values())
+        out.vert_ops.append(V.Op(g["coord"], tuple(float(l) for l in g["levels"]), g["c"], g["z"], tuple(g["targets"]), fields, outside))
+    if len(out.vert_ops) > V.MAX_OPS:
+        raise ValueError(f"derived: {len(out.vert_ops)} vertical-interpolation ops for {[n for _, n in requests]}; one call holds {V.MAX_OPS}")
+
+
 def column_levels(names, levels=None) -> list:
     """The pressure levels (hPa, ascending) with q, u and v among ``names`` and 300 <= level <= 1000 (or those of ``levels``)."""
     names = set(names)
@@ -407,18 +527,20 @@ def column_levels(names, levels=None) -> list:
     return use
 
 
-def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=None) -> Plan:
+def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=None, vertical=None) -> Plan:
     """Resolve the derived ``fields`` against the channels ``names`` of a (C, H, W) state on the grid (lat, lon).  Every refusal is a
     ValueError before the device is touched: an unknown name, a name that is one of the model's channels, missing input channels (named),
     more than ``MAX_OPS`` ops, a grid vorticity cannot be formed on.  ``vo<X>`` and ``div<X>`` of one level share an op, and so do the
     four column integrals.  ``surface``: a surface geopotential will be given, so the parcel columns need z; ``column``: the levels of the
-    thermodynamic columns when they are not to be taken from the channels (``Plan.column`` of the forecast, for its truth)."""
+    thermodynamic columns when they are not to be taken from the channels (``Plan.column`` of the forecast, for its truth);
+    ``vertical``: ``{"outside": "nan" | "nearest"}``, what a field on a surface is where the surface does not cross the column."""
     names, fields = list(names), list(fields)
+    outside = vertical_options(vertical)
     if not fields:
         raise ValueError("derived: at least one field")
     if len(set(fields)) != len(fields):
         raise ValueError(f"derived: a field is named twice in {fields}")
-    ops, inputs, merged, thermal = [], {}, {}, []
+    ops, inputs, merged, thermal, surfaces = [], {}, {}, [], []
     out = Plan(fields, ops, inputs)
     for slot, name in enumerate(fields):
         if name in names:
@@ -427,9 +549,12 @@ def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=Non
         if parsed is None and _parse_thermo(name) is not None:
             thermal.append((slot, name))
             continue
+        if parsed is None and _parse_vert(name) is not None:
+            surfaces.append((slot, name))
+            continue
         if parsed is None:
             raise ValueError(f"derived: unknown field {name!r}; known are ws10m, ws100m, ws<level>, thk<a>_<b>, vo<X>, div<X> "
-                             f"(X a level, 10m or 100m), {', '.join(COLUMN_FIELDS)}, {THERMO_KNOWN}")
+                             f"(X a level, 10m or 100m), {', '.join(COLUMN_FIELDS)}, {VERT_KNOWN}, {THERMO_KNOWN}")
         kind, raw, result = parsed
         if kind == COLUMN:
             if not out.levels:
@@ -459,6 +584,8 @@ def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=Non
         raise ValueError(f"derived: {len(ops)} ops for {fields}; one call holds {MAX_OPS}")
     if thermal:
         _thermo_plan(out, names, thermal, surface, column)
+    if surfaces:
+        _vert_plan(out, names, surfaces, surface, column, outside)
     if any(op.kind == VORTDIV for op in ops):
         out.rowc, e0, e1 = row_table(lat, lon)
         out.edges = (e0, e1)
@@ -467,14 +594,14 @@ def plan(names, fields, lat, lon, levels=None, surface: bool = False, column=Non
     return out
 
 
-def check_request(names, fields, lat, lon, n_members: int = 1, levels=None, surface: bool = False, column=None) -> Plan:
+def check_request(names, fields, lat, lon, n_members: int = 1, levels=None, surface: bool = False, column=None, vertical=None) -> Plan:
     """Every refusal that needs no device; returns the plan."""
     if _world_size() > 1:
         raise NotImplementedError("derived fields are made on one GPU from members that all lie there; members sharded over the ranks of "
                                   "a process group are out of scope (DESIGN.md 21)")
     if not 1 <= int(n_members) <= MAX_MEMBERS:
         raise ValueError(f"n_members = {n_members}: derived fields are made for 1 to {MAX_MEMBERS} members (SKDERIVE_MAX_MEMBERS)")
-    return plan(names, fields, lat, lon, levels, surface, column)
+    return plan(names, fields, lat, lon, levels, surface, column, vertical)
 
 
 # ---- the drivers ------------------------------------------------------------------------------------------------------------------------- #
@@ -482,10 +609,12 @@ class LeadDeriver:
     """Derives one lead time after the other into its own (M, D, H, W) buffer.  ``names``: the forecast's channels in the order of its
     (C, H, W) states; ``fields``: the derived names, channel d of the buffer is fields[d].  ``surface``: the (H, W) surface geopotential
     in the units of z, which masks the levels below the ground for zdeg0 and the parcel fields (None: they are treated as air);
-    ``column``: ``Plan.column`` of another plan, whose thermodynamic columns this one is to use."""
+    ``column``: ``Plan.column`` of another plan, whose thermodynamic columns this one is to use.  For the fields ``<field>@<surface>`` the
+    surface is also the ground of ``@<Z>magl``, and ``vertical`` (``{"outside": "nan" | "nearest"}``) says what they are where the surface does
+    not cross the column."""
 
-    def __init__(self, names, lat, lon, n_members, fields, device="cuda:0", levels=None, surface=None, column=None):
-        self.plan = check_request(names, fields, lat, lon, n_members, levels, surface is not None, column)
+    def __init__(self, names, lat, lon, n_members, fields, device="cuda:0", levels=None, surface=None, column=None, vertical=None):
+        self.plan = check_request(names, fields, lat, lon, n_members, levels, surface is not None, column, vertical)
         self.names, self.fields, self.M = list(names), list(fields), int(n_members)
         self.lat, self.lon, self.device = np.asarray(lat, np.float64), np.asarray(lon, np.float64), device
         self.surface = None
@@ -504,11 +633,12 @@ class LeadDeriver:
             states = [out[m] for m in range(self.M)]
             self._dev = dict(out=out, states=states, table=member_table(states),
                              rowc=None if self.plan.rowc is None else torch.from_numpy(self.plan.rowc).to(dev),
-                             surface=None if self.surface is None or not self.plan.thermo_ops else torch.from_numpy(self.surface).to(dev))
+                             surface=None if self.surface is None or not (self.plan.thermo_ops or self.plan.vert_ops) else torch.from_numpy(self.surface).to(dev))
         return self._dev
 
     def add(self, states, table=None) -> tuple:
-        """ONE derive launch over the M device states (C, H, W), then one of the thermodynamic ops when the request names any; returns
+        """ONE derive launch over the M device states (C, H, W), then one of the thermodynamic ops and one of the vertical interpolation
+        when the request names any; returns
         (derived_states, derived_table): M (D, H, W) views of the buffer and their ``ensemble.member_table``, ready for
         ``ensemble.stats`` and ``LeadScorer.add``.  The next ``add`` overwrites them."""
         from .ensemble import member_table
@@ -521,6 +651,9 @@ class LeadDeriver:
         if self.plan.thermo_ops:
             from . import thermo
             thermo.run(states, table, self.plan.thermo_ops, b["out"], b["surface"])
+        if self.plan.vert_ops:
+            from . import vertical
+            vertical.run(states, table, self.plan.vert_ops, b["out"], b["surface"])
         return b["states"], b["table"]
 
 
@@ -531,15 +664,18 @@ class TruthDeriver:
     truth holds no part of, the plan's own refusal).  ``levels``: the pressure levels of the forecast's column integrals, so that the
     truth's are the same integral (None: those the truth holds between 300 and 1000 hPa).
     ``surface``, ``column``, ``moisture``: the surface geopotential, ``Plan.column`` and ``Plan.moisture`` of the forecast's deriver, so
-    that the truth's thermodynamic fields are made from the same levels and the same kind of humidity."""
+    that the truth's thermodynamic fields are made from the same levels and the same kind of humidity; ``vertical``: the forecast's, so
+    that the truth's fields on surfaces go through the same ops."""
 
-    def __init__(self, fields, lat, lon, device="cuda:0", levels=None, surface=None, column=None, moisture=None):
+    def __init__(self, fields, lat, lon, device="cuda:0", levels=None, surface=None, column=None, moisture=None, vertical=None):
         self.fields, self.lat, self.lon, self.device, self.levels = list(fields), lat, lon, device, levels
-        self.surface, self.column, self.moisture = surface, column, moisture
+        self.surface, self.column, self.moisture, self.vertical = surface, column, moisture, vertical
         self.dropped: dict = {}
         self._derivers: dict = {}
 
     def _needs(self, name, have) -> list:
+        if _parse(name) is None and _parse_vert(name) is not None:      # a field on a surface, over the forecast's levels when they are given
+            return vert_inputs(name, have, self.surface is not None, self.column)["raw"]
         if _parse(name) is None:                               # column thermodynamics, over the forecast's levels when they are given
             op, key, slot = _parse_thermo(name)
             moisture = self.moisture or moisture_of(have) or "q"
@@ -557,6 +693,11 @@ class TruthDeriver:
 
     def _partners(self, name, have) -> list:
         """The channels that would complete the levels ``have`` holds in part for the column of ``name``: t850 without z850 names z850"""
+        if _parse_vert(name) is not None:
+            levels = (self.column or {}).get("vert") or []
+            fld, coord, _ = _parse_vert(name)
+            letters = {"P": "", "Z": "z", "Z_AGL": "z", "THETA": "t", "T": "t"}[coord] + {"ws": "uv", "theta": "t", "p": ""}.get(fld, fld)
+            return [f"{x}{l}" for l in levels for x in dict.fromkeys(letters) if f"{x}{l}" not in have]
         op = _parse_thermo(name)[0]
         letters = "tz" if op == "freeze" else "t" + (self.moisture or moisture_of(have) or "q") + ("z" if self.surface is not None else "")
         levels = sorted({int(n[1:]) for n in have if n[0] in letters and n[1:].isdigit()}, reverse=True)
@@ -585,7 +726,7 @@ class TruthDeriver:
             raw = []
             for name in scored:
                 raw += [c for c in self._needs(name, set(fields.names)) if c not in raw]
-            hit = (raw, LeadDeriver(raw, self.lat, self.lon, 1, list(scored), self.device, self.levels, self.surface, self.column), fields)
+            hit = (raw, LeadDeriver(raw, self.lat, self.lon, 1, list(scored), self.device, self.levels, self.surface, self.column, self.vertical), fields)
             self._derivers[key] = hit                          # (holds ``fields``: its id stays taken while the entry lives)
         raw, deriver, _ = hit
         state = torch.from_numpy(fields.at(time, raw)).to(deriver.device)
@@ -609,14 +750,15 @@ class DerivedProducts:
     dropped: dict = field(default_factory=dict)
 
 
-def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: bool = False, save_config: dict | None = None, surface=None):
+def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: bool = False, save_config: dict | None = None, surface=None,
+                 vertical=None):
     """``GlobalModel.derive_fields`` (core/models/base.py has the user-facing description)."""
     from .labeled import DataArray
     model = gm.model
     if n_steps < 0:
         raise ValueError("n_steps >= 0")
-    check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1, surface=surface is not None)      # before anything of the device
-    deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device, surface=surface)
+    check_request(model.out_channel_names, fields, model.grid.lat, model.grid.lon, 1, surface=surface is not None, vertical=vertical)      # before anything of the device
+    deriver = LeadDeriver(model.out_channel_names, model.grid.lat, model.grid.lon, 1, fields, device=model.device, surface=surface, vertical=vertical)
     require_gpu(model.device, "derive_fields derives with HIP kernels where the forecast lies: the model must be on a GPU")
     times, host = [], []
 
@@ -634,15 +776,15 @@ def derive_model(gm, start_time: datetime.datetime, n_steps: int, fields, save: 
     return da
 
 
-def derive_prediction(pred, fields, device="cuda:0", surface=None):
+def derive_prediction(pred, fields, device="cuda:0", surface=None, vertical=None):
     """Derived fields of a forecast that already exists: a ``GlobalPrediction``, a (time, channel, lat, lon) DataArray, a saved netCDF
     file or zarr store, or a list of such files (their time entries in order, duplicates of a valid time derived once).  Each time
     entry is uploaded on its own and goes through the same kernel as ``derive_fields``.  ``surface``: the (lat, lon) surface
-    geopotential of ``LeadDeriver``.  Returns DataArray(time, channel=fields, lat, lon)."""
+    geopotential of ``LeadDeriver``, ``vertical`` its options for the fields ``<field>@<surface>``.  Returns DataArray(time, channel=fields, lat, lon)."""
     from .labeled import DataArray
     saved = open_saved(pred, "derive_prediction")
     lat, lon = saved.lat, saved.lon
-    deriver = LeadDeriver(saved.names, lat, lon, 1, fields, device=device, surface=surface)
+    deriver = LeadDeriver(saved.names, lat, lon, 1, fields, device=device, surface=surface, vertical=vertical)
     require_gpu(device, "derive_prediction derives with HIP kernels: it needs a GPU", present=True)
     times, host = [], []
     for _, time, state in saved.states(deriver.device):

@@ -315,7 +315,7 @@ Plan = make_dataclass("Plan", "asked M products saved names derived exceed quant
 
 def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
                  neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None,
-                 extremes=None, archive=None, save=False, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None,
+                 extremes=None, archive=None, save=False, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None, derived=None, grid=None,
                  regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None,
                  perturb_scale=None) -> Plan:
     """Every refusal that needs no device, in one fixed order, and the request normalised once: the ``Plan``.  The keywords are those of
@@ -342,7 +342,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
         raise ValueError(f"unknown products {unknown}; choose from {PRODUCTS}")
     names, dnames = list(model.out_channel_names), list(derived or [])
     if derived is not None:
-        deriving.check_request(names, dnames, model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None)
+        deriving.check_request(names, dnames, model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None, vertical=vertical)
     known = names + dnames
     aplan, groups = None, []
     if aggregates is not None:
@@ -422,7 +422,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
              neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None,
-             save=False, breeding=None, stochastic=None, aggregates=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             save=False, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device (``plan_request``); returns (products, exceed, quantiles, saved step numbers) normalised."""
     p = plan_request(**locals())
@@ -611,10 +611,10 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     tracker = tracking.LeadTracker(gm.model_name, names, lat, lon, M, track_config, device=dev) if tracks else None
     deriver = derived = truth_deriver = None
     if dnames:                                             # derived fields (skyrim_amd/derived.py): their own products, labelled with their names
-        deriver = deriving.LeadDeriver(names, lat, lon, M, dnames, device=dev, surface=a.derived_surface)
+        deriver = deriving.LeadDeriver(names, lat, lon, M, dnames, device=dev, surface=a.derived_surface, vertical=a.vertical)
         # what every truth of these fields shares with the forecast: its levels, its thermodynamic columns, its kind of humidity, its surface mask
         truth_deriver = functools.partial(deriving.TruthDeriver, dnames, lat, lon, device=dev, levels=deriver.plan.levels or None,
-                                          column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=a.derived_surface)
+                                          column=deriver.plan.column or None, moisture=deriver.plan.moisture, surface=a.derived_surface, vertical=a.vertical)
         derived = Family(products(dnames, lat, lon, n_saved, "derived", p.keep_members, "derived-"),
                          lambda ens: _put(ens, "derived", deriving.DerivedProducts(dnames)),
                          scorer(dnames, lat, lon, truth, None, "derived", truth_deriver() if scores else None))
@@ -711,7 +711,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None, breeding=None, stochastic=None, aggregates=None, derived_surface=None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description): the plan of the request, the stages of a
@@ -723,7 +723,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     p = plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=events,
                      neighbourhoods_km=neighbourhoods_km, scores=scores, points=points, point_channels=point_channels, point_method=point_method,
                      scenarios=scenarios, spectra=spectra, objects=objects, extremes=extremes, archive=archive, save=save, breeding=breeding, stochastic=stochastic,
-                     aggregates=aggregates, derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
+                     aggregates=aggregates, vertical=vertical, derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
                      length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels, perturb_scale=perturb_scale)
     todo, families = stages(gm, p, start_time, truth, climatology, scores, tracks, track_config)
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()

@@ -20,6 +20,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     track_detect                                         (cyclone candidates of M states, include/skyrim_track.h)
     derive_fields                                        (derived channels of M states, include/skyrim_derive.h)
     thermo_fields                                        (column thermodynamics of M states, include/skyrim_thermo.h)
+    vert_fields                                          (fields of M states on chosen surfaces, include/skyrim_vert.h)
     regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
     event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
@@ -558,6 +559,12 @@ def _thermo_fields(members, table, program, params, out, surface) -> None:
     thermo.run(list(members), table, thermo.decode(program, params), out, surface)
 
 
+def _vert_fields(members, table, program, params, out, surface) -> None:
+    """``program`` / ``params``: vertical.encode(ops); ``surface``: the (H, W) surface geopotential on the device, or None."""
+    from . import vertical
+    vertical.run(list(members), table, vertical.decode(program, params), out, surface)
+
+
 # ---- regridding ------------------------------------------------------------------------------------------------------------------- #
 def _regrid(members, table, channels, row_start, row_count, row_weight, col_start, col_count, col_weight, out) -> None:
     """The two tables: ``regrid.Tables.on(device)``; ``out``: (M, len(channels), Ho, Wo)."""
@@ -777,6 +784,7 @@ _SCHEMAS = [
      "Tensor? h_core, Tensor rowc, Tensor(a!) records, Tensor(b!) count, Tensor(c!) workspace) -> ()", _track_detect),
     ("derive_fields(Tensor[] members, Tensor table, int[] program, float[] weights, Tensor(a!) out, Tensor? rowc, int[] edges) -> ()", _derive_fields),
     ("thermo_fields(Tensor[] members, Tensor table, int[] program, float[] params, Tensor(a!) out, Tensor? surface) -> ()", _thermo_fields),
+    ("vert_fields(Tensor[] members, Tensor table, int[] program, float[] params, Tensor(a!) out, Tensor? surface) -> ()", _vert_fields),
     ("regrid(Tensor[] members, Tensor table, int[] channels, Tensor row_start, Tensor row_count, Tensor row_weight, Tensor col_start, "
      "Tensor col_count, Tensor col_weight, Tensor(a!) out) -> ()", _regrid),
     ("event_counts(Tensor[] members, Tensor table, Tensor truth, int[] channels, int[] n_thr, float[] thresholds, Tensor(a!) counts, int[] hy, "

@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes
 from dataclasses import dataclass
 
+import numpy as np
+
 from . import native
 from .members import member_count, member_set
 
@@ -50,6 +52,34 @@ def load_library() -> ctypes.CDLL:
     if _lib is None:
         _lib = native.load(SPEC)
     return _lib
+
+
+def sk_log(x) -> np.ndarray:
+    """fp32 sk_log of include/skyrim_thermo.h (x positive, normal, finite) in numpy: the bits csrc/thermo_math.h makes on the host and the device"""
+    f = np.float32
+    m, e = np.frexp(np.asarray(x, f))
+    lo = m < f("0.70710678")
+    m = np.where(lo, m + m, m).astype(f)
+    e = (e - lo).astype(f)
+    s = (m - f(1)) / (m + f(1))
+    z = s * s
+    p = f("0.181818182")
+    for c in ("0.222222222", "0.285714286", "0.4", "0.666666667", "2"):
+        p = p * z + f(c)
+    return ((e * f("-2.12194440e-4") + s * p) + e * f("0.693359375")).astype(f)
+
+
+def sk_exp(x) -> np.ndarray:
+    """fp32 sk_exp of include/skyrim_thermo.h in numpy"""
+    f = np.float32
+    x = np.clip(np.asarray(x, f), f(-87), f(88)).astype(f)
+    n = np.rint(x * f("1.44269504")).astype(f)
+    r = (x - n * f("0.693359375")) - n * f("-2.12194440e-4")
+    p = f("1.98412698e-4")
+    for c in ("1.38888889e-3", "8.33333333e-3", "4.16666667e-2", "1.66666667e-1", "0.5"):
+        p = p * r + f(c)
+    p = ((p * r) * r + r) + f(1)
+    return np.ldexp(p, n.astype(np.int32)).astype(f)
 
 
 @dataclass(frozen=True)
