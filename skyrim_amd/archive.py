@@ -538,7 +538,7 @@ class ArchiveMembers:
 
 
 REPLAY_ARGS = ("products", "exceed", "quantiles", "channels", "keep_members", "derived", "derived_surface", "vertical", "grid", "regrid_method", "scores",
-               "truth", "climatology", "events", "neighbourhoods_km", "points", "point_channels", "point_method", "aggregates", "extremes",
+               "truth", "climatology", "events", "neighbourhoods_km", "points", "point_channels", "point_method", "aggregates", "neighbourhood", "extremes",
                "scenarios", "spectra", "objects", "tracks", "track_config", "save", "save_config")
 
 
@@ -570,7 +570,7 @@ def replay(arch, device="cuda:0", **request):
                          data_source=None)
     n_steps = len(arch.leads) - 1
     extra = {k: r[k] for k in ("events", "neighbourhoods_km", "points", "point_channels", "point_method", "scenarios", "spectra", "objects",
-                               "extremes", "aggregates", "derived_surface", "vertical", "derived", "grid", "regrid_method") if k in r}
+                               "extremes", "aggregates", "neighbourhood", "derived_surface", "vertical", "derived", "grid", "regrid_method") if k in r}
     try:
         p = ensemble.plan_request(gm.model, n_steps, arch.M, int(arch.manifest.get("seed") or 0), r["products"], r["exceed"], r["quantiles"],
                                   r["channels"], 1, r["keep_members"], scores=r["scores"], **extra)

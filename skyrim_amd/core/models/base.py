@@ -121,8 +121,8 @@ class GlobalModel:
                           points=None, point_channels: List[str] | None = None, point_method: str = "bilinear",
                           scenarios: dict | None = None, spectra: dict | None = None, objects: dict | None = None, extremes: dict | None = None,
                           archive: dict | None = None, breeding: dict | None = None, stochastic: dict | None = None,
-                          aggregates: List[str] | None = None, vertical: dict | None = None, derived_surface=None,
-                          derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
+                          aggregates: List[str] | None = None, neighbourhood: List[str] | None = None, vertical: dict | None = None,
+                          derived_surface=None, derived: List[str] | None = None, grid=None, regrid_method: str = "conservative", perturbation: str = "white",
                           length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
                           perturb_channels: List[str] | None = None):
         """An ``n_members`` ensemble of THIS model from perturbed initial conditions (skyrim_amd/ensemble.py): member m
@@ -165,6 +165,12 @@ class GlobalModel:
         ``point_channels`` (raw channels and fields of ``derived``; default ``channels``, or every raw and derived channel): the
         ``points.PointForecast`` (member, time, channel, point) lands in ``EnsembleForecast.points``, and each aggregate group's fields at
         the points, sampled when a window closes, in ``EnsembleForecast.aggregated[label].points``.
+        ``neighbourhood=["ws10m:max:100km", "t2m:frac_above@303.15:50km", "msl:mean:200km"]`` asks for neighbourhood fields
+        ``channel:stat:radius`` (skyrim_amd/neighbourhood.py) of raw channels and of the fields in ``derived``: every member is
+        reduced over the great-circle disc around every grid point on the device (``stat``: max, min, the area-weighted mean,
+        frac_above@<threshold>), and the same ``products``, ``exceed`` / ``quantiles`` / ``events`` under the fields' names
+        (``ws10m_max_100km``: ``exceed`` of it is the chance of the event SOMEWHERE within 100 km), the members with ``keep_members``, the
+        scores with ``scores=True`` and the points with ``points=`` land in ``EnsembleForecast.neighbourhood``.
         ``scenarios={"channels": ["z500"], "region": (lat_s, lat_n, lon_w, lon_e), "n_clusters": 3, "n_eofs": 3, "normalise": "spread"}``
         relates the members to each other as patterns (skyrim_amd/scenarios.py): at each saved lead time ONE device pass
         makes the member Gram matrix of the named raw channels over the region (None: the globe; a box may cross the date line), and from
@@ -229,6 +235,8 @@ class GlobalModel:
             extra.update(grid=grid, regrid_method=regrid_method)
         if aggregates is not None:
             extra["aggregates"] = aggregates
+        if neighbourhood is not None:
+            extra["neighbourhood"] = neighbourhood
         if points is not None:
             extra.update(points=points, point_channels=point_channels, point_method=point_method)
         if scenarios is not None:
@@ -312,6 +320,17 @@ class GlobalModel:
         forecast of ``{model}-agg<label>``.  A request that cannot be served is refused with ValueError before the device is touched."""
         from ... import aggregate
         return aggregate.aggregate_model(self, start_time, n_steps, list(aggregates), derived=derived, save=save, save_config=save_config)
+
+    def neighbourhood_forecast(self, start_time: datetime.datetime, n_steps: int = 4, neighbourhood: List[str] = (),
+                               derived: List[str] | None = None, save: bool = False, save_config: dict | None = None):
+        """Neighbourhood fields of the deterministic forecast at the lead times 0 .. ``n_steps`` (skyrim_amd/neighbourhood.py).
+        ``neighbourhood``: requests ``channel:stat:radius`` -- ``stat`` one of max, min, mean (area-weighted), frac_above@<threshold>;
+        ``radius`` ``<N>km``, the radius of the great-circle disc around every grid point; ``derived``: derived fields the requests may name.
+        The model's TimeLoop is advanced and every state is reduced where it lies in HBM; only the fields cross to the host.  Returns
+        DataArray(time, channel = ``ws10m_max_100km`` ..., lat, lon); ``save=True`` writes it as the forecast of ``{model}-nbr``.  A request
+        that cannot be served is refused with ValueError before the device is touched."""
+        from ... import neighbourhood as nbr
+        return nbr.neighbourhood_model(self, start_time, n_steps, list(neighbourhood), derived=derived, save=save, save_config=save_config)
 
     def point_forecast(self, start_time: datetime.datetime, n_steps: int = 4, points=None, channels: List[str] | None = None,
                        derived: List[str] | None = None, method: str = "bilinear", save: bool = False, save_config: dict | None = None):

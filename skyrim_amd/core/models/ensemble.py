@@ -132,6 +132,10 @@ class GlobalEnsemble:
         raise ValueError(f"derive_fields derives from the forecast of ONE model; {self!r} is a multi-model ensemble -- derive from its saved "
                          "ensemble-mean files with skyrim_amd.derived.derive_prediction, or build Skyrim(<one model name>)")
 
+    def neighbourhood_forecast(self, *args, **kwargs):
+        raise ValueError(f"neighbourhood_forecast reduces the forecast of ONE model; {self!r} is a multi-model ensemble -- make the fields of its "
+                         "saved ensemble-mean files with skyrim_amd.neighbourhood.neighbourhood_prediction, or build Skyrim(<one model name>)")
+
     def aggregate_forecast(self, *args, **kwargs):
         raise ValueError(f"aggregate_forecast aggregates the forecast of ONE model; {self!r} is a multi-model ensemble -- aggregate its saved "
                          "ensemble-mean files with skyrim_amd.aggregate.aggregate_prediction, or build Skyrim(<one model name>)")

@@ -145,6 +145,10 @@ class GraphcastModel(GlobalModel):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator derive_fields advances: "
                                   "derive from its forecast with skyrim_amd.derived.derive_prediction(forecast_or_saved_files, fields)")
 
+    def neighbourhood_forecast(self, *args, **kwargs):
+        raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator neighbourhood_forecast advances: "
+                                  "make the fields of its forecast with skyrim_amd.neighbourhood.neighbourhood_prediction(forecast_or_saved_files, requests)")
+
     def aggregate_forecast(self, *args, **kwargs):
         raise NotImplementedError("GraphCast is driven through its own stepper, not through the TimeLoop generator aggregate_forecast advances: "
                                   "aggregate its forecast with skyrim_amd.aggregate.aggregate_prediction(forecast_or_saved_files, aggregates)")

@@ -127,6 +127,19 @@ class Skyrim:
         from .. import aggregate
         return aggregate.aggregate_prediction(pred, aggregates, derived=derived, device=device)
 
+    def neighbourhood_forecast(self, start_time: datetime.datetime, n_steps: int = 4, neighbourhood=(), derived=None, **kwargs):
+        """Neighbourhood fields (maximum, minimum, mean, fraction above a threshold within R km of every grid point) of the single model's
+        forecast as a DataArray(time, channel = ``ws10m_max_100km`` ..., lat, lon) (``GlobalModel.neighbourhood_forecast`` has the
+        arguments).  ``ensemble_forecast(..., neighbourhood=[...])`` gives their ensemble products."""
+        start_time = start_time.replace(second=0, microsecond=0)
+        return self.model.neighbourhood_forecast(start_time, n_steps=n_steps, neighbourhood=neighbourhood, derived=derived, **kwargs)
+
+    @staticmethod
+    def neighbourhood_prediction(pred, neighbourhood, derived=None, device="cuda:0"):
+        """Neighbourhood fields of a forecast that is already in memory or on disk (``neighbourhood.neighbourhood_prediction``)."""
+        from .. import neighbourhood as nbr
+        return nbr.neighbourhood_prediction(pred, neighbourhood, derived=derived, device=device)
+
     def point_forecast(self, start_time: datetime.datetime, n_steps: int = 4, points=None, **kwargs):
         """The single model's forecast at scattered places -- stations, cities, wind farms -- as a ``points.PointForecast``
         (``GlobalModel.point_forecast`` has the arguments).  ``ensemble_forecast(..., points=...)`` gives every member there."""

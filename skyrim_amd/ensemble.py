@@ -266,6 +266,7 @@ class EnsembleForecast:
     derived: object = None       # derived.DerivedProducts with ``derived=[...]``
     regridded: object = None     # regrid.RegriddedProducts with ``grid=...``
     aggregated: dict = field(default_factory=dict)      # {window label: aggregate.AggregatedProducts} with ``aggregates=[...]``
+    neighbourhood: object = None # neighbourhood.NeighbourhoodProducts with ``neighbourhood=[...]``
     points: object = None        # points.PointForecast with ``points=...``
     scenarios: object = None     # scenarios.Scenarios with ``scenarios={...}``
     spectra: object = None       # spectra.Spectra with ``spectra={...}``
@@ -305,17 +306,18 @@ def scenario_std(model, names) -> np.ndarray:
 # keywords as given, by name -- what a ``Lead*`` object normalises itself reaches it as it came; ``saved``: the saved step numbers;
 # ``names`` / ``derived``: the model's output channels and the derived fields ([]: none); ``exceed`` / ``quantiles`` / ``events``:
 # ``{family: {field: values}}`` with the families ``"raw"`` (the regridded channels share it), ``"derived"`` and ``"agg{label}"`` per window
-# group; ``radii``: the events' neighbourhoods, km; ``keep_members``: the raw, derived and aggregated ones; ``noise`` / ``breeding`` /
+# group and ``"nbr"`` (the neighbourhood fields); ``radii``: the events' neighbourhoods, km; ``keep_members``: the raw, derived and aggregated ones; ``noise`` / ``breeding`` /
 # ``stochastic`` / ``aggregate``: the plans of those modules, or None; ``regrid``: ``regrid.Tables`` or None; ``points``: ``points.Points`` or
 # None; ``point_channels``: what is sampled there (``point_channels``, else ``channels``, else None = every raw channel); ``extremes``: the
-# checked ``extremes.Request`` or None; ``archive``: the checked ``archive=`` request (``archive.check_request``) or None.
+# checked ``extremes.Request`` or None; ``archive``: the checked ``archive=`` request (``archive.check_request``) or None; ``neighbourhood``:
+# ``neighbourhood.Plan`` or None -- its fields are the family ``"nbr"``.
 Plan = make_dataclass("Plan", "asked M products saved names derived exceed quantiles events radii keep_members keep_regridded noise breeding "
-                      "stochastic aggregate regrid points point_channels extremes archive".split())
+                      "stochastic aggregate regrid points point_channels extremes archive neighbourhood".split())
 
 
 def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
                  neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None,
-                 extremes=None, archive=None, save=False, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None, derived=None, grid=None,
+                 extremes=None, archive=None, save=False, breeding=None, stochastic=None, aggregates=None, neighbourhood=None, vertical=None, derived_surface=None, derived=None, grid=None,
                  regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None, perturb_channels=None,
                  perturb_scale=None) -> Plan:
     """Every refusal that needs no device, in one fixed order, and the request normalised once: the ``Plan``.  The keywords are those of
@@ -325,7 +327,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
     which ``run`` passes and ``validate`` has not."""
     asked = SimpleNamespace(**locals())
     from . import aggregate, archive as archiving, breeding as breed, derived as deriving, extremes as extreming, noise, objects as objecting
-    from . import points as pointing, regrid, scenarios as scen, spectra as spec, stochastic as stoch
+    from . import neighbourhood as nbr, points as pointing, regrid, scenarios as scen, spectra as spec, stochastic as stoch
     from .core.models.utils import _PINNED_LIMIT
     if _world_size() > 1:
         raise NotImplementedError("ensemble_forecast runs all members on one GPU; under a process group of more than one rank use "
@@ -345,6 +347,17 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
         deriving.check_request(names, dnames, model.grid.lat, model.grid.lon, n_members, surface=derived_surface is not None, vertical=vertical)
     known = names + dnames
     aplan, groups = None, []
+    n_asked = [nbr.parse_request(r).name for r in neighbourhood] if isinstance(neighbourhood, (list, tuple)) else []
+    if n_asked:                                             # neighbourhood fields feed the statistics, the scorer, the events and the points, no other product
+        for what, req in (("aggregates", [getattr(r, "channel", str(r).split(":")[0].strip()) for r in aggregates or []]), ("extremes", extremes),
+                          ("objects", objects), ("spectra", spectra), ("scenarios", scenarios)):
+            asked_there = list(req) if isinstance(req, (dict, list, tuple)) else []
+            if isinstance(req, dict):
+                asked_there += [c for k in ("channels", "fields") if isinstance(req.get(k), (list, tuple)) for c in req[k]]
+            named = [f for f in n_asked if f in asked_there]
+            if named:
+                raise ValueError(f"{what}: {named} are neighbourhood fields; neighbourhood fields as input to {what}= are out of scope "
+                                 "(DESIGN.md 35)")
     if aggregates is not None:
         aplan = aggregate.check_request(known, aggregates, model.time_step, n_steps, model.grid.lat, model.grid.lon, n_members)
         groups = aplan.groups
@@ -352,6 +365,14 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
         if clash:
             raise ValueError(f"aggregates: {clash} are already channels of this forecast")
         known = known + [f for g in groups for f in g.fields]
+    nbplan = None
+    if neighbourhood is not None:
+        if grid is not None:
+            raise ValueError("neighbourhood= together with grid= is not supported: neighbourhood fields are made on the model's own global "
+                             "grid only (DESIGN.md 35, out of scope)")
+        nbplan = nbr.check_request(names, neighbourhood, model.grid.lat, model.grid.lon, n_members, dnames, [f for g in groups for f in g.fields])
+        known = known + nbplan.fields
+    n_fields = nbplan.fields if nbplan is not None else []
     tabs = None
     if grid is not None:
         if derived is not None:
@@ -363,7 +384,8 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
             if ch not in known:
                 raise ValueError(f"{what}: channel {ch!r} is not an output channel of this model"
                                  + ("" if derived is None else " or one of the derived fields")
-                                 + ("" if aplan is None else " or one of the aggregates"))
+                                 + ("" if aplan is None else " or one of the aggregates")
+                                 + ("" if nbplan is None else " or one of the neighbourhood fields"))
             if not 1 <= len(vals) <= cap:
                 raise ValueError(f"{what}[{ch!r}]: 1 to {cap} values per channel, got {len(vals)}")
     for ch, vals in (quantiles or {}).items():
@@ -389,6 +411,8 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
         pointing.host_limit(n_members, len(saved), len(picked), len(pts))
         for g in groups:
             pointing.check_request(g.fields, model.grid.lat, model.grid.lon, n_members, pts, None, point_method, max(g.n_windows, 1))
+        if n_fields:
+            pointing.check_request(n_fields, model.grid.lat, model.grid.lon, n_members, pts, None, point_method, len(saved))
     a_fields = [f for g in groups for f in g.fields]
     if scenarios is not None:                               # raw channels of the model's grid only; names of other products are refused by name
         if scen.check_request(names, model.grid.lat, model.grid.lon, n_members, scenarios, scores, dnames + a_fields)["normalise"] == "std":
@@ -404,7 +428,7 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
     if keep_members not in (False, True, "regridded") or (keep_members == "regridded" and grid is None):
         raise ValueError('keep_members is False, True or, with grid=, "regridded" (only the regridded members are kept)')
     if keep_members:
-        planes = len(saved) * (len(names) + len(dnames)) + sum(g.n_windows * len(g.fields) for g in groups)
+        planes = len(saved) * (len(names) + len(dnames) + len(n_fields)) + sum(g.n_windows * len(g.fields) for g in groups)
         need = 0 if keep_members == "regridded" else int(n_members) * planes * len(model.grid.lat) * len(model.grid.lon) * 4
         if tabs is not None:                                # the regridded members are checked at the size they have
             need += int(n_members) * len(saved) * len(names) * tabs.lat.size * tabs.lon.size * 4
@@ -412,17 +436,17 @@ def plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, c
             raise ValueError(f"keep_members=True would hold {need / 2 ** 30:.1f} GiB of member states on the host (limit "
                              f"{_PINNED_LIMIT / 2 ** 30:.0f} GiB): fewer members, fewer steps or a larger save_every -- or archive={{...}}, which writes "
                              "the members to files as they are made and replays them later (skyrim_amd/archive.py)")
-    fields_of = dict({"derived": dnames} if dnames else {}, **{f"agg{g.label}": g.fields for g in groups})
+    fields_of = dict({"derived": dnames} if dnames else {}, **{f"agg{g.label}": g.fields for g in groups}, **({"nbr": n_fields} if n_fields else {}))
     exceed = {k: [float(np.float32(v)) for v in vs] for k, vs in (exceed or {}).items()}
     quantiles = {k: [float(v) for v in vs] for k, vs in (quantiles or {}).items()}
     return Plan(asked, int(n_members), products, saved, names, dnames, _per_family(exceed, fields_of), _per_family(quantiles, fields_of),
                 _per_family(ev, fields_of), radii, bool(keep_members) and keep_members != "regridded", bool(keep_members) and grid is not None,
-                nplan, bplan, splan, aplan, tabs, pts, point_channels, xreq, areq)
+                nplan, bplan, splan, aplan, tabs, pts, point_channels, xreq, areq, nbplan)
 
 
 def validate(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=None,
              neighbourhoods_km=(), scores=False, points=None, point_channels=None, point_method="bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None,
-             save=False, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
+             save=False, breeding=None, stochastic=None, aggregates=None, neighbourhood=None, vertical=None, derived_surface=None, derived=None, grid=None, regrid_method="conservative", perturbation="white", length_scale_km=500.0, alpha=2.0, lmax=None,
              perturb_channels=None):
     """Every refusal that needs no device (``plan_request``); returns (products, exceed, quantiles, saved step numbers) normalised."""
     p = plan_request(**locals())
@@ -557,7 +581,8 @@ class Family:
         target, ps = self.hang(ens), self.products
         ps.fill(target, self.times, self.select, window_start=self.starts)
         if self.points is not None:
-            target.points = self.points.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid, window_start=self.starts)
+            target.points = self.points.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid,
+                                               **({} if self.starts is None else dict(window_start=self.starts)))
         if self.extremes is not None:
             target.extremes = _hang(self.extremes.result(product_model_name(ps.model_name, ps.M, ps.prefix[:-1]), fid, window_start=self.starts),
                                     fid, xsink)
@@ -574,7 +599,7 @@ Stage = collections.namedtuple("Stage", "add due finish close", defaults=(None, 
 
 
 def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, tracks=False, track_config=None) -> tuple[list, list]:
-    """(the stages of a lead time, the families: raw, derived, regridded, then the window groups).  THE place a product is wired in: its
+    """(the stages of a lead time, the families: raw, derived, regridded, neighbourhood, then the window groups).  THE place a product is wired in: its
     ``Lead*`` object is made here, in the order the refusals of these objects have, with the checks that need the truth, and it gets one
     ``Stage`` in the list at the end, whose order is the order of the launches of a lead (DESIGN.md 17 has the rules it keeps):
     ``add(L)`` is called where ``due(L)`` (default: at saved leads), ``finish(ens, fid, sink)`` once after the last lead, ``close()`` when
@@ -582,6 +607,7 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     a lead: ``k``, ``time``, ``slot`` (the entry of a saved lead, else None), ``states``, ``table``, ``sink`` (where files go) and, set by the
     stages before, ``truth`` (the raw scorer's truth state), ``derived`` = (states, table) of the deriver, ``dtruth``."""
     from . import aggregate, archive as archiving, derived as deriving, extremes as extreming, objects as objecting, points as pointing, regrid
+    from . import neighbourhood as nbr
     from . import scenarios as scen
     from . import spectra as spec
     from . import tracks as tracking, verify
@@ -628,6 +654,14 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
                                    lambda ens, g=g: ens.aggregated.setdefault(g.label, aggregate.AggregatedProducts(
                                        g.label, list(g.fields), incomplete=p.aggregate.incomplete.get(g.label))),
                                    scorer(g.fields, lat, lon, truth, None, f"agg{g.label}", hook), windows=True)
+    neighbour = neighbours = None
+    if p.neighbourhood is not None:                        # neighbourhood fields (skyrim_amd/neighbourhood.py): their own products, read like raw channels
+        nfields = p.neighbourhood.fields
+        neighbour = nbr.LeadNeighbourhood(names, lat, lon, M, p.neighbourhood.requests, dev, dnames)
+        hook = nbr.TruthNeighbourhood(p.neighbourhood.requests, lat, lon, dev, inner=truth_deriver and truth_deriver()) if scores else None
+        neighbours = Family(products(nfields, lat, lon, n_saved, "nbr", p.keep_members, "nbr-"),
+                            lambda ens: _put(ens, "neighbourhood", nbr.NeighbourhoodProducts(list(nfields))),
+                            scorer(nfields, lat, lon, truth, None, "nbr", hook))
     regridder = regridded = None
     if a.grid is not None:                                 # the same products on the target grid (skyrim_amd/regrid.py)
         regridder = regrid.LeadRegridder(names, lat, lon, M, a.grid, a.regrid_method, device=dev)
@@ -640,6 +674,8 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
     pointer = pointing.LeadPoints(names, lat, lon, M, p.points, p.point_channels, a.point_method, dev, dnames, n_saved) if p.points is not None else None
     for g in groups if p.points is not None else ():
         windowed[g.label].points = pointing.LeadPoints(g.fields, lat, lon, M, p.points, None, a.point_method, dev, (), max(g.n_windows, 1))
+    if neighbours is not None and p.points is not None:
+        neighbours.points = pointing.LeadPoints(nfields, lat, lon, M, p.points, None, a.point_method, dev, (), n_saved)
     # EFI, SOT and tail odds against a quantile climate (skyrim_amd/extremes.py): raw channels and derived fields at each saved lead, a window
     # group's fields when a window closes
     x = p.extremes
@@ -672,6 +708,12 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
         L.derived = deriver.add(L.states, L.table)
         L.dtruth = derived.score(L.time, *L.derived)
 
+    def neighbourhoods(L):                                 # one launch for the ops on the states, one for those on the deriver's buffer
+        fields = neighbour.add(L.states, L.table, L.derived)
+        neighbours.score(L.time, *fields)
+        if L.slot is not None:
+            neighbours.reduce(L.time, *fields, L.slot)
+
     def close_windows(L):                                  # windows close independently of ``save_every``
         for c in aggregator.add(L.k, L.time, L.states, L.table, L.derived):
             windowed[c.label].reduce(c.end, c.states, c.table, c.window, c.start)
@@ -690,6 +732,7 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
         (deriver, Stage(derive, lambda L: _saved(L) or derived.scorer is not None or (folds_derived and L.k >= 1))),
         (spectrists.get("derived"), Stage(lambda L: spectrists["derived"].add(L.time, *L.derived, L.dtruth))),
         (deriver, Stage(lambda L: derived.reduce(L.time, *L.derived, L.slot), finish=lambda ens, fid, sink: derived.fill(ens, fid))),
+        (neighbour, Stage(neighbourhoods, lambda L: _saved(L) or neighbours.scorer is not None, lambda ens, fid, sink: neighbours.fill(ens, fid))),
         (scenarist, Stage(lambda L: scenarist.add(L.time, L.states, L.table, L.truth),
                           finish=hung("scenarios", lambda fid: scenarist.result(label, fid), False))),
         (spectrists.get("raw"), Stage(lambda L: spectrists["raw"].add(L.time, L.states, L.table, L.truth))),
@@ -704,14 +747,14 @@ def stages(gm, p: Plan, start_time, truth=None, climatology=None, scores=False, 
         (regridder, Stage(lambda L: regridded.lead(L.time, *regridder.add(L.states, L.table), L.slot),     # ONE launch: all channels, all members
                           lambda L: _saved(L) or regridded.scorer is not None, lambda ens, fid, sink: regridded.fill(ens, fid))),
     ]
-    return [stage for wanted, stage in todo if wanted], [f for f in (raw, derived, regridded) if f is not None] + list(windowed.values())
+    return [stage for wanted, stage in todo if wanted], [f for f in (raw, derived, regridded, neighbours) if f is not None] + list(windowed.values())
 
 
 def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10, perturb_scale: float = 1e-3, seed: int = 0,
         products=("mean", "spread"), exceed=None, quantiles=None, channels=None, save_every: int = 1, keep_members: bool = False,
         save: bool = False, save_config: dict | None = None, truth=None, climatology=None, scores: bool = False,
         tracks: bool = False, track_config=None, events=None, neighbourhoods_km=(), points=None, point_channels=None,
-        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None, breeding=None, stochastic=None, aggregates=None, vertical=None, derived_surface=None,
+        point_method: str = "bilinear", scenarios=None, spectra=None, objects=None, extremes=None, archive=None, breeding=None, stochastic=None, aggregates=None, neighbourhood=None, vertical=None, derived_surface=None,
         derived=None, grid=None, regrid_method: str = "conservative", perturbation: str = "white", length_scale_km: float = 500.0, alpha: float = 2.0, lmax: int | None = None,
         perturb_channels=None) -> EnsembleForecast:
     """``GlobalModel.ensemble_forecast`` (core/models/base.py has the user-facing description): the plan of the request, the stages of a
@@ -723,7 +766,7 @@ def run(gm, start_time: datetime.datetime, n_steps: int = 4, n_members: int = 10
     p = plan_request(model, n_steps, n_members, seed, products, exceed, quantiles, channels, save_every, keep_members, events=events,
                      neighbourhoods_km=neighbourhoods_km, scores=scores, points=points, point_channels=point_channels, point_method=point_method,
                      scenarios=scenarios, spectra=spectra, objects=objects, extremes=extremes, archive=archive, save=save, breeding=breeding, stochastic=stochastic,
-                     aggregates=aggregates, vertical=vertical, derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
+                     aggregates=aggregates, neighbourhood=neighbourhood, vertical=vertical, derived_surface=derived_surface, derived=derived, grid=grid, regrid_method=regrid_method, perturbation=perturbation,
                      length_scale_km=length_scale_km, alpha=alpha, lmax=lmax, perturb_channels=perturb_channels, perturb_scale=perturb_scale)
     todo, families = stages(gm, p, start_time, truth, climatology, scores, tracks, track_config)
     x0 = get_initial_condition_for_model(model, gm.data_source, start_time).to(model.device, torch.float32).contiguous()

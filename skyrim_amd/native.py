@@ -1,4 +1,4 @@
-"""The one binding policy of the C-ABI libraries (include/skyrim_{pangu,sfno,graphcast,fcn,dlwp,fuxi,fengwu,io,ens,score,noise,track,derive,thermo,vert,point,gram,breed,stoch,spec,object,clim,pack,regrid,agg,event}.h, built into skyrim_amd/lib/).
+"""The one binding policy of the C-ABI libraries (include/skyrim_{pangu,sfno,graphcast,fcn,dlwp,fuxi,fengwu,io,ens,score,noise,track,derive,thermo,vert,point,gram,breed,stoch,spec,object,clim,pack,nbr,regrid,agg,event}.h, built into skyrim_amd/lib/).
 
 Each binding module declares a ``Spec`` -- file stem, override variable, symbol prefix, ABI version, signature table -- and its
 ``load_library()`` calls ``load(SPEC)`` once: the path (the override variable names a variant build), the ctypes signatures and the ABI

@@ -24,6 +24,7 @@ are stream-ordered, allocation-free and capturable in a HIP graph.
     regrid                                               (M states on another lat-lon grid, include/skyrim_regrid.h)
     event_counts                                         (joint counts and neighbourhood sums of threshold events, include/skyrim_event.h)
     agg_update                                           (one lead time folded into the time-window aggregates, include/skyrim_agg.h)
+    nbr_fields                                           (max, min, mean, fraction above over great-circle discs, include/skyrim_nbr.h)
     point_gather                                         (M states sampled at scattered points, include/skyrim_point.h)
     gram / member_combine                                (member Gram matrices and linear combinations of M states, include/skyrim_gram.h)
     zonal_spectra                                        (zonal power spectra of M states, their mean, spread and errors, include/skyrim_spec.h)
@@ -592,6 +593,14 @@ def _agg_update(members, table, program, params, stamp: float, acc) -> None:
     aggregate.run(list(members), table, aggregate.decode(program, params), acc, stamp)
 
 
+# ---- neighbourhood fields ------------------------------------------------------------------------------------------------------------ #
+def _nbr_fields(members, table, program, params, half, weights, out) -> None:
+    """``program`` / ``params``: neighbourhood.encode(ops); ``half``: one int32 (H, 2 reach + 1) disc table per radius; ``weights``: float64
+    (H); ``out``: (M, D, H, W)."""
+    from . import neighbourhood
+    neighbourhood.run(list(members), table, neighbourhood.decode(program, params), list(half), weights, out)
+
+
 # ---- climate-relative extremes ---------------------------------------------------------------------------------------------------------- #
 def _clim_extremes(members, table, channels, clim, levels, floor, sot_index, sot_frac, sot_ref, sot_base, prob_level, prob_below, efi, sot,
                    prob) -> None:
@@ -790,6 +799,7 @@ _SCHEMAS = [
     ("event_counts(Tensor[] members, Tensor table, Tensor truth, int[] channels, int[] n_thr, float[] thresholds, Tensor(a!) counts, int[] hy, "
      "Tensor? hx, Tensor(b!)? sums, Tensor(c!)? workspace) -> ()", _event_counts),
     ("agg_update(Tensor[] members, Tensor table, int[] program, float[] params, float stamp, Tensor(a!) acc) -> ()", _agg_update),
+    ("nbr_fields(Tensor[] members, Tensor table, int[] program, float[] params, Tensor[] half, Tensor weights, Tensor(a!) out) -> ()", _nbr_fields),
     ("point_gather(Tensor[] members, Tensor table, int[] channels, Tensor records, Tensor(a!) out) -> ()", _point_gather),
     ("gram(Tensor[] members, Tensor table, Tensor? truth, int[] channels, int[] region, Tensor lat_weight, Tensor(a!) out, "
      "Tensor(b!) workspace) -> ()", _gram),
