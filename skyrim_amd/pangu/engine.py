@@ -459,7 +459,7 @@ class PanguEngine:
         return out
 
     def patch_recover(self, skip: torch.Tensor, x4: torch.Tensor) -> torch.Tensor:
-        out = torch.zeros(self.state_shape, dtype=torch.float32, device=self.device)
+        out = torch.empty(self.state_shape, dtype=torch.float32, device=self.device)      # as ``step`` allocates: the epilogue writes every element
         skip, x4 = skip.contiguous(), x4.contiguous()
         self._chk_dev(skip, self.tokens(1)), self._chk_dev(x4, self.tokens(1))
         ops.hip.pangu_patch_recover(self._ctx.value, skip, x4, out)

@@ -147,11 +147,12 @@ def test_longitude_shift_equivariance_toy(eng, toy):
     assert O.per_channel_rel_err(torch.roll(y2, -96, dims=-1).cpu(), y.cpu()).max().item() < 3 * STEP_TOL[eng.precision]
 
 
-@pytest.mark.parametrize("grid", [(61, 192), (73, 288), (25, 96)])
+@pytest.mark.parametrize("grid", [(61, 192), (73, 288), (25, 96), (24, 96), (33, 96), (27, 192)])
 def test_other_geometries_step_vs_oracle(grid):
     """Padding / window-type / down-sample parity cases the 49x192 toy and the full grid do not hit: an even coarse
     latitude count (61 -> 16 rows: no DownSample pad row), three longitude window columns at the coarse level (288),
-    and the smallest grid the window shapes allow (25x96: one longitude window at the coarse level)."""
+    and the smallest grid the window shapes allow (25x96: one longitude window at the coarse level); no latitude padding at all
+    and a single latitude window in layers 1 / 4 (24x96), window paddings of 3 and 1 rows (33x96), one row of input padding (27x192)."""
     from skyrim_amd.pangu.engine import PanguEngine
     g = PanguGeometry(*grid)
     params = init_synthetic(g, 5)
