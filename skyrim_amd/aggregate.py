@@ -22,10 +22,9 @@ from dataclasses import dataclass, field, replace
 
 import numpy as np
 
-from . import native
+from . import native, program
 from .common import world_size as _world_size
 from .leads import open_saved, require_gpu, run_model
-from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS = 64, 16                                   # include/skyrim_agg.h SKAGG_MAX_*
 MAX, MIN, SUM, COUNT_ABOVE = 1, 2, 3, 4                         # SKAGG_MAX ...
@@ -106,7 +105,8 @@ def decode(ints, floats) -> list:
 def describe(ops, M, C, H, W, D, member_stride, stamp=0.0, member_align=16) -> AggDesc:
     """The descriptor of a call, its pointers still NULL."""
     d = AggDesc()
-    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride, d.stamp = M, member_align, C, H, W, D, member_stride, stamp
+    program.fill_head(d, M, C, H, W, D, member_stride, member_align)
+    d.stamp = stamp
     ops = list(ops)
     d.n_ops = len(ops)
     for k, op in enumerate(ops[:MAX_OPS]):
@@ -119,22 +119,12 @@ def run(members, table, ops, acc, stamp) -> None:
     """One ``skagg_update``: fold the M ``members`` (equal-shaped contiguous float32 (C, H, W) device tensors of one lead time; ``table`` =
     ``ensemble.member_table(members)``) into ``acc``, float32 (M, D, H, W), by the ops ``ops``; ``stamp``: the lead time in hours.
     Queued on torch's current stream.  As in ``derived.run``, the contents of ``table`` are trusted to be the addresses of ``members``."""
-    import torch
     ops = list(ops)
-    member_count(members, "agg_update", MAX_MEMBERS)
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise ValueError(f"agg_update: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    M, dev, align = member_set(members, table, "agg_update", MAX_MEMBERS)
-    C, H, W = members[0].shape
-    pa = native.tensor_ptr(acc, "agg_update: acc", torch.float32, dev)
-    if acc.dim() != 4 or acc.shape[0] != M or tuple(acc.shape[2:]) != (H, W):
-        raise ValueError(f"agg_update: acc must be ({M}, D, {H}, {W})")
-    D = acc.shape[1]
+    M, dev, align, C, H, W, D, pa = program.bind("agg_update", members, table, ops, acc, "agg_update: acc", MAX_MEMBERS, MAX_OPS)
     d = describe(ops, M, C, H, W, D, D * H * W, float(stamp), align)
     d.members, d.acc = table.data_ptr(), pa
     lib = load_library()
-    with torch.cuda.device(dev):
-        native.check(lib.skagg_update(ctypes.byref(d), native.stream(dev)), "skagg_update", lib)
+    program.launch(lib, lib.skagg_update, d, dev)
 
 
 # ---- requests ---------------------------------------------------------------------------------------------------------------------------- #

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "../../include/skyrim_agg.h"
 #include "fields.h"
+#include "program.h"
 
 #pragma clang fp contract(off)
 
@@ -32,6 +33,7 @@ struct AggArgs {
 };
 
 using namespace skfields;
+using namespace skprogram;
 
 // one op on the VEC points `x` of a lane; `e` is the lane's first point in a plane
 template <int VEC>
@@ -78,13 +80,12 @@ __global__ void __launch_bounds__(256) agg_kernel(const AggArgs a, const float* 
     const int lane = threadIdx.x & 63;
     const uint32_t total = (uint32_t)a.M * a.tiles, nw = gridDim.x * 4u;
     for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += nw) {
-        const int m = uniform((int)(w / a.tiles));
-        const uint32_t t = (uint32_t)uniform((int)(w - (uint32_t)m * a.tiles));
-        const int g = uniform((int)(t / a.tiles_per_group));
-        const uint32_t tile = t - (uint32_t)g * a.tiles_per_group;
+        const MemberTile mt = member_tile(w, a.tiles);
+        const int g = uniform((int)(mt.t / a.tiles_per_group));
+        const uint32_t tile = mt.t - (uint32_t)g * a.tiles_per_group;
         const GroupArgs& G = a.grp[g];
-        const float* x = members[m];
-        float* y = acc + (size_t)m * a.member_stride;
+        const float* x = members[mt.m];
+        float* y = acc + (size_t)mt.m * a.member_stride;
 #pragma unroll 1
         for (int s = 0; s < TILE / (64 * VEC); ++s) {
             const uint32_t e = tile * TILE + (uint32_t)(s * 64 + lane) * VEC;      // (vector path: n is a multiple of 4, so e < n covers e + 3)
@@ -98,24 +99,16 @@ __global__ void __launch_bounds__(256) agg_kernel(const AggArgs a, const float* 
 // every refusal of skagg_update: nothing here touches the GPU
 bool valid(const skagg_desc* d) {
     if (!d || !d->members || ((uintptr_t)d->members & 7) || !d->acc || ((uintptr_t)d->acc & 3)) return false;
-    if (d->M < 1 || d->M > SKAGG_MAX_MEMBERS || (d->member_align != 4 && d->member_align != 16)) return false;
-    if (d->C < 1 || d->H < 1 || d->W < 1 || d->D < 1) return false;
-    const size_t lim = (size_t)1 << 30, HW = (size_t)d->H * (size_t)d->W;
-    if (HW > lim || (size_t)d->C > lim / HW || (size_t)d->D > lim / HW || d->member_stride < (size_t)d->D * HW) return false;
+    if (!grid_ok(d->M, SKAGG_MAX_MEMBERS, d->member_align, d->C, d->H, d->W, d->D, d->member_stride)) return false;
     if (d->n_ops < 1 || d->n_ops > SKAGG_MAX_OPS) return false;
-    int slots[2 * SKAGG_MAX_OPS], n_slots = 0;
+    Slots<2 * SKAGG_MAX_OPS> slots;
     for (int o = 0; o < d->n_ops; ++o) {
         const skagg_op& op = d->ops[o];
         if (op.kind < SKAGG_MAX || op.kind > SKAGG_COUNT_ABOVE) return false;
         if (op.phase < 0 || op.phase > (SKAGG_FIRST | SKAGG_LAST)) return false;
         if (op.in < 0 || op.in >= d->C || op.out < 0 || op.out >= d->D || op.when < -1 || op.when >= d->D) return false;
         if (op.when >= 0 && op.kind != SKAGG_MAX && op.kind != SKAGG_MIN) return false;
-        for (int s : {op.out, op.when}) {
-            if (s < 0) continue;
-            for (int k = 0; k < n_slots; ++k)
-                if (slots[k] == s) return false;
-            slots[n_slots++] = s;
-        }
+        if (!slots.claim(op.out, d->D) || !slots.claim(op.when, d->D)) return false;
     }
     return true;
 }
@@ -128,7 +121,7 @@ extern "C" int skagg_update(const skagg_desc* d, void* stream) {
     if (!valid(d)) return SKAGG_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t HW = (uint32_t)d->H * (uint32_t)d->W;
-    const bool vec = d->member_align == 16 && !((uintptr_t)d->acc & 15) && d->member_stride % 4 == 0 && HW % 4 == 0;
+    const bool vec = vec_ok(d->member_align, HW % 4 == 0, d->member_stride, d->acc);
     AggArgs a = {};
     a.M = d->M;
     a.n = HW;
@@ -153,9 +146,7 @@ extern "C" int skagg_update(const skagg_desc* d, void* stream) {
     }
     a.tiles_per_group = (HW + TILE - 1) / TILE;
     a.tiles = a.tiles_per_group * (uint32_t)a.n_groups;
-    // 256 CUs x 8 workgroups of four waves at the most; a wave walks the (member, tile) pairs with the grid's stride
-    const size_t groups = ((size_t)d->M * a.tiles + 3) / 4;
-    const unsigned blocks = (unsigned)(groups < 2048 ? groups : 2048);
+    const unsigned blocks = blocks_for(d->M, a.tiles);
     if (vec)
         hipLaunchKernelGGL(agg_kernel<4>, dim3(blocks), dim3(256), 0, s, a, d->members, d->acc);
     else

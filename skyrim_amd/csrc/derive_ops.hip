@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "../../include/skyrim_derive.h"
 #include "fields.h"
+#include "program.h"
 
 #pragma clang fp contract(off)
 
@@ -32,6 +33,7 @@ struct DeriveArgs {
 };
 
 using namespace skfields;
+using namespace skprogram;
 
 __device__ __forceinline__ float speed(float u, float v) {
     const float uu = u * u, vv = v * v;
@@ -140,18 +142,17 @@ __global__ void __launch_bounds__(256) derive_kernel(const DeriveArgs a, const f
     const int lane = threadIdx.x & 63;
     const uint32_t total = (uint32_t)a.M * a.tiles, nw = gridDim.x * 4u;
     for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += nw) {
-        const int m = uniform((int)(w / a.tiles));
-        const uint32_t t = (uint32_t)uniform((int)(w - (uint32_t)m * a.tiles));
+        const MemberTile mt = member_tile(w, a.tiles);
         int o = 0;
-        for (int k = 1; k < a.n_ops; ++k) o += t >= a.op[k].tile0 ? 1 : 0;
+        for (int k = 1; k < a.n_ops; ++k) o += mt.t >= a.op[k].tile0 ? 1 : 0;
         o = uniform(o);
         const OpArgs& op = a.op[o];
-        const float* x = members[m];
-        float* y = out + (size_t)m * a.member_stride;
+        const float* x = members[mt.m];
+        float* y = out + (size_t)mt.m * a.member_stride;
         if (op.kind == SKDERIVE_VORTDIV)
-            vortdiv_tile<VEC>(a, op, x, y, rowc, t - op.tile0, lane);
+            vortdiv_tile<VEC>(a, op, x, y, rowc, mt.t - op.tile0, lane);
         else
-            pointwise_tile<VEC>(a, op, x, y, t - op.tile0, lane);
+            pointwise_tile<VEC>(a, op, x, y, mt.t - op.tile0, lane);
     }
 }
 
@@ -183,19 +184,14 @@ __global__ void __launch_bounds__(64) derive_pole_kernel(const DeriveArgs a, con
     }
 }
 
-bool channel_ok(int ch, int C) { return ch >= 0 && ch < C; }
-
 int results_of(int kind) { return kind == SKDERIVE_COLUMN ? 4 : (kind == SKDERIVE_VORTDIV ? 2 : 1); }
 
 // every refusal of skderive_run: nothing here touches the GPU
 bool valid(const skderive_desc* d) {
     if (!d || !d->members || !d->out || ((uintptr_t)d->out & 3)) return false;
-    if (d->M < 1 || d->M > SKDERIVE_MAX_MEMBERS || (d->member_align != 4 && d->member_align != 16)) return false;
-    if (d->C < 1 || d->H < 3 || d->W < 4 || d->D < 1) return false;
-    const size_t lim = (size_t)1 << 30, HW = (size_t)d->H * (size_t)d->W;
-    if (HW > lim || (size_t)d->C > lim / HW || (size_t)d->D > lim / HW || d->member_stride < (size_t)d->D * HW) return false;
+    if (!grid_ok(d->M, SKDERIVE_MAX_MEMBERS, d->member_align, d->C, d->H, d->W, d->D, d->member_stride, 3, 4)) return false;
     if (d->n_ops < 1 || d->n_ops > SKDERIVE_MAX_OPS) return false;
-    int slots[4 * SKDERIVE_MAX_OPS], n_slots = 0;
+    Slots<4 * SKDERIVE_MAX_OPS> slots;
     bool vortdiv = false;
     for (int o = 0; o < d->n_ops; ++o) {
         const skderive_op& op = d->ops[o];
@@ -210,13 +206,8 @@ bool valid(const skderive_desc* d) {
         vortdiv = vortdiv || op.kind == SKDERIVE_VORTDIV;
         bool any = false;
         for (int r = 0; r < results_of(op.kind); ++r) {
-            const int s = op.out[r];
-            if (s < -1 || s >= d->D) return false;
-            if (s < 0) continue;
-            for (int k = 0; k < n_slots; ++k)
-                if (slots[k] == s) return false;
-            slots[n_slots++] = s;
-            any = true;
+            if (!slots.claim(op.out[r], d->D)) return false;
+            any = any || op.out[r] >= 0;
         }
         if (!any) return false;
     }
@@ -235,7 +226,7 @@ extern "C" int skderive_abi_version(void) { return SKDERIVE_ABI_VERSION; }
 extern "C" int skderive_run(const skderive_desc* d, void* stream) {
     if (!valid(d)) return SKDERIVE_E_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = d->member_align == 16 && !((uintptr_t)d->out & 15) && d->member_stride % 4 == 0 && d->W % 4 == 0;
+    const bool vec = vec_ok(d->member_align, d->W % 4 == 0, d->member_stride, d->out);
     const uint32_t HW = (uint32_t)d->H * (uint32_t)d->W;
     const uint32_t chunks = (uint32_t)d->W / (vec ? 4u : 1u);
     DeriveArgs a = {};
@@ -270,9 +261,7 @@ extern "C" int skderive_run(const skderive_desc* d, void* stream) {
         }
         a.n_ops = n;
         a.tiles = tiles;
-        // 256 CUs x 8 workgroups of four waves at the most; a wave walks the (member, tile) pairs with the grid's stride
-        const size_t groups = ((size_t)d->M * tiles + 3) / 4;
-        const unsigned blocks = (unsigned)(groups < 2048 ? groups : 2048);
+        const unsigned blocks = blocks_for(d->M, tiles);
         if (vec)
             hipLaunchKernelGGL(derive_kernel<4>, dim3(blocks), dim3(256), 0, s, a, d->members, d->rowc, d->out);
         else

@@ -1,5 +1,6 @@
 // What the product kernels (score, event, track, derive, thermo, regrid, agg, point, gram, breed, spec, object) share on the device: how a lane reads and
-// writes the points of a member state, and the wave reductions.  Everything is __device__ __forceinline__ and leaves no call behind.
+// writes the points of a member state, the wave reductions, and the walk of the (member, tile) kernels (derive, thermo, vert, agg):
+// `member_tile` gives the pair of a wave index.  Everything is __device__ __forceinline__ and leaves no call behind.
 // (ens_ops.hip is not among them: its load goes through a generic pointer.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -69,6 +70,13 @@ __device__ __forceinline__ void store(float* base, uint32_t elem, const Pts<VEC>
 
 // a value the compiler is told is the same in every lane: it goes to a scalar register
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the (member, tile) pair of the wave index w, when every member has `tiles` tiles; both are the same in every lane
+struct MemberTile { int m; uint32_t t; };
+__device__ __forceinline__ MemberTile member_tile(uint32_t w, uint32_t tiles) {
+    const int m = uniform((int)(w / tiles));
+    return {m, (uint32_t)uniform((int)(w - (uint32_t)m * tiles))};
+}
 
 // butterflies over the 64 lanes: every lane ends with the same bits
 template <typename T>

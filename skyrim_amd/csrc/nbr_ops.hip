@@ -6,6 +6,7 @@
 #include <cstdint>
 #include "../../include/skyrim_nbr.h"
 #include "fields.h"
+#include "program.h"
 
 #pragma clang fp contract(off)
 
@@ -263,23 +264,20 @@ __global__ void __launch_bounds__(THREADS) nbr_kernel(const NbrArgs a, const flo
 bool valid(const sknbr_desc* d) {
     if (!d || !d->members || ((uintptr_t)d->members & 7) || !d->out || ((uintptr_t)d->out & 3)) return false;
     if (!d->weights || ((uintptr_t)d->weights & 7)) return false;
-    if (d->M < 1 || d->M > SKNBR_MAX_MEMBERS || (d->member_align != 4 && d->member_align != 16)) return false;
-    if (d->C < 1 || d->H < 1 || d->W < 1 || d->D < 1 || d->W > SKNBR_MAX_W) return false;
-    const size_t lim = (size_t)1 << 30, HW = (size_t)d->H * (size_t)d->W;
-    if (HW > lim || (size_t)d->C > lim / HW || (size_t)d->D > lim / HW || d->member_stride < (size_t)d->D * HW) return false;
+    if (!skprogram::grid_ok(d->M, SKNBR_MAX_MEMBERS, d->member_align, d->C, d->H, d->W, d->D, d->member_stride) || d->W > SKNBR_MAX_W) return false;
     if (d->n_radii < 1 || d->n_radii > SKNBR_MAX_RADII) return false;
     for (int r = 0; r < d->n_radii; ++r) {
         const sknbr_radius& R = d->radii[r];
         if (R.reach < 0 || R.reach > SKNBR_MAX_REACH || !R.half || ((uintptr_t)R.half & 3)) return false;
     }
     if (d->n_ops < 1 || d->n_ops > SKNBR_MAX_OPS) return false;
+    skprogram::Slots<SKNBR_MAX_OPS> slots;
     for (int o = 0; o < d->n_ops; ++o) {
         const sknbr_op& op = d->ops[o];
         if (op.kind < SKNBR_MAX || op.kind > SKNBR_FRAC_ABOVE) return false;
         if (op.in < 0 || op.in >= d->C || op.out < 0 || op.out >= d->D || op.radius < 0 || op.radius >= d->n_radii) return false;
         if (op.kind == SKNBR_FRAC_ABOVE && op.thr != op.thr) return false;
-        for (int p = 0; p < o; ++p)
-            if (d->ops[p].out == op.out) return false;
+        if (!slots.claim(op.out, d->D)) return false;
     }
     // one workgroup per (member, op, centre row): what a grid holds
     if ((size_t)d->M * (size_t)d->n_ops * (size_t)d->H > 0x7fffffffu) return false;

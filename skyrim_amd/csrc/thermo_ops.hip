@@ -6,6 +6,7 @@
 #include <cstdint>
 #include "../../include/skyrim_thermo.h"
 #include "fields.h"
+#include "program.h"
 #include "thermo_math.h"
 
 #pragma clang fp contract(off)
@@ -41,6 +42,7 @@ struct ThermoArgs {
 };
 
 using namespace skfields;
+using namespace skprogram;
 using namespace skthermo_math;
 
 constexpr float EPS = 0.622f, ONE_M_EPS = 0.378f, KAPPA = 0.2854f, RD = 287.04f, T0C = 273.15f, E_MIN = 1e-10f;
@@ -297,37 +299,30 @@ __global__ void __launch_bounds__(256) thermo_kernel(const ThermoArgs a, const f
     const int lane = threadIdx.x & 63;
     const uint32_t total = (uint32_t)a.M * a.tiles, nw = gridDim.x * 4u;
     for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += nw) {
-        const int m = uniform((int)(w / a.tiles));
-        const uint32_t t = (uint32_t)uniform((int)(w - (uint32_t)m * a.tiles));
+        const MemberTile mt = member_tile(w, a.tiles);
         int o = 0;
-        for (int k = 1; k < a.n_ops; ++k) o += t >= a.op[k].tile0 ? 1 : 0;
+        for (int k = 1; k < a.n_ops; ++k) o += mt.t >= a.op[k].tile0 ? 1 : 0;
         o = uniform(o);
         const OpArgs& op = a.op[o];
-        const float* x = members[m];
-        float* y = out + (size_t)m * a.member_stride;
+        const float* x = members[mt.m];
+        float* y = out + (size_t)mt.m * a.member_stride;
         if (op.kind == SKTHERMO_PARCEL)
-            parcel_tile(a, op, x, zs, y, t - op.tile0, lane);
+            parcel_tile(a, op, x, zs, y, mt.t - op.tile0, lane);
         else
-            pointwise_tile<VEC>(a, op, x, zs, y, t - op.tile0, lane);
+            pointwise_tile<VEC>(a, op, x, zs, y, mt.t - op.tile0, lane);
     }
 }
 
-bool channel_ok(int ch, int C) { return ch >= 0 && ch < C; }
-
 int results_of(int kind) { return kind == SKTHERMO_MOIST ? 4 : (kind == SKTHERMO_INDEX ? 2 : (kind == SKTHERMO_FREEZE ? 1 : 3)); }
-
-bool pressure_ok(float p) { return finite(p) && p > 0.f && p <= 2000.f && p >= 1e-3f; }
 
 // every refusal of skthermo_run: nothing here touches the GPU
 bool valid(const skthermo_desc* d) {
     if (!d || !d->members || !d->out || ((uintptr_t)d->out & 3) || ((uintptr_t)d->zs & 3)) return false;
-    if (d->M < 1 || d->M > SKTHERMO_MAX_MEMBERS || (d->member_align != 4 && d->member_align != 16)) return false;
-    if (d->C < 1 || d->H < 1 || d->W < 1 || d->D < 1) return false;
-    const size_t lim = (size_t)1 << 30, HW = (size_t)d->H * (size_t)d->W;
-    if (HW > lim || (size_t)d->C > lim / HW || (size_t)d->D > lim / HW || d->member_stride < (size_t)d->D * HW) return false;
+    if (!grid_ok(d->M, SKTHERMO_MAX_MEMBERS, d->member_align, d->C, d->H, d->W, d->D, d->member_stride)) return false;
     if (d->n_ops < 1 || d->n_ops > SKTHERMO_MAX_OPS) return false;
+    const size_t HW = (size_t)d->H * (size_t)d->W;
     if ((size_t)d->M * (size_t)d->n_ops * (HW / PTILE + 1) > ((size_t)1 << 31)) return false;      // (member, tile) pairs are counted in 32 bits
-    int slots[4 * SKTHERMO_MAX_OPS], n_slots = 0;
+    Slots<4 * SKTHERMO_MAX_OPS> slots;
     for (int o = 0; o < d->n_ops; ++o) {
         const skthermo_op& op = d->ops[o];
         if (op.kind < SKTHERMO_MOIST || op.kind > SKTHERMO_PARCEL) return false;
@@ -360,13 +355,8 @@ bool valid(const skthermo_desc* d) {
         }
         bool any = false;
         for (int r = 0; r < results_of(op.kind); ++r) {
-            const int s = op.out[r];
-            if (s < -1 || s >= d->D) return false;
-            if (s < 0) continue;
-            for (int k = 0; k < n_slots; ++k)
-                if (slots[k] == s) return false;
-            slots[n_slots++] = s;
-            any = true;
+            if (!slots.claim(op.out[r], d->D)) return false;
+            any = any || op.out[r] >= 0;
         }
         if (!any) return false;
     }
@@ -411,7 +401,7 @@ extern "C" int skthermo_run(const skthermo_desc* d, void* stream) {
     if (!valid(d)) return SKTHERMO_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t HW = (uint32_t)d->H * (uint32_t)d->W;
-    const bool vec = d->member_align == 16 && !((uintptr_t)d->out & 15) && !((uintptr_t)d->zs & 15) && d->member_stride % 4 == 0 && HW % 4 == 0;
+    const bool vec = vec_ok(d->member_align, HW % 4 == 0, d->member_stride, d->out, d->zs);
     static_assert(sizeof(ThermoArgs) <= 4096, "the launch arguments fit the kernel-argument segment");
     ThermoArgs a = {};
     a.M = d->M; a.H = d->H; a.W = d->W;
@@ -454,9 +444,7 @@ extern "C" int skthermo_run(const skthermo_desc* d, void* stream) {
         }
         a.n_ops = n;
         a.tiles = tiles;
-        // 256 CUs x 8 workgroups of four waves at the most; a wave walks the (member, tile) pairs with the grid's stride
-        const size_t groups = ((size_t)d->M * tiles + 3) / 4;
-        const unsigned blocks = (unsigned)(groups < 2048 ? groups : 2048);
+        const unsigned blocks = blocks_for(d->M, tiles);
         if (vec)
             hipLaunchKernelGGL(thermo_kernel<4>, dim3(blocks), dim3(256), 0, s, a, d->members, d->zs, d->out);
         else

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include "../../include/skyrim_vert.h"
 #include "fields.h"
+#include "program.h"
 #include "thermo_math.h"
 
 #pragma clang fp contract(off)
@@ -41,6 +42,7 @@ struct VertArgs {
 };
 
 using namespace skfields;
+using namespace skprogram;
 using namespace skthermo_math;
 
 constexpr float KAPPA = 0.2854f;
@@ -278,30 +280,23 @@ __global__ void __launch_bounds__(256) vert_kernel(const VertArgs a, const float
     const int lane = threadIdx.x & 63;
     const uint32_t total = (uint32_t)a.M * a.tiles, nw = gridDim.x * 4u;
     for (uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6); w < total; w += nw) {
-        const int m = uniform((int)(w / a.tiles));
-        const uint32_t t = (uint32_t)uniform((int)(w - (uint32_t)m * a.tiles));
+        const MemberTile mt = member_tile(w, a.tiles);
         int o = 0;
-        for (int k = 1; k < a.n_ops; ++k) o += t >= a.op[k].tile0 ? 1 : 0;
+        for (int k = 1; k < a.n_ops; ++k) o += mt.t >= a.op[k].tile0 ? 1 : 0;
         o = uniform(o);
         const OpArgs& op = a.op[o];
-        vert_tile<VEC>(a, op, members[m], zs, out + (size_t)m * a.member_stride, t - op.tile0, lane);
+        vert_tile<VEC>(a, op, members[mt.m], zs, out + (size_t)mt.m * a.member_stride, mt.t - op.tile0, lane);
     }
 }
-
-bool channel_ok(int ch, int C) { return ch >= 0 && ch < C; }
-
-bool pressure_ok(float p) { return finite(p) && p > 0.f && p <= 2000.f && p >= 1e-3f; }
 
 // every refusal of skvert_run: nothing here touches the GPU
 bool valid(const skvert_desc* d) {
     if (!d || !d->members || !d->out || ((uintptr_t)d->out & 3) || ((uintptr_t)d->zs & 3)) return false;
-    if (d->M < 1 || d->M > SKVERT_MAX_MEMBERS || (d->member_align != 4 && d->member_align != 16)) return false;
-    if (d->C < 1 || d->H < 1 || d->W < 1 || d->D < 1) return false;
-    const size_t lim = (size_t)1 << 30, HW = (size_t)d->H * (size_t)d->W;
-    if (HW > lim || (size_t)d->C > lim / HW || (size_t)d->D > lim / HW || d->member_stride < (size_t)d->D * HW) return false;
+    if (!grid_ok(d->M, SKVERT_MAX_MEMBERS, d->member_align, d->C, d->H, d->W, d->D, d->member_stride)) return false;
     if (d->n_ops < 1 || d->n_ops > SKVERT_MAX_OPS) return false;
+    const size_t HW = (size_t)d->H * (size_t)d->W;
     if ((size_t)d->M * (size_t)d->n_ops * (HW / TILE + 1) > ((size_t)1 << 31)) return false;        // (member, tile) pairs are counted in 32 bits
-    int slots[SKVERT_MAX_OPS * SKVERT_MAX_FIELDS * SKVERT_MAX_TARGETS], n_slots = 0;
+    Slots<SKVERT_MAX_OPS * SKVERT_MAX_FIELDS * SKVERT_MAX_TARGETS> slots;
     for (int o = 0; o < d->n_ops; ++o) {
         const skvert_op& op = d->ops[o];
         if (op.coord < SKVERT_P || op.coord > SKVERT_T) return false;
@@ -336,13 +331,8 @@ bool valid(const skvert_desc* d) {
             }
             if ((!speed_kind || fd.node_a == SKVERT_NODE_NONE) && fd.node_b != SKVERT_NODE_NONE) return false;
             for (int t = 0; t < op.n_targets; ++t) {
-                const int sl = fd.out[t];
-                if (sl < -1 || sl >= d->D) return false;
-                if (sl < 0) continue;
-                for (int k = 0; k < n_slots; ++k)
-                    if (slots[k] == sl) return false;
-                slots[n_slots++] = sl;
-                any = true;
+                if (!slots.claim(fd.out[t], d->D)) return false;
+                any = any || fd.out[t] >= 0;
             }
         }
         if (!any) return false;
@@ -366,7 +356,7 @@ extern "C" int skvert_run(const skvert_desc* d, void* stream) {
     if (!valid(d)) return SKVERT_E_ARG;
     hipStream_t s = (hipStream_t)stream;
     const uint32_t HW = (uint32_t)d->H * (uint32_t)d->W;
-    const bool vec = d->member_align == 16 && !((uintptr_t)d->out & 15) && !((uintptr_t)d->zs & 15) && d->member_stride % 4 == 0 && HW % 4 == 0;
+    const bool vec = vec_ok(d->member_align, HW % 4 == 0, d->member_stride, d->out, d->zs);
     static_assert(sizeof(VertArgs) <= 4096, "the launch arguments fit the kernel-argument segment");
     static_assert(POOL_FIELDS >= SKVERT_MAX_FIELDS && POOL_LEVELS >= ML && POOL_CHAN >= (2 + 2 * SKVERT_MAX_FIELDS) * ML, "one op always fits a launch");
     const float LN1000 = sk_log(1000.f);
@@ -422,9 +412,7 @@ extern "C" int skvert_run(const skvert_desc* d, void* stream) {
         }
         a.n_ops = n;
         a.tiles = tiles;
-        // 256 CUs x 8 workgroups of four waves at the most; a wave walks the (member, tile) pairs with the grid's stride
-        const size_t groups = ((size_t)d->M * tiles + 3) / 4;
-        const unsigned blocks = (unsigned)(groups < 2048 ? groups : 2048);
+        const unsigned blocks = blocks_for(d->M, tiles);
         if (vec)
             hipLaunchKernelGGL(vert_kernel<4>, dim3(blocks), dim3(256), 0, s, a, d->members, d->zs, d->out);
         else

@@ -25,10 +25,9 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import native
+from . import native, program
 from .common import world_size as _world_size
 from .leads import open_saved, require_gpu, run_model
-from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS, MAX_LEVELS = 64, 16, 16                   # include/skyrim_derive.h SKDERIVE_MAX_*
 SPEED, DIFF, COLUMN, VORTDIV = 1, 2, 3, 4                       # SKDERIVE_SPEED ...
@@ -122,7 +121,7 @@ def decode(ints, floats) -> list:
 def describe(ops, M, C, H, W, D, member_stride, member_align=16, edges=(EDGE_POLE, EDGE_POLE)) -> DeriveDesc:
     """The descriptor of a program, its pointers still NULL."""
     d = DeriveDesc()
-    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride = M, member_align, C, H, W, D, member_stride
+    program.fill_head(d, M, C, H, W, D, member_stride, member_align)
     d.edge_first, d.edge_last = int(edges[0]), int(edges[1])
     ops = list(ops)
     d.n_ops = len(ops)
@@ -148,21 +147,13 @@ def run(members, table, ops, out, rowc=None, edges=(EDGE_POLE, EDGE_POLE)) -> No
     ``verify.score``, the contents of ``table`` are trusted to be the addresses of ``members``."""
     import torch
     ops = list(ops)
-    member_count(members, "derive_fields", MAX_MEMBERS)
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise ValueError(f"derive_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    M, dev, align = member_set(members, table, "derive_fields", MAX_MEMBERS)
-    C, H, W = members[0].shape
-    po = native.tensor_ptr(out, "derive_fields: out", torch.float32, dev)
-    if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
-        raise ValueError(f"derive_fields: out must be ({M}, D, {H}, {W})")
+    M, dev, align, C, H, W, D, po = program.bind("derive_fields", members, table, ops, out, "derive_fields: out", MAX_MEMBERS, MAX_OPS)
     for op in ops:
         if op.kind == COLUMN and (len(set(len(x) for x in op.inputs)) != 1 or len(op.weights) != len(op.inputs[0])
                                   or not 2 <= len(op.weights) <= MAX_LEVELS):
             raise ValueError(f"derive_fields: a COLUMN op has 2 to {MAX_LEVELS} levels, each with q, u, v and a weight")
         if len(op.outputs) != RESULTS.get(op.kind, 0):
             raise ValueError("derive_fields: an op has one slot per result (SPEED, DIFF: 1; VORTDIV: 2; COLUMN: 4)")
-    D = out.shape[1]
     d = describe(ops, M, C, H, W, D, D * H * W, align, edges)
     d.members, d.out = table.data_ptr(), po
     if any(op.kind == VORTDIV for op in ops):
@@ -170,8 +161,7 @@ def run(members, table, ops, out, rowc=None, edges=(EDGE_POLE, EDGE_POLE)) -> No
             raise ValueError(f"derive_fields: vorticity and divergence need rowc ({H}, 4)")
         d.rowc = native.tensor_ptr(rowc, "derive_fields: rowc", torch.float32, dev)
     lib = load_library()
-    with torch.cuda.device(dev):
-        native.check(lib.skderive_run(ctypes.byref(d), native.stream(dev)), "skderive_run", lib)
+    program.launch(lib, lib.skderive_run, d, dev)
 
 
 # ---- the row coefficients of vorticity and divergence ------------------------------------------------------------------------------------- #

@@ -1,7 +1,8 @@
 """The member set of the product libraries: M member states on one device plus the device table of their addresses.
 
-Every product binding (ensemble, verify, events, tracks, derived, thermo, regrid, aggregate, points, scenarios, spectra, breeding) takes
-``members`` and ``table = member_table(members)`` and validates them here, with its own name in front of every message.
+Every product binding (ensemble, verify, events, tracks, regrid, points, scenarios, spectra, breeding) takes ``members`` and
+``table = member_table(members)`` and validates them here, with its own name in front of every message.  The program-driven bindings
+(derived, thermo, vertical, aggregate, neighbourhood) do so through ``program.bind``, the prelude they share.
 """
 from __future__ import annotations
 

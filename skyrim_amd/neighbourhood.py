@@ -23,10 +23,9 @@ from dataclasses import dataclass, field, replace
 
 import numpy as np
 
-from . import native
+from . import native, program
 from .common import world_size as _world_size
 from .leads import open_saved, require_gpu, run_model
-from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS, MAX_RADII = 64, 16, 4                     # include/skyrim_nbr.h SKNBR_MAX_*
 MAX_W, MAX_REACH = 2048, 128                                    # SKNBR_MAX_W, SKNBR_MAX_REACH
@@ -108,7 +107,7 @@ def decode(ints, floats) -> list:
 def describe(ops, M, C, H, W, D, member_stride, reaches, member_align=16) -> NbrDesc:
     """The descriptor of a call, its pointers still NULL.  ``reaches``: the reach of each radius."""
     d = NbrDesc()
-    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride = M, member_align, C, H, W, D, member_stride
+    program.fill_head(d, M, C, H, W, D, member_stride, member_align)
     reaches = list(reaches)
     d.n_radii = len(reaches)
     for k, r in enumerate(reaches[:MAX_RADII]):
@@ -128,16 +127,10 @@ def run(members, table, ops, half, weights, out) -> None:
     ``table`` are trusted to be the addresses of ``members``."""
     import torch
     ops, half = list(ops), list(half)
-    member_count(members, "nbr_fields", MAX_MEMBERS)
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise ValueError(f"nbr_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
+    program.counts("nbr_fields", members, ops, MAX_MEMBERS, MAX_OPS)
     if not 1 <= len(half) <= MAX_RADII:
         raise ValueError(f"nbr_fields: {len(half)} radii; 1 to {MAX_RADII} are supported")
-    M, dev, align = member_set(members, table, "nbr_fields", MAX_MEMBERS)
-    C, H, W = members[0].shape
-    po = native.tensor_ptr(out, "nbr_fields: out", torch.float32, dev)
-    if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
-        raise ValueError(f"nbr_fields: out must be ({M}, D, {H}, {W})")
+    M, dev, align, C, H, W, D, po = program.bind("nbr_fields", members, table, ops, out, "nbr_fields: out", MAX_MEMBERS, MAX_OPS, counted=True)
     pw = native.tensor_ptr(weights, "nbr_fields: weights", torch.float64, dev)
     if tuple(weights.shape) != (H,):
         raise ValueError(f"nbr_fields: weights must be ({H},)")
@@ -147,14 +140,12 @@ def run(members, table, ops, half, weights, out) -> None:
         if t.dim() != 2 or t.shape[0] != H or t.shape[1] % 2 != 1:
             raise ValueError(f"nbr_fields: half[{k}] must be ({H}, 2 reach + 1)")
         reaches.append((t.shape[1] - 1) // 2)
-    D = out.shape[1]
     d = describe(ops, M, C, H, W, D, D * H * W, reaches, align)
     d.members, d.out, d.weights = table.data_ptr(), po, pw
     for k, p in enumerate(ph):
         d.radii[k].half = p
     lib = load_library()
-    with torch.cuda.device(dev):
-        native.check(lib.sknbr_run(ctypes.byref(d), native.stream(dev)), "sknbr_run", lib)
+    program.launch(lib, lib.sknbr_run, d, dev)
 
 
 # ---- the disc ---------------------------------------------------------------------------------------------------------------------------- #

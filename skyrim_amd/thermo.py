@@ -11,8 +11,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import native
-from .members import member_count, member_set
+from . import native, program
 
 MAX_MEMBERS, MAX_OPS, MAX_LEVELS = 64, 16, 16                   # include/skyrim_thermo.h SKTHERMO_MAX_*
 MOIST, INDEX, FREEZE, PARCEL = 1, 2, 3, 4                       # SKTHERMO_MOIST ...
@@ -134,7 +133,7 @@ def decode(ints, floats) -> list:
 def describe(ops, M, C, H, W, D, member_stride, member_align=16) -> ThermoDesc:
     """The descriptor of a program, its pointers still NULL."""
     d = ThermoDesc()
-    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride = M, member_align, C, H, W, D, member_stride
+    program.fill_head(d, M, C, H, W, D, member_stride, member_align)
     ops = list(ops)
     d.n_ops = len(ops)
     for k, op in enumerate(ops[:MAX_OPS]):
@@ -173,14 +172,7 @@ def run(members, table, ops, out, surface=None) -> None:
     the contents of ``table`` are trusted to be the addresses of ``members``."""
     import torch
     ops = list(ops)
-    member_count(members, "thermo_fields", MAX_MEMBERS)
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise ValueError(f"thermo_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    M, dev, align = member_set(members, table, "thermo_fields", MAX_MEMBERS)
-    C, H, W = members[0].shape
-    po = native.tensor_ptr(out, "thermo_fields: out", torch.float32, dev)
-    if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
-        raise ValueError(f"thermo_fields: out must be ({M}, D, {H}, {W})")
+    M, dev, align, C, H, W, D, po = program.bind("thermo_fields", members, table, ops, out, "thermo_fields: out", MAX_MEMBERS, MAX_OPS)
     for op in ops:
         if op.kind not in RESULTS:
             raise ValueError(f"thermo_fields: unknown op kind {op.kind}")
@@ -188,13 +180,9 @@ def run(members, table, ops, out, surface=None) -> None:
             raise ValueError(f"thermo_fields: {_SHAPES[op.kind]}")
         if len(op.outputs) != RESULTS[op.kind]:
             raise ValueError("thermo_fields: an op has one slot per result (MOIST: 4; INDEX: 2; FREEZE: 1; PARCEL: 3)")
-    D = out.shape[1]
     d = describe(ops, M, C, H, W, D, D * H * W, align)
     d.members, d.out = table.data_ptr(), po
     if surface is not None:
-        if tuple(surface.shape) != (H, W):
-            raise ValueError(f"thermo_fields: surface must be ({H}, {W})")
-        d.zs = native.tensor_ptr(surface, "thermo_fields: surface", torch.float32, dev)
+        d.zs = program.plane("thermo_fields", surface, "surface", (H, W), torch.float32, dev)
     lib = load_library()
-    with torch.cuda.device(dev):
-        native.check(lib.skthermo_run(ctypes.byref(d), native.stream(dev)), "skthermo_run", lib)
+    program.launch(lib, lib.skthermo_run, d, dev)

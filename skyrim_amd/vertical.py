@@ -11,9 +11,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import native
+from . import native, program
 from .thermo import sk_exp, sk_log
-from .members import member_count, member_set
 
 MAX_MEMBERS, MAX_OPS, MAX_LEVELS, MAX_TARGETS, MAX_FIELDS = 64, 16, 16, 4, 8      # include/skyrim_vert.h SKVERT_MAX_*
 P, Z, Z_AGL, THETA, T = 1, 2, 3, 4, 5                           # SKVERT_P ...: the coordinate
@@ -167,7 +166,7 @@ def describe(ops, M, C, H, W, D, member_stride, member_align=16) -> VertDesc:
     """The descriptor of a program, its pointers still NULL.  What does not fit the descriptor's arrays is cut; the counts say what was
     asked for, so the library refuses it."""
     d = VertDesc()
-    d.M, d.member_align, d.C, d.H, d.W, d.D, d.member_stride = M, member_align, C, H, W, D, member_stride
+    program.fill_head(d, M, C, H, W, D, member_stride, member_align)
     ops = list(ops)
     d.n_ops = len(ops)
     for k, op in enumerate(ops[:MAX_OPS]):
@@ -220,25 +219,14 @@ def run(members, table, ops, out, surface=None) -> None:
     ``table`` are trusted to be the addresses of ``members``."""
     import torch
     ops = list(ops)
-    member_count(members, "vert_fields", MAX_MEMBERS)
-    if not 1 <= len(ops) <= MAX_OPS:
-        raise ValueError(f"vert_fields: {len(ops)} ops; 1 to {MAX_OPS} are supported")
-    M, dev, align = member_set(members, table, "vert_fields", MAX_MEMBERS)
-    C, H, W = members[0].shape
-    po = native.tensor_ptr(out, "vert_fields: out", torch.float32, dev)
-    if out.dim() != 4 or out.shape[0] != M or tuple(out.shape[2:]) != (H, W):
-        raise ValueError(f"vert_fields: out must be ({M}, D, {H}, {W})")
+    M, dev, align, C, H, W, D, po = program.bind("vert_fields", members, table, ops, out, "vert_fields: out", MAX_MEMBERS, MAX_OPS)
     for op in ops:
         err = _shape_error(op, surface is not None)
         if err:
             raise ValueError(f"vert_fields: {err}")
-    D = out.shape[1]
     d = describe(ops, M, C, H, W, D, D * H * W, align)
     d.members, d.out = table.data_ptr(), po
     if surface is not None:
-        if tuple(surface.shape) != (H, W):
-            raise ValueError(f"vert_fields: surface must be ({H}, {W})")
-        d.zs = native.tensor_ptr(surface, "vert_fields: surface", torch.float32, dev)
+        d.zs = program.plane("vert_fields", surface, "surface", (H, W), torch.float32, dev)
     lib = load_library()
-    with torch.cuda.device(dev):
-        native.check(lib.skvert_run(ctypes.byref(d), native.stream(dev)), "skvert_run", lib)
+    program.launch(lib, lib.skvert_run, d, dev)

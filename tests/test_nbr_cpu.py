@@ -223,7 +223,7 @@ def test_build_entries_and_exports():
     for k, kind in enumerate(("MAX", "MIN", "MEAN", "FRAC_ABOVE"), 1):
         assert re.search(rf"#define SKNBR_{kind} {k}\b", text) and getattr(N, kind) == k
     make = (ROOT / "skyrim_amd/csrc/Makefile").read_text()
-    assert re.search(r"^\$\(LIB_NBR\): nbr_ops\.hip fields\.h \.\./\.\./include/skyrim_nbr\.h\n.*\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -ffp-contract=off -shared", make, re.M)
+    assert re.search(r"^\$\(LIB_NBR\): nbr_ops\.hip fields\.h \.\./\.\./include/skyrim_nbr\.h program\.h\n.*\n\t\$\(HIPCC\) \$\(CXXFLAGS\) -ffp-contract=off -shared", make, re.M)
     assert all("$(LIB_NBR)" in line for line in make.splitlines() if line.startswith("all:") or line.startswith("\trm -rf"))
     assert ",nbr," in make.splitlines()[0] and "event}" in make and ",nbr," in native.__doc__ and "event}" in native.__doc__
     assert "sknbr_abi_version() == 1" in (ROOT / "__graft_entry__.py").read_text()
