@@ -184,7 +184,7 @@ def test_recovery_channel_placement(rig, zero):
 
 
 # ---- blocks at window paddings 0, 1 and 3 ---------------------------------------------------------------------------------------------- #
-BEFORE = {(1, 0): "embed", (1, 1): "layer1.block0", (2, 0): "down", (2, 1): "layer2.block0"}
+BEFORE = R.BEFORE           # the tap in front of each tested block
 
 
 def check_block(e, grid, p64, taps, layer, i, conv=O.DEFAULT):

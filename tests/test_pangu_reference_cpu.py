@@ -1,8 +1,10 @@
 """The float64 reference of tests/test_pangu_kernels_gpu.py, checked on the CPU: it really runs in float64, the float32 oracle agrees
 with it to float32's own rounding, the stage helpers reproduce the oracle's taps, and the small grids have the paddings they were
-chosen for."""
+chosen for.  Likewise the helpers of tests/test_pangu_attention_kernels_gpu.py: the compact bias addresses every cell once, the window
+table is a permutation, the peaked parameters are peaked, and together the helpers rebuild the oracle's block."""
 import pytest
 import torch
+import torch.nn.functional as F
 
 import _pangu_reference as R
 from oracle import pangu_oracle as O
@@ -96,3 +98,133 @@ def test_locate_names_rows_and_padding():
     assert "touches a padded latitude" in R.locate("down", g, ((2 * 4 + 3) * 12 + 1) * 384)      # merged row 3 = fine rows 6, 7
     assert "(channel, lat, lon) = (68, 26, 95)" in R.locate("recover", g, 68 * 27 * 96 + 26 * 96 + 95)
     assert "partly cropped" in R.locate("recover", g, 26 * 96) and "is whole" in R.locate("recover", g, 23 * 96)
+
+
+# ---- the attention helpers of tests/test_pangu_attention_kernels_gpu.py ------------------------------------------------------------- #
+ATTN_GRIDS = [R.GRID["24x96"], R.GRID["33x96"], R.make_grid(49, 96), R.GRID["25x96-back"], R.make_grid(25, 864)]      # the grids of its tests C - E
+
+
+@pytest.mark.parametrize("rolled", [False, True], ids=["plain", "rolled"])
+@pytest.mark.parametrize("mask_value", [-100.0, -1000.0])
+@pytest.mark.parametrize("bias_index", ["qk", "kq"])
+@pytest.mark.parametrize("roll_sign", [-1, +1])
+@pytest.mark.parametrize("nH", [1, 2, 3])
+def test_compact_bias_addresses_every_cell_without_conflict(nH, roll_sign, bias_index, mask_value, rolled):
+    """The 144 x 144 pairs fill the 144 x 23 live cells of every (type, head), and pairs that share a cell agree on its value, mask
+    included: the shifted-window mask is a function of the table ROW.  Every table entry is distinct, so agreement is no accident."""
+    nZ, heads = 4, 2
+    types = nZ * nH
+    conv = O.Conventions(roll_sign=roll_sign, bias_index=bias_index, mask_value=mask_value)
+    n = 3312 * types * heads
+    table = ((torch.randperm(n, generator=torch.Generator().manual_seed(nH)).float() - n / 2) * (8.0 / n)).reshape(3312, types, heads)
+    got, unaddressed, conflicts = R.compact_bias(table, types, heads, nZ, nH, rolled, conv)
+    assert (unaddressed, conflicts) == (0, 0)
+    assert got.shape == (types, heads, 144, 24) and got.dtype == torch.float32 and not got[..., 23].any()
+    full = R.full_bias(table, types, heads, nZ, nH, rolled, conv)
+    # one pair spelt out by hand: query (z, h, w) = (1, 4, 2), key (0, 1, 9) -> row (1 + 0) 36 + (4 + 6), column 9 - 2 + 11
+    q, k = 72 + 4 * 12 + 2, 12 + 9
+    assert torch.equal(got[:, :, 46, 18], full[:, :, q, k])
+    entry = (1 + 0) * 23 * 36 + (4 + 6 * 1) * 23 + (2 - 9 + 11) if bias_index == "qk" else (0 + 2) * 23 * 36 + (1 + 6 * 4) * 23 + (9 - 2 + 11)
+    t = torch.arange(types)                 # h_q = 4, h_k = 1 lie across the latitude seam of the mixed window, z_q = 1, z_k = 0 across the level seam
+    masked = ((t % nH == (nH - 1 if roll_sign < 0 else 0)) | (t // nH == (nZ - 1 if roll_sign < 0 else 0))) & rolled
+    assert torch.equal(got[:, :, 46, 18], table[entry] + mask_value * masked[:, None].float())
+    assert rolled == bool((got < mask_value / 2).any())
+
+
+@pytest.mark.parametrize("grid", [*R.GRIDS, R.make_grid(49, 96)], ids=lambda g: g.id)
+def test_window_table_is_a_permutation_with_the_padding_marked(grid):
+    for pad in ("centre", "back"):
+        for roll_sign in (-1, +1):
+            for surface in ("first", "last"):
+                conv = O.Conventions(pad=pad, roll_sign=roll_sign, surface=surface)
+                for layer in (1, 2):
+                    Z, H, W = O.Geometry(grid.n_lat, grid.n_lon, pad).res(layer)
+                    Hp, top, _ = O._centre_pad(H, 6, pad)
+                    for rolled in (False, True):
+                        t = R.window_table(grid, layer, rolled, conv)
+                        assert t.numel() == Z * Hp * W and int((t < 0).sum()) == Z * (Hp - H) * W and int(t.min()) >= -1
+                        assert torch.equal(t[t >= 0].sort().values, torch.arange(Z * H * W))
+                    if surface == "first":       # unrolled: token 0 sits in window 0 at (z, h, w) = (0, top, 0)
+                        assert top < 6 and int(R.window_table(grid, layer, False, conv)[top * 12]) == 0
+
+
+def test_window_table_spot_values():
+    """Written out by hand on 25 x 96, layer 1 (Z, H, W = 8, 7, 24; Hp = 12): one value per pad mode, roll direction and surface setting."""
+    g = R.GRID["25x96"]
+    tok = lambda z, h, w: (z * 7 + h) * 24 + w
+    centre, back = O.Conventions(pad="centre"), O.Conventions(pad="back")
+    assert int(R.window_table(g, 1, False, centre)[2 * 12]) == 0 and int(R.window_table(g, 1, False, centre)[0]) == -1      # top = 2
+    assert int(R.window_table(g, 1, False, back)[0]) == 0 and int(R.window_table(g, 1, False, back)[2 * 144 + 12]) == -1   # window (0, 1, 0), h = 1: padded row 7
+    # rolled by -(1, 3, 6): window row 0 holds padded position (1, 3, 6) -> latitude row 3 - top
+    assert int(R.window_table(g, 1, True, centre)[0]) == tok(1, 1, 6) and int(R.window_table(g, 1, True, back)[0]) == tok(1, 3, 6)
+    # rolled by +(1, 3, 6): window row 0 holds padded position (7, 9, 18) -> a padded latitude on both pads (9 - 2 = 7, 9 - 0 = 9 >= 7) ...
+    plus = O.Conventions(pad="centre", roll_sign=+1)
+    assert int(R.window_table(g, 1, True, plus)[0]) == -1
+    assert int(R.window_table(g, 1, True, plus)[(0 * 6 + 5) * 12 + 7]) == tok(7, 0, 1)          # ... (0, 5, 7) holds (7, 2, 1): latitude row 0
+    # surface last: logical level 0 is storage level 1, logical level 7 is storage level 0
+    last = O.Conventions(pad="centre", surface="last")
+    t = R.window_table(g, 1, False, last)
+    assert int(t[2 * 12]) == tok(1, 0, 0) and int(t[3 * 2 * 2 * 144 + 72 + 2 * 12]) == tok(0, 0, 0)      # window (3, 0, 0), z = 1 = logical 7
+    assert R.locate_window_row(3 * 2 * 2 * 144 + 144 + 72 + 2 * 12 + 5, 2, 2) == (6, 1, 1, 2, 5)
+
+
+def _peaked_block(grid, layer, i, conv, fp16):
+    """The four helpers on one block of the peaked parameters: (operands, compact bias, o, p, D); ``fp16``: operands rounded as the device holds them."""
+    pp, pp64 = R.peaked_params(grid, conv)
+    extra = tuple((f, getattr(conv, f)) for f in ("roll_sign", "mask_value", "bias_index") if getattr(conv, f) != getattr(O.DEFAULT, f))
+    taps, _ = R.reference(grid.n_lat, grid.n_lon, grid.pad, conventions=extra)
+    heads, rolled = O.HEADS[layer - 1], i % 2 == 1
+    nZ, nH, nW = R.window_shape(grid, layer, conv)
+    ops = R.qkv_reference(O._block_params(pp64, layer, i), taps[R.BEFORE[layer, i]].float(), R.window_table(grid, layer, rolled, conv), heads, conv)
+    table = O._block_params(pp if fp16 else pp64, layer, i)["attn.bias_table"]
+    cb, unaddressed, conflicts = R.compact_bias(table, nZ * nH, heads, nZ, nH, rolled, conv)
+    assert (unaddressed, conflicts) == (0, 0)
+    q, k, vt = (ops[n][0].half() if fp16 else ops[n][0] for n in ("q", "k", "vt"))
+    return ops, cb, R.attention_reference(q, k, vt, cb.half() if fp16 else cb, nZ * nH, heads, nW)
+
+
+@pytest.mark.parametrize("layer,i", R.PEAKED_BLOCKS)
+@pytest.mark.parametrize("grid", ATTN_GRIDS, ids=lambda g: g.id)
+def test_peaked_params_make_the_softmax_peaked_but_not_degenerate(grid, layer, i):
+    """The condition the GPU tests rely on, on the reference alone: the weights are far from 1 / 144 (a misplaced bias entry moves them), some rows
+    are dominated by one key, most are not, and nothing leaves fp16's range."""
+    ops, cb, (o, p, D) = _peaked_block(grid, layer, i, R.conventions_of(grid), fp16=True)
+    neff, pmax = 1 / (p * p).sum(-1), p.amax(-1)
+    big = max(ops[n][0].abs().max().item() for n in ("q", "k", "vt"))
+    print(f"{grid.id} layer{layer}.block{i}: effective keys median {neff.median():.1f} (min {neff.min():.2f}, max {neff.max():.1f}); largest weight median {pmax.median():.3f}, "
+          f"above 0.5 in {100 * (pmax > 0.5).double().mean():.2f} % of rows, max {pmax.max():.4f}; largest |q|, |k|, |v| {big:.1f}; bias std {cb[..., :23][cb[..., :23] > -50].std():.2f}")
+    assert 5 <= neff.median().item() <= 60
+    assert (pmax > 0.5).double().mean().item() >= 0.01
+    assert big < 1000
+
+
+@pytest.mark.parametrize("gid,layer,i,conv", [("33x96", 1, 1, {}), ("33x96", 2, 0, {}), ("24x96", 2, 1, dict(roll_sign=+1, bias_index="kq", mask_value=-1000.0)),
+                                              ("25x96-back", 1, 1, dict(bias_index="kq"))], ids=lambda v: str(v))
+def test_attention_helpers_rebuild_the_oracles_block(gid, layer, i, conv):
+    """window_table + qkv_reference + compact_bias + attention_reference, then the oracle's remaining lines (proj, scatter back through the table,
+    the two LayerNorm residuals), give ``earth_block`` to float64 rounding on the peaked parameters: the helpers' layouts are the oracle's."""
+    grid = R.GRID[gid]
+    conv = R.conventions_of(grid, **conv)
+    ops, cb, (o, p, D) = _peaked_block(grid, layer, i, conv, fp16=False)
+    pb = O._block_params(R.peaked_params(grid, conv)[1], layer, i)
+    extra = tuple((f, getattr(conv, f)) for f in ("roll_sign", "mask_value", "bias_index") if getattr(conv, f) != getattr(O.DEFAULT, f))
+    xin = R.reference(grid.n_lat, grid.n_lon, grid.pad, conventions=extra)[0][R.BEFORE[layer, i]].float().double()
+    want = O.earth_block(pb, xin, O.Geometry(grid.n_lat, grid.n_lon, grid.pad).res(layer), O.HEADS[layer - 1], i % 2 == 1, None, conv)
+    tab = R.window_table(grid, layer, i % 2 == 1, conv)
+    C = xin.shape[1]
+    a = torch.empty_like(xin)
+    a[tab[tab >= 0]] = F.linear(o, pb["attn.proj.weight"], pb["attn.proj.bias"])[tab >= 0]
+    x = xin + F.layer_norm(a, (C,), pb["norm1.weight"], pb["norm1.bias"], O.LN_EPS)
+    h = F.linear(F.gelu(F.linear(x, pb["mlp.fc1.weight"], pb["mlp.fc1.bias"])), pb["mlp.fc2.weight"], pb["mlp.fc2.bias"])
+    got = x + F.layer_norm(h, (C,), pb["norm2.weight"], pb["norm2.bias"], O.LN_EPS)
+    err = R.max_rel(got, want)[0]
+    print(f"{gid} layer{layer}.block{i} {conv}: helpers against earth_block {err:.1e}")
+    assert err < 1e-12
+    # p and D are what they are said to be: rows of p sum to 1; D of one row by hand; D = 0 where a row has one key only would need p = 1
+    assert torch.allclose(p.sum(-1), torch.ones(()).double(), rtol=0, atol=1e-13)
+    win, head, qi = 3, 2, 77
+    v = ops["vt"][0][win, head].T                                                   # [key][dim]
+    by_hand = (p[win, head, qi][:, None] * (v - o[win * 144 + qi, head * 32:head * 32 + 32][None]).abs()).sum(0)
+    assert torch.allclose(D[win * 144 + qi, head * 32:head * 32 + 32], by_hand, rtol=1e-12, atol=0)
+    assert "head 2 (dim 5), query 77 -> (z_q, h_q, w_q) = (1, 0, 5)" in R.locate_attention_row(win * 144 + qi, 2 * 32 + 5, 2)
+    assert "row 46 -> (z_q, z_k, h_q, h_k) = (1, 0, 4, 1), column 18" in R.locate_bias_cell((5 * 144 + 46) * 24 + 18, 6)
