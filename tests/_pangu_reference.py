@@ -1,6 +1,7 @@
 """Float64 route through the Pangu oracle, the small grids whose paddings the 49 x 192 toy never has, the error norms of the
 stage tests (tests/test_pangu_kernels_gpu.py, tests/test_pangu_reference_cpu.py), and the operands of the attention tests
-(tests/test_pangu_attention_kernels_gpu.py): window table, compact bias, Q / K / V^T, softmax core, parameters with a peaked softmax.
+(tests/test_pangu_attention_kernels_gpu.py): window table, compact bias, Q / K / V^T, softmax core, parameters with a peaked softmax; and
+everything of a block after the attention, per term form, with its bar and edge parameters (tests/test_pangu_block_kernels_gpu.py).
 
 oracle/pangu_oracle.py takes its dtype from its input, so the reference here is the oracle itself on double inputs; this file restates no
 kernel.  What it adds is glue the oracle keeps inside ``forward``: the normalisation in front of PatchEmbedding, the concat and the
@@ -322,3 +323,176 @@ def _peaked_params(grid, conv):
         out[pre + "attn.qkv.weight"][:C] *= gain
         out[pre + "attn.qkv.bias"][:C] *= gain
     return out, to64(out)
+
+
+# ---- everything of a block after the attention (tests/test_pangu_block_kernels_gpu.py) ------------------------------------------------ #
+# csrc/fused_block.hip's header gives the operation and, per term form, where an operand is rounded on its way into a GEMM; nothing of the
+# kernels is restated: Linear, LayerNorm and erf-GELU are torch's own, in the dtype of ``x``.
+FORMS = ("three", "two", "one")
+GELU_CLAMP = 5.9396969619669995                 # tools/gelu_fit.py U = 4.2 sqrt(2)
+# tools/gelu_fit.py c1 .. c8 as csrc/common.h gelu_erf2 holds them (float32 values; c0 = 0)
+GELU_COEFFS = (-1.151117682e+00, -4.591012597e-01, -5.282834917e-02, 7.545167115e-03, -4.982745158e-04, -4.273382365e-05, 1.091520153e-05, -6.177511978e-07)
+
+
+def gelu_poly64(x):
+    """The project's degree-8 fit of log2 erfc evaluated in float64: E = 2^Q(min(|x|, U)), GELU = x / 2 (2 - E) for x > 0 and x / 2 E otherwise."""
+    x = x.double()
+    a = x.abs().clamp(max=GELU_CLAMP)
+    c = torch.tensor(GELU_COEFFS, dtype=torch.float32).double()
+    p = torch.zeros_like(a)
+    for k in range(len(GELU_COEFFS) - 1, -1, -1):
+        p = (p + c[k]) * a
+    e = torch.exp2(p)
+    return 0.5 * x * torch.where(x > 0, 2 - e, e)
+
+
+def form_of(plan, layer):
+    """The term form the block kernels of ``layer`` (1 .. 4) run under term plan ``plan`` (skyrim_amd/pangu/engine.py: bits 0-3 two terms, bits 8-11 one)."""
+    return "one" if (plan >> (8 + layer - 1)) & 1 else "two" if (plan >> (layer - 1)) & 1 else "three"
+
+
+def inverse_window_table(table, ntok):
+    """Stream token -> window row: the left inverse of ``window_table`` on every real token (each token sits in exactly one window row)."""
+    rows = torch.nonzero(table >= 0).flatten()
+    inv = torch.full((ntok,), -1, dtype=torch.long)
+    inv[table[rows]] = rows
+    return inv
+
+
+def ao_tokens(planes, table, ntok, C, one):
+    """The device's attention output in stream-token order, float64: ``planes`` = (hi, lo) flat planes of the blocked ``ao`` buffer (fp16 or
+    bf16), un-blocked as pangu/calibration.py does and gathered through the inverse of ``table``.  hi + lo is exact in float64; ``one``: the
+    hi plane alone (a one-term layer neither writes nor reads the lo plane, it holds stale bytes)."""
+    from skyrim_amd.pangu.calibration import _unblock
+    hi, lo = planes
+    flat = hi.double() if one else hi.double() + lo.double()
+    return _unblock(flat, table.numel(), C)[inverse_window_table(table, ntok)]
+
+
+def stream_planes(x, bf16=False):
+    """The float32 stream as the engine holds it after ``to_planes``: hi = x rounded to fp16 (bf16), lo = (x - hi) rounded; hi + lo in float64."""
+    t = torch.bfloat16 if bf16 else torch.float16
+    hi = x.float().to(t)
+    lo = (x.float() - hi.float()).to(t)
+    return hi.double() + lo.double()
+
+
+def post_attention_reference(pb, x, ao_tokens, form, eps=1e-5, gelu=F.gelu, parts=False):
+    """x_mid = x + LN1(ao Wp^T + bp);  out = x_mid + LN2(fc2(GELU(fc1(x_mid)))) in the dtype of ``x`` (float64: the reference; float32: the
+    yardstick, same rounding points).  ``pb``: the block's parameters in any float type.  ``form``: "three" -- weights as they are; "two" --
+    proj / fc1 / fc2 weights rounded to ONE fp16 plane (with nearest rounding and no calibration those ARE the engine's weights); "one" -- also
+    the GEMM operands x_mid and the hidden activation rounded to fp16 where they enter a GEMM (``ao_tokens`` is then the hi plane already); the
+    residual path keeps x_mid unrounded.  ``parts``: also the intermediates, as a dict."""
+    assert form in FORMS
+    dt = x.dtype
+    p = {k: v.to(dt) for k, v in pb.items() if v.is_floating_point()}
+    w = (lambda k: p[k]) if form == "three" else (lambda k: pb[k].half().to(dt))
+    rnd = (lambda t: t.half().to(dt)) if form == "one" else (lambda t: t)
+    C = x.shape[-1]
+    a = F.linear(ao_tokens.to(dt), w("attn.proj.weight"), p["attn.proj.bias"])
+    ln1 = F.layer_norm(a, (C,), p["norm1.weight"], p["norm1.bias"], eps)
+    x_mid = x + ln1
+    pre = F.linear(rnd(x_mid), w("mlp.fc1.weight"), p["mlp.fc1.bias"])
+    hid = gelu(pre).to(dt)
+    y = F.linear(rnd(hid), w("mlp.fc2.weight"), p["mlp.fc2.bias"])
+    out = x_mid + F.layer_norm(y, (C,), p["norm2.weight"], p["norm2.bias"], eps)
+    return dict(proj=a, ln1=ln1, x_mid=x_mid, pre=pre, hid=hid, fc2=y, out=out) if parts else out
+
+
+def oracle_attention_tokens(pb, x, grid, layer, rolled, conv=O.DEFAULT):
+    """The oracle's own attention output (before the projection) in stream-token order, in the dtype of ``x``: ``earth_attention`` with an
+    identity projection on the rows gathered through ``window_table``."""
+    heads, C = O.HEADS[layer - 1], x.shape[-1]
+    nZ, nH, nW = window_shape(grid, layer, conv)
+    table = window_table(grid, layer, rolled, conv)
+    rows = torch.where((table >= 0)[:, None], x[table.clamp_min(0)], torch.zeros((), dtype=x.dtype)).reshape(nZ * nH, nW, L, C)
+    p = dict(pb)
+    p["attn.proj.weight"], p["attn.proj.bias"] = torch.eye(C, dtype=x.dtype), torch.zeros(C, dtype=x.dtype)
+    mask = O.shifted_window_mask(2 * nZ, 6 * nH, 12 * nW, x.dtype, conv) if rolled else None
+    o = O.earth_attention(p, rows, nZ * nH, heads, mask, None, conv).reshape(-1, C)
+    return o[inverse_window_table(table, x.shape[0])]
+
+
+def weight_planes(w, bf16=False):
+    """A three-term weight as the engine holds it: hi + lo planes of fp16 (bf16), in float64.  The lo plane of an fp16 pair is below 2^-14
+    whenever |w| < 2^-3, and fp16 resolves it to 2^-25 there whatever its size: a weight of 0.013 is held to 19 bits, one of 0.001 to 15."""
+    return stream_planes(w, bf16)
+
+
+def block_bar(pb, x64, ao64, form, bf16=False, eps=1e-5):
+    """(ref, e32, e_gelu, e_w, bar) of one post-attention case, from the reference alone: ref = the float64 result; e32 = the float32 yardstick
+    against it; e_gelu = the same float64 run with ``gelu_poly64`` against it; e_w (form "three" only, else 0) = the same float64 run with the
+    proj / fc1 / fc2 weights as ``weight_planes`` against it (all as max|.| / max|ref|);
+    bar = max(B, 16 k e32) + 2 e_gelu + e_w with B = BAR3 = 2e-6, k = 1 for fp16 planes and B = 64 BAR3, k = 64 for bf16."""
+    ref = post_attention_reference(pb, x64, ao64, form, eps)
+    f32 = post_attention_reference({k: v.float() for k, v in pb.items()}, x64.float(), ao64.float(), form, eps)
+    e32 = max_rel(f32, ref)[0]
+    e_gelu = max_rel(post_attention_reference(pb, x64, ao64, form, eps, gelu=gelu_poly64), ref)[0]
+    e_w = 0.0
+    if form == "three":
+        pw = {k: (weight_planes(v, bf16) if k in ("attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight") else v) for k, v in pb.items()}
+        e_w = max_rel(post_attention_reference(pw, x64, ao64, form, eps), ref)[0]
+    k = 64 if bf16 else 1
+    return ref, e32, e_gelu, e_w, max(k * BLOCK_BAR3, 16 * k * e32) + 2 * e_gelu + e_w
+
+
+BLOCK_BAR3 = 2e-6                               # tests/test_pangu_kernels_gpu.py BAR3
+EDGES = ("zero_ao", "zero_ao_fc2", "zero_var", "eps", "gelu")
+ZERO_VAR_BIAS = 0.375                           # exactly representable; 192 and 384 copies of it sum exactly in fp32 and float64
+EPS_TARGET_VAR = 3e-4                           # median row variance of the two LayerNorm inputs under "eps": eps = 1e-5 is 3 % of it
+GELU_SHIFT, GELU_STD = -4.0, 4.0                # fc1 pre-activations under "gelu": centred in the negative tail, 0.6 % of a normal law beyond +5.94
+
+
+def edge_params(grid, edge):
+    """(float32 parameters, their float64 copy) of ``peaked_params`` edited in the four tested blocks -- a block kernel always runs behind its
+    attention, so an edge is reached through parameters:
+      zero_ao      the V rows of attn.qkv (weight and bias) are zero: the attention output is 0 exactly, x_mid - x = LN1(proj.bias) for every token
+      zero_ao_fc2  and mlp.fc2.weight = 0: out = x + LN1(bp) + LN2(b2)
+      zero_var     zero_ao with attn.proj.bias = 0.375 in every channel: LayerNorm 1 sees rows of variance exactly 0 and yields norm1.bias
+      eps          attn.proj and mlp.fc2 (weight and bias) scaled so that the median row variance in front of each LayerNorm is 3e-4
+      gelu         mlp.fc1 scaled and shifted so that its pre-activations have mean -4, std 4: past the clamp on both sides
+    The scales of ``eps`` and ``gelu`` are measured in float64 on the oracle's own attention output of the block's input tap.  Read-only."""
+    assert edge in EDGES
+    return _edge_params(grid, edge)
+
+
+@lru_cache(maxsize=None)
+def _edge_params(grid, edge):
+    conv = conventions_of(grid)
+    base, base64 = peaked_params(grid)
+    taps, _ = reference(grid.n_lat, grid.n_lon, grid.pad)
+    out = {k: v.clone() for k, v in base.items()}
+    for layer, i in PEAKED_BLOCKS:
+        pre, C = f"layer{layer}.block{i}.", O.DIM * (1 if layer in (1, 4) else 2)
+        if edge in ("zero_ao", "zero_ao_fc2", "zero_var"):
+            out[pre + "attn.qkv.weight"][2 * C:] = 0
+            out[pre + "attn.qkv.bias"][2 * C:] = 0
+            if edge == "zero_ao_fc2":
+                out[pre + "mlp.fc2.weight"].zero_()
+            if edge == "zero_var":
+                out[pre + "attn.proj.bias"].fill_(ZERO_VAR_BIAS)
+            continue
+        x = taps[BEFORE[layer, i]].float().double()
+        pb = O._block_params(base64, layer, i)
+        ao = oracle_attention_tokens(pb, x, grid, layer, i % 2 == 1, conv)
+        if edge == "eps":
+            s1 = (EPS_TARGET_VAR / post_attention_reference(pb, x, ao, "three", parts=True)["proj"].var(-1, unbiased=False).median().item()) ** 0.5
+            out[pre + "attn.proj.weight"] *= s1
+            out[pre + "attn.proj.bias"] *= s1
+            pb = O._block_params(to64({k: v for k, v in out.items() if k.startswith(pre)}), layer, i)
+            s2 = (EPS_TARGET_VAR / post_attention_reference(pb, x, ao, "three", parts=True)["fc2"].var(-1, unbiased=False).median().item()) ** 0.5
+            out[pre + "mlp.fc2.weight"] *= s2
+            out[pre + "mlp.fc2.bias"] *= s2
+        else:
+            h = post_attention_reference(pb, x, ao, "three", parts=True)["pre"]
+            gain = GELU_STD / h.std().item()
+            out[pre + "mlp.fc1.weight"] *= gain
+            out[pre + "mlp.fc1.bias"] = out[pre + "mlp.fc1.bias"] * gain + (GELU_SHIFT - gain * h.mean().item())
+    return out, to64(out)
+
+
+def locate_token(grid, layer, flat, C):
+    """(token row -> z, h, w; channel) of a flat index into a [tokens][C] stream."""
+    _, H, W = O.Geometry(grid.n_lat, grid.n_lon, grid.pad).res(layer)
+    m, c = flat // C, flat % C
+    return f"token row {m} -> (z, h, w) = ({m // (H * W)}, {m % (H * W) // W}, {m % W}), channel {c}"

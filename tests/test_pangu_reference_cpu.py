@@ -1,7 +1,9 @@
 """The float64 reference of tests/test_pangu_kernels_gpu.py, checked on the CPU: it really runs in float64, the float32 oracle agrees
 with it to float32's own rounding, the stage helpers reproduce the oracle's taps, and the small grids have the paddings they were
 chosen for.  Likewise the helpers of tests/test_pangu_attention_kernels_gpu.py: the compact bias addresses every cell once, the window
-table is a permutation, the peaked parameters are peaked, and together the helpers rebuild the oracle's block."""
+table is a permutation, the peaked parameters are peaked, and together the helpers rebuild the oracle's block.  And those of
+tests/test_pangu_block_kernels_gpu.py: the post-attention reference rebuilds the block too, the GELU fit is the one csrc/common.h claims, and
+each edge parameter set has the property that makes it an edge."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -228,3 +230,131 @@ def test_attention_helpers_rebuild_the_oracles_block(gid, layer, i, conv):
     assert torch.allclose(D[win * 144 + qi, head * 32:head * 32 + 32], by_hand, rtol=1e-12, atol=0)
     assert "head 2 (dim 5), query 77 -> (z_q, h_q, w_q) = (1, 0, 5)" in R.locate_attention_row(win * 144 + qi, 2 * 32 + 5, 2)
     assert "row 46 -> (z_q, z_k, h_q, h_k) = (1, 0, 4, 1), column 18" in R.locate_bias_cell((5 * 144 + 46) * 24 + 18, 6)
+
+
+# ---- everything after the attention (tests/test_pangu_block_kernels_gpu.py) ------------------------------------------------------------ #
+BLOCK_GRIDS = [R.GRID["25x96-back"], R.GRID["33x96"]]
+
+
+@pytest.mark.parametrize("layer,i", R.PEAKED_BLOCKS)
+@pytest.mark.parametrize("gid", ["24x96", "33x96"])
+def test_post_attention_reference_rebuilds_the_oracles_block(gid, layer, i):
+    """form = "three" on the unrounded stream with the oracle's own attention output gives ``earth_block`` to float64 rounding, and the inverse
+    table is a left inverse of the window table on every real token."""
+    grid = R.GRID[gid]
+    conv = R.conventions_of(grid)
+    pb = O._block_params(R.peaked_params(grid)[1], layer, i)
+    xin = R.reference(grid.n_lat, grid.n_lon, grid.pad)[0][R.BEFORE[layer, i]].float().double()
+    want = O.earth_block(pb, xin, O.Geometry(grid.n_lat, grid.n_lon, grid.pad).res(layer), O.HEADS[layer - 1], i % 2 == 1, None, conv)
+    ao = R.oracle_attention_tokens(pb, xin, grid, layer, i % 2 == 1, conv)
+    err = R.max_rel(R.post_attention_reference(pb, xin, ao, "three"), want)[0]
+    print(f"{gid} layer{layer}.block{i}: post_attention_reference against earth_block {err:.1e}")
+    assert err < 1e-12
+    # the same attention output through the attention helpers (the route the device buffer takes: window rows, gathered through the inverse)
+    o = _peaked_block(grid, layer, i, conv, fp16=False)[2][0]
+    table = R.window_table(grid, layer, i % 2 == 1, conv)
+    inv = R.inverse_window_table(table, xin.shape[0])
+    assert torch.equal(table[inv], torch.arange(xin.shape[0])) and int((table >= 0).sum()) == xin.shape[0]
+    assert R.max_rel(o[inv], ao)[0] < 1e-12
+
+
+def test_ao_tokens_unblocks_gathers_and_sums_the_planes():
+    grid = R.GRID["33x96"]
+    table = R.window_table(grid, 2, True)
+    ntok, C = grid.tokens[1], 384
+    rows = torch.randn(table.numel(), C, generator=torch.Generator().manual_seed(1))
+    hi = rows.half()
+    lo = (rows - hi.float()).half()
+    blocked = lambda t: t.reshape(-1, 16, C // 32, 32).permute(0, 2, 1, 3).reshape(-1)
+    stale = torch.full_like(blocked(lo), float("nan"))
+    got = R.ao_tokens((blocked(hi), blocked(lo)), table, ntok, C, one=False)
+    assert torch.equal(got[table[table >= 0]], (hi.double() + lo.double())[table >= 0])
+    assert torch.equal(R.ao_tokens((blocked(hi), stale), table, ntok, C, one=True)[table[table >= 0]], hi.double()[table >= 0])
+    x = torch.randn(64, 8)
+    assert (R.stream_planes(x) - x.double()).abs().max() <= 2.0 ** -21 * x.abs().max() and (R.stream_planes(x, bf16=True) - x.double()).abs().max() > 2.0 ** -21
+
+
+def test_gelu_poly64_is_the_fit_common_h_claims():
+    x = torch.linspace(-8, 8, 1600001, dtype=torch.float64)
+    err = (R.gelu_poly64(x) - F.gelu(x)).abs().max().item()
+    print(f"gelu_poly64 against erf-GELU on [-8, 8]: {err:.2e}")
+    assert err <= 3.8e-7
+    assert R.form_of(0x66F, 1) == "two" and R.form_of(0x66F, 2) == "one" and R.form_of(0x10F, 1) == "one" and R.form_of(0x10F, 2) == "two" and R.form_of(0, 3) == "three"
+
+
+def test_forms_differ_where_they_should_and_only_there():
+    """"two" is "three" on fp16 weights; "one" also rounds x_mid and the hidden activation; the float32 yardstick follows the float64 run."""
+    grid = R.GRID["24x96"]
+    layer, i = 2, 1
+    pb = O._block_params(R.peaked_params(grid)[1], layer, i)
+    x = R.stream_planes(R.reference(grid.n_lat, grid.n_lon, grid.pad)[0][R.BEFORE[layer, i]].float())
+    ao = R.oracle_attention_tokens(pb, x, grid, layer, True).half().double()
+    three, two, one = (R.post_attention_reference(pb, x, ao, f) for f in R.FORMS)
+    pb16 = {k: (v.half().double() if k in ("attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight") else v) for k, v in pb.items()}
+    assert torch.equal(R.post_attention_reference(pb16, x, ao, "three"), two)
+    d2, d1 = R.max_rel(two, three)[0], R.max_rel(one, two)[0]
+    print(f"two against three {d2:.1e}, one against two {d1:.1e}")
+    assert 1e-6 < d2 < 1e-3 and 1e-6 < d1 < 1e-3
+    for form in R.FORMS:
+        ref, e32, e_gelu, e_w, bar = R.block_bar(pb, x, ao, form)
+        print(f"{form}: e32 {e32:.2e} e_gelu {e_gelu:.2e} e_w {e_w:.2e} bar {bar:.2e}")
+        assert (e_w > 0) == (form == "three") and e_w < 1e-5
+        # "one": an operand that sits on an fp16 tie rounds the other way when the value in front of it differs in its last float32 bits (or by
+        # the GELU fit's 1e-7), so both yardsticks carry whole fp16 steps of single operands there
+        assert (e32 < 1e-5 and e_gelu < 3.8e-7 and bar < 2e-4) if form != "one" else (e32 < 1e-3 and e_gelu < 1e-3)
+        assert bar >= R.BLOCK_BAR3
+
+
+def _edge_case(grid, edge, layer, i):
+    pb = O._block_params(R.edge_params(grid, edge)[1], layer, i)
+    x = R.stream_planes(R.reference(grid.n_lat, grid.n_lon, grid.pad)[0][R.BEFORE[layer, i]].float())
+    ao = R.oracle_attention_tokens(pb, x, grid, layer, i % 2 == 1, R.conventions_of(grid))
+    return pb, x, ao
+
+
+@pytest.mark.parametrize("layer,i", R.PEAKED_BLOCKS)
+@pytest.mark.parametrize("grid", BLOCK_GRIDS, ids=lambda g: g.id)
+def test_zero_attention_edges_are_what_they_claim(grid, layer, i):
+    for edge in ("zero_ao", "zero_ao_fc2", "zero_var"):
+        pb, x, ao = _edge_case(grid, edge, layer, i)
+        assert torch.equal(ao, torch.zeros_like(ao)), edge
+        C = x.shape[1]
+        r = R.post_attention_reference(pb, x, ao, "three", parts=True)
+        row = F.layer_norm(pb["attn.proj.bias"], (C,), pb["norm1.weight"], pb["norm1.bias"], 1e-5)
+        assert (r["x_mid"] - x - row).abs().max() <= 1e-14, edge                      # one row for every token
+        if edge == "zero_ao_fc2":
+            want = x + row + F.layer_norm(pb["mlp.fc2.bias"], (C,), pb["norm2.weight"], pb["norm2.bias"], 1e-5)
+            assert (r["out"] - want).abs().max() <= 1e-14
+        if edge == "zero_var":
+            assert torch.equal(r["proj"].var(-1, unbiased=False), torch.zeros(x.shape[0]).double())
+            assert (r["ln1"] - pb["norm1.bias"]).abs().max() <= 1e-14
+
+
+@pytest.mark.parametrize("layer,i", R.PEAKED_BLOCKS)
+@pytest.mark.parametrize("grid", BLOCK_GRIDS, ids=lambda g: g.id)
+def test_eps_edge_makes_the_layernorm_epsilon_visible(grid, layer, i):
+    pb, x, ao = _edge_case(grid, "eps", layer, i)
+    r = R.post_attention_reference(pb, x, ao, "three", parts=True)
+    v1, v2 = (r[k].var(-1, unbiased=False).median().item() for k in ("proj", "fc2"))
+    assert 1e-4 <= v1 <= 1e-2 and 1e-4 <= v2 <= 1e-2, (v1, v2)
+    moved = []
+    for form in R.FORMS:
+        ref, e32, e_gelu, e_w, bar = R.block_bar(pb, x, ao, form)
+        moved.append(R.max_rel(R.post_attention_reference(pb, x, ao, form, eps=1e-6), ref)[0] / bar)
+    print(f"{grid.id} layer{layer}.block{i}: row variances {v1:.2e} {v2:.2e}; eps = 1e-6 moves the result by {moved[0]:.0f} / {moved[1]:.0f} / {moved[2]:.0f} bars")
+    # "one": its bar is the tie flips of single fp16 operands (test_forms_differ_where_they_should_and_only_there), some hundred times the
+    # arithmetic's own; a tenfold eps still moves the result past it
+    assert min(moved[:2]) >= 20 and moved[2] >= 2
+
+
+@pytest.mark.parametrize("layer,i", R.PEAKED_BLOCKS)
+@pytest.mark.parametrize("grid", BLOCK_GRIDS, ids=lambda g: g.id)
+def test_gelu_edge_reaches_past_the_clamp_on_both_sides(grid, layer, i):
+    pb, x, ao = _edge_case(grid, "gelu", layer, i)
+    for form in R.FORMS:
+        r = R.post_attention_reference(pb, x, ao, form, parts=True)
+        h = r["pre"]
+        hi, lo, tail = (h > R.GELU_CLAMP).double().mean().item(), (h < -R.GELU_CLAMP).double().mean().item(), ((h > -6) & (h < -2)).double().mean().item()
+        print(f"{grid.id} layer{layer}.block{i} {form}: above +5.94 {100 * hi:.2f} %, below -5.94 {100 * lo:.2f} %, in -6 .. -2 {100 * tail:.1f} %, median {h.median():.2f}, max|h| {h.abs().max():.1f}")
+        assert hi >= 1e-3 and lo >= 1e-3 and h.abs().max() > 8 and -6 < h.median() < -2 and tail >= 0.3
+        assert r["hid"].abs().max() < 65504 and h.abs().max() < 65504
