@@ -456,6 +456,41 @@ class GlobalModel:
         return pred, output_paths
 
 
+class EngineModel(GlobalModel):
+    """A wrapper whose model is a HIP-engine TimeLoop: ``timeloop`` names its class as ``"module:Class"`` under this package (imported
+    when the model is built), the keyword arguments beyond the reference's signature go to it, and what the reference reads off the model
+    is passed through."""
+
+    model_name = ""
+    timeloop = ""
+
+    def __init__(self, *args, cfg=None, device="cuda:0", params=None, **kwargs):
+        # extras beyond the reference's signature (all optional): network configuration, device, parameter dict
+        self._engine_kw = dict(cfg=cfg, device=device, params=params)
+        super().__init__(self.model_name, *args, **kwargs)
+
+    def build_model(self):
+        import importlib
+        module, name = self.timeloop.split(":")
+        return getattr(importlib.import_module(f"...{module}", __package__), name)(**self._engine_kw)
+
+    @property
+    def device(self):
+        return self.model.device
+
+    @property
+    def time_step(self):
+        return self.model.time_step
+
+    @property
+    def in_channel_names(self):
+        return self.model.in_channel_names
+
+    @property
+    def out_channel_names(self):
+        return self.model.out_channel_names
+
+
 def _axis_index(axis: np.ndarray, x: float) -> tuple[int, bool]:
     """(index of the axis value nearest to x, whether it is an exact hit).  Uniform axes (lat 90..-90, lon 0..359.75) are
     inverted arithmetically; anything else falls back to a linear scan."""

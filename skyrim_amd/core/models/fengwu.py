@@ -3,13 +3,11 @@ earth2studio's ``FengWu.load_model(...)``; ``predict``, ``rollout``, saving and 
 FengwuModel runs ``forecast`` only: its rollout raises NotImplementedError)."""
 from __future__ import annotations
 
-import datetime
-
 from ...fengwu.spec import CHANNELS  # noqa: F401  (the reference's fengwu.py channel list)
-from .base import GlobalModel
+from .base import EngineModel
 
 
-class FengwuModel(GlobalModel):
+class FengwuModel(EngineModel):
     """
     From:
     https://github.com/NVIDIA/earth2studio/blob/68dd00bd76be8abc90badd39d0f51f26294ce526/earth2studio/models/px/fengwu.py#L113-L125
@@ -29,28 +27,4 @@ class FengwuModel(GlobalModel):
     """
 
     model_name = "fengwu"
-
-    def __init__(self, *args, cfg=None, device="cuda:0", params=None, **kwargs):
-        # extras beyond the reference's signature (all optional): network configuration, device, parameter dict
-        self._engine_kw = dict(cfg=cfg, device=device, params=params)
-        super().__init__(self.model_name, *args, **kwargs)
-
-    def build_model(self):
-        from ...fengwu.timeloop import FengwuTimeLoop
-        return FengwuTimeLoop(**self._engine_kw)
-
-    @property
-    def device(self):
-        return self.model.device
-
-    @property
-    def time_step(self):
-        return datetime.timedelta(hours=6)
-
-    @property
-    def in_channel_names(self):
-        return self.model.in_channel_names
-
-    @property
-    def out_channel_names(self):
-        return self.model.out_channel_names
+    timeloop = "fengwu.timeloop:FengwuTimeLoop"

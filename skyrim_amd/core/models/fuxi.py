@@ -3,13 +3,11 @@ earth2studio's ``FuXi.load_model(...)``; ``predict``, ``rollout``, saving and en
 FuxiModel runs ``forecast`` only: its rollout raises NotImplementedError, fuxi.py:120-124)."""
 from __future__ import annotations
 
-import datetime
-
 from ...fuxi.spec import CHANNELS  # noqa: F401  (the reference's fuxi.py:14-22 channel list)
-from .base import GlobalModel
+from .base import EngineModel
 
 
-class FuxiModel(GlobalModel):
+class FuxiModel(EngineModel):
     """
     n_history_levels: int = 2  (states at t - 6 h and t; one step = 6 h)
     grid.lat: list of length 721, [90, 89.75, 89.50, ..., -89.75, -90]
@@ -19,28 +17,4 @@ class FuxiModel(GlobalModel):
     """
 
     model_name = "fuxi"
-
-    def __init__(self, *args, cfg=None, device="cuda:0", params=None, **kwargs):
-        # extras beyond the reference's signature (all optional): network configuration, device, parameter dict
-        self._engine_kw = dict(cfg=cfg, device=device, params=params)
-        super().__init__(self.model_name, *args, **kwargs)
-
-    def build_model(self):
-        from ...fuxi.timeloop import FuxiTimeLoop
-        return FuxiTimeLoop(**self._engine_kw)
-
-    @property
-    def device(self):
-        return self.model.device
-
-    @property
-    def time_step(self):
-        return datetime.timedelta(hours=6)
-
-    @property
-    def in_channel_names(self):
-        return self.model.in_channel_names
-
-    @property
-    def out_channel_names(self):
-        return self.model.out_channel_names
+    timeloop = "fuxi.timeloop:FuxiTimeLoop"

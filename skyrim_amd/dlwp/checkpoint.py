@@ -20,6 +20,7 @@ import tarfile
 import numpy as np
 import torch
 
+from .. import weights
 from .spec import MAP_SLOTS, DlwpConfig, param_spec
 
 # slot -> (file, variable) of the static fields
@@ -102,6 +103,10 @@ def read_state_dict(path: str) -> dict:
         if isinstance(sd, dict) and key in sd:
             sd = sd[key]
     return sd
+
+
+def load(path: str, cfg: DlwpConfig) -> dict:
+    return weights.load_slots(path, lambda d: load_package(d, cfg))
 
 
 def load_package(path: str, cfg: DlwpConfig) -> dict:

@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from .. import native
+from ..engine import Engine
 from .spec import MAP_SLOTS, SKIP_OF, DlwpConfig, convs, days_since_j2000, pad_table_i32, param_spec, to_csr
 
 _P = ctypes.c_void_p
@@ -96,25 +97,17 @@ class _Map:
         self.S = torch.from_numpy(s.astype(np.float32)).to(device)
 
 
-class DlwpEngine:
+class DlwpEngine(Engine):
+    keep = ("convs",)
+    prepare_symbol = "skdlwp_prepare_weight"
+
     def __init__(self, cfg: DlwpConfig | None = None, device: str | torch.device = "cuda:0"):
         self.cfg = c = cfg or DlwpConfig()
         if c.face % 4 or c.channels > 8 or c.n_history != 2 or c.in_ch > IN_LD or c.out_ch > OUT_LD or not -1 <= c.polar_flip_face <= 5:
             raise ValueError(f"compiled for face sizes that are multiples of 4, at most 8 channels and 2 history levels; got face {c.face}, "
                              f"{c.channels} channels, {c.n_history} levels")
         self.convs = convs(c)
-        self.lib = load_library()
-        self.device = torch.device(device)
-        self.state_shape = (c.channels, c.n_lat, c.n_lon)
-        self.prepared = False
-
-    def release(self):
-        """Drop every prepared matrix and work buffer (the C ABI holds no state of its own)."""
-        keep = ("cfg", "convs", "lib", "device", "state_shape")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
-        self.prepared = False
+        self._bind(load_library(), device, (c.channels, c.n_lat, c.n_lon))
 
     def load_params(self, params: dict):
         c = self.cfg
@@ -147,7 +140,7 @@ class DlwpEngine:
                 cells = 6 * n * n
                 cin_pad = IN_LD if src == "x" else cin
                 ws = [params[f"{kind}_{name}.weight"].double() for kind in ("equatorial", "polar")]
-                w = native.HiLoWeight(dev, self.lib.skdlwp_prepare_weight, torch.stack([conv_matrix(x, cin_pad) for x in ws]))
+                w = self._weight(torch.stack([conv_matrix(x, cin_pad) for x in ws]))
                 bias = f32(torch.stack([params[f"{kind}_{name}.bias"].double() for kind in ("equatorial", "polar")]))
                 ld = OUT_LD if name == "last" else cout
                 out = torch.zeros(cells * ld, dtype=torch.float32, device=dev)
@@ -194,16 +187,11 @@ class DlwpEngine:
         """The TISR times of the two input levels of a call whose newest level is at ``time`` (days since J2000.0)."""
         return tuple(days_since_j2000(time + datetime.timedelta(hours=h)) for h in self.cfg.tisr_offsets_h)
 
-    def _check_state(self, x: torch.Tensor, what: str):
-        if x.device != self.device or x.dtype != torch.float32 or tuple(x.shape) != self.state_shape or not x.is_contiguous():
-            raise ValueError(f"{what}: expected a contiguous float32 tensor of shape {self.state_shape} on {self.device}")
-
     def call(self, x0: torch.Tensor, x1: torch.Tensor, time: datetime.datetime):
         """One network call: states at time - 6 h (x0) and time (x1) -> new tensors (t + 6 h, t + 12 h)."""
-        if not self.prepared:
-            raise RuntimeError("DlwpEngine.call before load_params: not prepared")
-        self._check_state(x0, "x0")
-        self._check_state(x1, "x1")
+        self.require_prepared("call")
+        self.check_state(x0, "x0")
+        self.check_state(x1, "x1")
         with torch.cuda.device(self.device):
             y6 = torch.empty(self.state_shape, dtype=torch.float32, device=self.device)
             y12 = torch.empty_like(y6)

@@ -15,6 +15,7 @@ import re
 import numpy as np
 import torch
 
+from .. import weights
 from .spec import FcnConfig, param_spec
 
 # keys of the published model that the forward does not read: tolerated, never placed
@@ -52,7 +53,11 @@ def convert(state_dict: dict, cfg: FcnConfig, means, stds) -> dict:
     return out
 
 
-def load(weights_path: str, cfg: FcnConfig, means_path: str, stds_path: str) -> dict:
+def load(path: str, cfg: FcnConfig) -> dict:
+    return weights.load_slots(path, lambda d: load_package(d, cfg))
+
+
+def load_files(weights_path: str, cfg: FcnConfig, means_path: str, stds_path: str) -> dict:
     sd = torch.load(weights_path, map_location="cpu", weights_only=False)
     if isinstance(sd, dict) and "model_state" in sd:
         sd = sd["model_state"]
@@ -64,4 +69,4 @@ def load_package(path: str, cfg: FcnConfig) -> dict:
     names = sorted(n for n in os.listdir(path) if n.endswith((".tar", ".pt", ".pth")))
     if len(names) != 1:
         raise ValueError(f"{path}: expected exactly one weights archive (*.tar / *.pt / *.pth), found {names}")
-    return load(os.path.join(path, names[0]), cfg, os.path.join(path, "global_means.npy"), os.path.join(path, "global_stds.npy"))
+    return load_files(os.path.join(path, names[0]), cfg, os.path.join(path, "global_means.npy"), os.path.join(path, "global_stds.npy"))

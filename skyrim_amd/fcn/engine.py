@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import native
+from ..engine import Engine
 from .spec import FcnConfig, param_spec
 
 SPECTRAL_BLOCK = 96            # block size the spectral MLP kernel is compiled for
@@ -131,7 +132,9 @@ class _Pairs:
         torch.cuda.current_stream(eng.device).synchronize()
 
 
-class FcnEngine:
+class FcnEngine(Engine):
+    prepare_symbol = "skfcn_prepare_weight"
+
     def __init__(self, cfg: FcnConfig | None = None, device: str | torch.device = "cuda:0"):
         self.cfg = c = cfg or FcnConfig()
         if c.n_lat % c.patch or c.n_lon % c.patch:
@@ -141,21 +144,7 @@ class FcnEngine:
                              f"multiples of 32; got embed {c.embed_dim}, {c.num_blocks} blocks, hidden {c.hidden}")
         if not 0 < c.km <= c.w // 2 + 1:
             raise ValueError(f"kept_lon_modes {c.km} outside (0, {c.w // 2 + 1}]")
-        self.lib = load_library()
-        self.device = torch.device(device)
-        self.state_shape = (c.in_chans, c.n_lat, c.n_lon)
-        self.prepared = False
-
-    def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
-        return native.HiLoWeight(self.device, self.lib.skfcn_prepare_weight, w)
-
-    def release(self):
-        """Drop every prepared matrix and work buffer (the C ABI holds no state of its own)."""
-        keep = ("cfg", "lib", "device", "state_shape")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
-        self.prepared = False
+        self._bind(load_library(), device, (c.in_chans, c.n_lat, c.n_lon))
 
     def load_params(self, params: dict):
         c = self.cfg
@@ -226,11 +215,9 @@ class FcnEngine:
 
     def step(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """One 6-h step: fp32 (in_chans, n_lat, n_lon) on the engine device -> (out_chans, n_lat, n_lon)."""
-        if not self.prepared:
-            raise RuntimeError("FcnEngine.step before load_params: not prepared")
+        self.require_prepared("step")
         c = self.cfg
-        if x.device != self.device or x.dtype != torch.float32 or tuple(x.shape) != self.state_shape or not x.is_contiguous():
-            raise ValueError(f"expected a contiguous float32 tensor of shape {self.state_shape} on {self.device}")
+        self.check_state(x)
         with torch.cuda.device(self.device):
             y = out if out is not None else torch.empty((c.out_chans, c.n_lat, c.n_lon), dtype=torch.float32, device=self.device)
             if y.device != self.device or y.dtype != torch.float32 or tuple(y.shape) != (c.out_chans, c.n_lat, c.n_lon) or not y.is_contiguous():

@@ -14,46 +14,39 @@ stacks have identical shapes, so the assumed order of use (spec.param_spec) is a
 from __future__ import annotations
 
 import glob
-import json
 import os
 
 import numpy as np
 import torch
 
-from ..pangu.onnx_weights import _apply, auto_map_slots, read_model
+from .. import weights
+from ..pangu.onnx_weights import load_graph_slots, map_slots, read_norm_json
 from .spec import FengwuConfig, param_spec, shape_source
 
 MAP_FILE = "fengwu.map.json"
 
 
 def load(path: str, cfg: FengwuConfig) -> dict:
-    if os.path.isdir(path):
-        return load_onnx_dir(path, cfg)
-    return torch.load(path, map_location="cpu")
+    return weights.load_slots(path, lambda d: load_onnx_dir(d, cfg))
 
 
 def graph_mapping(model, cfg: FengwuConfig, explicit: dict | None = None) -> tuple[dict, list]:
     """{slot: [onnx_name, transform]} and the list of unresolved slots."""
-    slots = param_spec(cfg)
-    if explicit is not None:
-        mapping = {k: (v if isinstance(v, list) else [v, "id"]) for k, v in explicit.items()}
-        return mapping, [s for s, _ in slots if s not in mapping]
-    return auto_map_slots(model, slots)
+    return map_slots(model, param_spec(cfg), explicit)
 
 
 def _affine(path: str, cfg: FengwuConfig) -> tuple:
     npy = [os.path.join(path, f) for f in ("global_means.npy", "global_stds.npy")]
     if all(os.path.exists(f) for f in npy):
-        mean, std = (np.load(f).astype(np.float64).reshape(-1) for f in npy)
-    elif os.path.exists(os.path.join(path, "norm.json")):
-        with open(os.path.join(path, "norm.json")) as f:
-            n = json.load(f)
-        mean, std = np.asarray(n["mean"], dtype=np.float64).reshape(-1), np.asarray(n["std"], dtype=np.float64).reshape(-1)
+        mean, std = (torch.tensor(np.load(f).astype(np.float64).reshape(-1), dtype=torch.float32) for f in npy)
     else:
-        raise ValueError(f"{path}: the input affine is missing (global_means.npy + global_stds.npy, or norm.json)")
-    if mean.size != cfg.channels or std.size != cfg.channels:
-        raise ValueError(f"{path}: the input affine holds {mean.size} / {std.size} values, the config's modalities {cfg.channels} channels")
-    return torch.tensor(mean, dtype=torch.float32), torch.tensor(std, dtype=torch.float32)
+        norm = read_norm_json(path)
+        if norm is None:
+            raise ValueError(f"{path}: the input affine is missing (global_means.npy + global_stds.npy, or norm.json)")
+        mean, std = norm[0].reshape(-1), norm[1].reshape(-1)
+    if mean.numel() != cfg.channels or std.numel() != cfg.channels:
+        raise ValueError(f"{path}: the input affine holds {mean.numel()} / {std.numel()} values, the config's modalities {cfg.channels} channels")
+    return mean, std
 
 
 def load_onnx_dir(path: str, cfg: FengwuConfig) -> dict:
@@ -62,24 +55,5 @@ def load_onnx_dir(path: str, cfg: FengwuConfig) -> dict:
         raise ValueError(f"{path}: expected exactly one *.onnx graph, found {len(graphs)}")
     out = {}
     out["norm.mean"], out["norm.std"] = _affine(path, cfg)
-    model = read_model(graphs[0], base_dir=path)
-    mp = os.path.join(path, MAP_FILE)
-    explicit = None
-    if os.path.exists(mp):
-        with open(mp) as fh:
-            explicit = json.load(fh)
-    mapping, unresolved = graph_mapping(model, cfg, explicit)
-    if unresolved:
-        raise ValueError(f"{graphs[0]}: {len(unresolved)} parameter slots unresolved: {unresolved}; write {MAP_FILE} "
-                         "({slot: onnx_name | [onnx_name, transform]}) next to it")
-    shapes = dict(param_spec(cfg))
-    for slot, (name, how) in mapping.items():
-        if slot not in shapes:
-            raise KeyError(f"{MAP_FILE}: {slot!r} is not a parameter slot of this config")
-        if name not in model.initializers:
-            raise KeyError(f"{slot}: initializer {name!r} not in {graphs[0]}")
-        try:
-            out[slot] = torch.from_numpy(_apply(model.initializers[name].array().astype(np.float32), how, shapes[slot]))
-        except ValueError as e:
-            raise ValueError(f"{graphs[0]}: slot {slot} (shape from FengwuConfig.{shape_source(slot)}): initializer {name!r}: {e}") from None
+    out.update(load_graph_slots(graphs[0], param_spec(cfg), os.path.join(path, MAP_FILE), source=lambda slot: f"FengwuConfig.{shape_source(slot)}"))
     return out

@@ -20,6 +20,7 @@ import math
 import torch
 
 from .. import native
+from ..engine import CheckedParams, Engine
 from .spec import (FengwuConfig, bias_table, block_geometry, block_shift, check_config, full_param_spec, pad_to, shape_source,
                    window_types)
 
@@ -85,27 +86,15 @@ def _ptr(t, off: int = 0):
     return None if t is None else t.data_ptr() + 4 * off
 
 
-class FengwuEngine:
+class FengwuEngine(Engine):
+    prepare_symbol = "skfw_prepare_weight"
+
     def __init__(self, cfg: FengwuConfig | None = None, device: str | torch.device = "cuda:0"):
         self.cfg = c = cfg or FengwuConfig()
         check_config(c)
-        self.lib = load_library()
-        self.device = torch.device(device)
-        self.state_shape = (c.channels, c.n_lat, c.n_lon)
-        self.prepared = False
-
-    def release(self):
-        """Drop every prepared matrix, table and work buffer (the C ABI holds no state of its own)."""
-        keep = ("cfg", "lib", "device", "state_shape")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
-        self.prepared = False
+        self._bind(load_library(), device, (c.channels, c.n_lat, c.n_lon))
 
     # ---- loading ---- #
-    def _hilo(self, w: torch.Tensor) -> native.HiLoWeight:
-        return native.HiLoWeight(self.device, self.lib.skfw_prepare_weight, w)
-
     def _f32(self, ts) -> torch.Tensor:
         return torch.stack([torch.as_tensor(t).float().cpu() for t in ts]).contiguous().to(self.device)
 
@@ -118,11 +107,11 @@ class FengwuEngine:
             g = lambda name: [p[f"{pre}.{i}.{name}"] for pre in prefixes]           # noqa: E731
             sh = block_shift(win, i)
             tabs = [bias_table(c, t, grid, win, sh) for t in g("attn.bias_table")]
-            out.append(dict(n1_g=self._f32(g("norm1.weight")), n1_b=self._f32(g("norm1.bias")), qkv=self._hilo(self._f32(g("attn.qkv.weight"))),
-                            qkv_b=self._f32(g("attn.qkv.bias")), table=self._f32(tabs), proj=self._hilo(self._f32(g("attn.proj.weight"))),
+            out.append(dict(n1_g=self._f32(g("norm1.weight")), n1_b=self._f32(g("norm1.bias")), qkv=self._weight(self._f32(g("attn.qkv.weight"))),
+                            qkv_b=self._f32(g("attn.qkv.bias")), table=self._f32(tabs), proj=self._weight(self._f32(g("attn.proj.weight"))),
                             proj_b=self._f32(g("attn.proj.bias")), n2_g=self._f32(g("norm2.weight")), n2_b=self._f32(g("norm2.bias")),
-                            fc1=self._hilo(self._f32(g("mlp.fc1.weight"))), fc1_b=self._f32(g("mlp.fc1.bias")),
-                            fc2=self._hilo(self._f32(g("mlp.fc2.weight"))), fc2_b=self._f32(g("mlp.fc2.bias")), shift=sh,
+                            fc1=self._weight(self._f32(g("mlp.fc1.weight"))), fc1_b=self._f32(g("mlp.fc1.bias")),
+                            fc2=self._weight(self._f32(g("mlp.fc2.weight"))), fc2_b=self._f32(g("mlp.fc2.bias")), shift=sh,
                             types=window_types(c, grid, win, sh)))
         return out
 
@@ -133,18 +122,14 @@ class FengwuEngine:
         for name, shape in shapes.items():
             if name not in params:
                 raise ValueError(f"parameter {name} missing (expected shape {shape})")
-        p = _Checked(params, shapes)
+        p = CheckedParams(params, shapes, source=lambda name: f"FengwuConfig.{shape_source(name)}")
         for name in shapes:                      # every shape before any upload: a mismatched graph is refused as a whole
             p[name]
         D1, D2 = c.dims
         names = [n for n, _ in c.modalities]
         enc, dec = [f"enc.{n}" for n in names], [f"dec.{n}" for n in names]
         with torch.cuda.device(dev):
-            std = p["norm.std"].double()
-            if not bool((std != 0).all()):
-                raise ValueError(f"norm.std must hold {c.channels} non-zero values")
-            self.mean = p["norm.mean"].float().contiguous().to(dev)
-            self.std, self.inv_std = std.float().to(dev), (1.0 / std).float().to(dev)
+            self.upload_affine(p["norm.mean"], p["norm.std"], c.channels)
             emb = torch.zeros(c.n_mod, D1, c.k_embed)
             rec = torch.zeros(c.n_mod, c.n_recover, D1)
             for z, (n, cm) in enumerate(c.modalities):
@@ -154,18 +139,18 @@ class FengwuEngine:
             for z, (n, cm) in enumerate(c.modalities):
                 rec_b[z, :cm] = p[f"dec.{n}.recovery.bias"].float()
             self.w = dict(
-                embed=self._hilo(emb), embed_b=self._f32([p[f"{e}.embed.bias"] for e in enc]),
+                embed=self._weight(emb), embed_b=self._f32([p[f"{e}.embed.bias"] for e in enc]),
                 en_g=self._f32([p[f"{e}.embed_norm.weight"] for e in enc]), en_b=self._f32([p[f"{e}.embed_norm.bias"] for e in enc]),
                 enc0=self._blocks(p, [f"{e}.s0" for e in enc], "s0", c.enc_depths[0]),
                 mg_g=self._f32([p[f"{e}.merge.norm.weight"] for e in enc]), mg_b=self._f32([p[f"{e}.merge.norm.bias"] for e in enc]),
-                merge=self._hilo(self._f32([p[f"{e}.merge.reduction.weight"] for e in enc])),
+                merge=self._weight(self._f32([p[f"{e}.merge.reduction.weight"] for e in enc])),
                 enc1=self._blocks(p, [f"{e}.s1" for e in enc], "s1", c.enc_depths[1]),
                 fuser=self._blocks(p, ["fuser"], "fuser", c.fuser_depth),
                 dec1=self._blocks(p, [f"{d}.s1" for d in dec], "s1", c.dec_depths[0]),
-                expand=self._hilo(self._f32([p[f"{d}.expand.weight"] for d in dec])),
-                skip=self._hilo(self._f32([p[f"{d}.skip.weight"] for d in dec])), skip_b=self._f32([p[f"{d}.skip.bias"] for d in dec]),
+                expand=self._weight(self._f32([p[f"{d}.expand.weight"] for d in dec])),
+                skip=self._weight(self._f32([p[f"{d}.skip.weight"] for d in dec])), skip_b=self._f32([p[f"{d}.skip.bias"] for d in dec]),
                 dec0=self._blocks(p, [f"{d}.s0" for d in dec], "s0", c.dec_depths[1]),
-                recover=self._hilo(rec), recover_b=rec_b.contiguous().to(dev))
+                recover=self._weight(rec), recover_b=rec_b.contiguous().to(dev))
             (h1, w1), (h2, w2) = c.grid1, c.grid2
             M, t1, t2 = c.n_mod, h1 * w1, h2 * w2
             big = M * max(t1 * D1, t2 * D2, t2 * 4 * D1)
@@ -291,11 +276,9 @@ class FengwuEngine:
 
     def call(self, x0: torch.Tensor, x1: torch.Tensor) -> torch.Tensor:
         """One network call: states at t - 6 h (x0) and t (x1) -> a new tensor, the state at t + 6 h."""
-        if not self.prepared:
-            raise RuntimeError("FengwuEngine.call before load_params: not prepared")
-        for t, w in ((x0, "x0"), (x1, "x1")):
-            if t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != self.state_shape or not t.is_contiguous():
-                raise ValueError(f"{w}: expected a contiguous float32 tensor of shape {self.state_shape} on {self.device}")
+        self.require_prepared("call")
+        self.check_state(x0, "x0")
+        self.check_state(x1, "x1")
         with torch.cuda.device(self.device):
             y = torch.empty(self.state_shape, dtype=torch.float32, device=self.device)
             self.embed_stage(x0, x1)
@@ -303,16 +286,3 @@ class FengwuEngine:
             self.fuser()
             self.decoders(y)
         return y
-
-
-class _Checked:
-    """``params`` read one key at a time, shape-checked: the error names the slot and the config field its shape comes from."""
-
-    def __init__(self, params, shapes: dict):
-        self.params, self.shapes = params, shapes
-
-    def __getitem__(self, name):
-        t = torch.as_tensor(self.params[name])
-        if tuple(t.shape) != tuple(self.shapes[name]):
-            raise ValueError(f"parameter {name}: expected shape {self.shapes[name]} (from FengwuConfig.{shape_source(name)}), got {tuple(t.shape)}")
-        return t

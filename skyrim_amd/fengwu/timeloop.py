@@ -5,76 +5,22 @@
 
 A loop continued from its own last output (run_basic_inference's resident state: ``rollout``) keeps counting its steps, so a non-finite
 state is reported with the step of the whole rollout; there is no cascade, every step runs the same network.
+
+``params``: mapping keyed by ``spec.full_param_spec``; default: ``SKYRIM_FENGWU_WEIGHTS`` (a directory with one *.onnx graph and the input
+affine, or a torch file of that dict), or seeded random parameters only with ``SKYRIM_SYNTHETIC_WEIGHTS=1`` (weights.resolve).
 """
 from __future__ import annotations
 
-import datetime
-
-import torch
-
-from .. import weights
-from ..timeloop import EngineTimeLoop, Grid
+from ..timeloop import HistoryTimeLoop
+from . import spec as _spec
 from .engine import FengwuEngine
-from .spec import CHANNELS, FengwuConfig, init_synthetic, latlon_axes, synthetic_state
 
 
-class FengwuTimeLoop(EngineTimeLoop):
-    n_history_levels = 2
-    time_step = datetime.timedelta(hours=6)
+class FengwuTimeLoop(HistoryTimeLoop):
+    engine_class, config_class, spec = FengwuEngine, _spec.FengwuConfig, _spec
+    weights_env, label = "SKYRIM_FENGWU_WEIGHTS", "fengwu"
+    guard_hint = "the FengWu network produced non-finite values"
+    synthetic_on_device = True
 
-    def __init__(self, params=None, cfg: FengwuConfig | None = None, device: str | torch.device = "cuda:0", seed: int = 0):
-        """``params``: mapping keyed by ``spec.full_param_spec``; default: ``SKYRIM_FENGWU_WEIGHTS`` (a directory with one *.onnx graph
-        and the input affine, or a torch file of that dict), or seeded random parameters only with ``SKYRIM_SYNTHETIC_WEIGHTS=1``
-        (weights.resolve)."""
-        self.cfg = cfg or FengwuConfig()
-        self.engine = FengwuEngine(self.cfg, device)
-        if params is None:
-            params = weights.resolve("SKYRIM_FENGWU_WEIGHTS", self._load, lambda: init_synthetic(self.cfg, seed, self.engine.device), "fengwu")
-        self.engine.load_params(params)
-        self.channel_std = torch.as_tensor(params["norm.std"]).float().reshape(-1)    # the scale of a perturbed ensemble member (skyrim_amd/ensemble.py)
-        self._channels(CHANNELS, self.cfg.channels)
-        lat, lon = latlon_axes(self.cfg)
-        self.grid = Grid(list(lat), list(lon))
-        self.guard = weights.FiniteGuard("the FengWu network produced non-finite values")
-        self._last = (None, 0)                  # (yielded tensor, its step) of the last yield
-
-    def _load(self, path: str):
-        from . import checkpoint
-        return checkpoint.load(path, self.cfg)
-
-    def synthetic_state(self, seed: int) -> torch.Tensor:
-        """Initial-condition hook of the synthetic DataSource."""
-        return synthetic_state(self.cfg, seed)
-
-    def take_pending_check(self):
-        """(flag, step, hint) of the last yielded state's deferred finite check, handed to the caller (models/utils.py)."""
-        p = self.guard.take()
-        return None if p is None else (p[0], p[1], self.guard.hint)
-
-    def _yield(self, time, state, step, restart, guard):
-        out = state.unsqueeze(0)
-        self._last = (out, step)
-        if step > 0:
-            guard.push(state, step)
-        return time, out, restart
-
-    def __call__(self, time: datetime.datetime, x: torch.Tensor, restart=None):
-        shape = (1, 2) + self.engine.state_shape
-        if x.dim() != 5 or tuple(x.shape) != shape:
-            raise ValueError(f"expected x of shape {shape} (states at time - 6 h and time), got {tuple(x.shape)}")
-        own = self.__dict__.pop("_state_is_own_output", False)      # run_basic_inference: x holds this loop's last outputs, still in HBM
-        step = self._last[1] if own else 0
-        x = x.to(self.device, torch.float32)
-        older, newer = x[0, 0].contiguous().clone(), x[0, 1].contiguous().clone()
-        # the deferred check belongs to THIS generator (several may be open at once: skyrim_amd/ensemble.py interleaves one per member);
-        # ``self.guard`` names the one opened last, which is the one take_pending_check's caller is draining
-        guard = self.guard = weights.FiniteGuard(self.guard.hint)
-        try:
-            yield self._yield(time, newer, step, restart, guard)
-            while True:
-                step += 1
-                older, newer = newer, self.engine.call(older, newer)
-                time = time + self.time_step
-                yield self._yield(time, newer, step, restart, guard)
-        finally:
-            guard.check()
+    def advance(self, older, newer, time, step):
+        return newer, self.engine.call(older, newer)

@@ -19,6 +19,7 @@ import datetime
 import torch
 
 from .. import native
+from ..engine import CheckedParams, Engine
 from .spec import STAGES, FuxiConfig, check_config, cpb_table, full_param_spec, param_spec, shift, time_encoding
 
 _P = ctypes.c_void_p
@@ -88,48 +89,36 @@ def tconv_matrix(w: torch.Tensor) -> torch.Tensor:
     return w.permute(2, 3, 1, 0).reshape(4 * w.shape[1], w.shape[0])
 
 
-class FuxiEngine:
+class FuxiEngine(Engine):
+    prepare_symbol = "skfuxi_prepare_weight"
+
     def __init__(self, cfg: FuxiConfig | None = None, device: str | torch.device = "cuda:0"):
         self.cfg = c = cfg or FuxiConfig()
         check_config(c)
-        self.lib = load_library()
-        self.device = torch.device(device)
-        self.state_shape = (c.channels, c.n_lat, c.n_lon)
-        self.prepared = False
-
-    def release(self):
-        """Drop every prepared matrix and work buffer (the C ABI holds no state of its own)."""
-        keep = ("cfg", "lib", "device", "state_shape")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
-        self.prepared = False
+        self._bind(load_library(), device, (c.channels, c.n_lat, c.n_lon))
 
     # ---- loading ---- #
-    def _hilo(self, w: torch.Tensor) -> native.HiLoWeight:
-        return native.HiLoWeight(self.device, self.lib.skfuxi_prepare_weight, w)
-
     def _prepare_stage(self, p) -> dict:
         c, dev = self.cfg, self.device
         f32 = lambda t: torch.as_tensor(t).float().contiguous().to(dev)          # noqa: E731
 
         def res(prefix):
-            return [dict(w=self._hilo(conv_matrix(p[f"{prefix}.res.{j}.conv.weight"])), b=f32(p[f"{prefix}.res.{j}.conv.bias"]),
+            return [dict(w=self._weight(conv_matrix(p[f"{prefix}.res.{j}.conv.weight"])), b=f32(p[f"{prefix}.res.{j}.conv.bias"]),
                          g=f32(p[f"{prefix}.res.{j}.norm.weight"]), beta=f32(p[f"{prefix}.res.{j}.norm.bias"])) for j in range(2)]
 
-        s = dict(embed=self._hilo(p["embed.weight"].reshape(c.embed, -1)), embed_b=f32(p["embed.bias"]), tw=f32(p["time_embed.weight"]),
+        s = dict(embed=self._weight(p["embed.weight"].reshape(c.embed, -1)), embed_b=f32(p["embed.bias"]), tw=f32(p["time_embed.weight"]),
                  tb=f32(p["time_embed.bias"]), en_g=f32(p["embed_norm.weight"]), en_b=f32(p["embed_norm.bias"]),
-                 down=self._hilo(conv_matrix(p["down.conv.weight"])), down_b=f32(p["down.conv.bias"]), down_res=res("down"), blocks=[])
+                 down=self._weight(conv_matrix(p["down.conv.weight"])), down_b=f32(p["down.conv.bias"]), down_res=res("down"), blocks=[])
         for i in range(c.depth):
             b = lambda n: p[f"blocks.{i}.{n}"]                                   # noqa: E731
             zero = torch.zeros(c.embed, dtype=torch.float32, device=b("attn.q_bias").device)
             cpb = cpb_table(c.window, b("attn.cpb_mlp.0.weight").cpu(), b("attn.cpb_mlp.0.bias").cpu(), b("attn.cpb_mlp.2.weight").cpu())
             s["blocks"].append(dict(
-                qkv=self._hilo(b("attn.qkv.weight")), qkv_b=f32(torch.cat([b("attn.q_bias").float(), zero, b("attn.v_bias").float()])),
-                scale=f32(b("attn.logit_scale").reshape(-1)), cpb=f32(cpb), proj=self._hilo(b("attn.proj.weight")), proj_b=f32(b("attn.proj.bias")),
-                n1_g=f32(b("norm1.weight")), n1_b=f32(b("norm1.bias")), fc1=self._hilo(b("mlp.fc1.weight")), fc1_b=f32(b("mlp.fc1.bias")),
-                fc2=self._hilo(b("mlp.fc2.weight")), fc2_b=f32(b("mlp.fc2.bias")), n2_g=f32(b("norm2.weight")), n2_b=f32(b("norm2.bias"))))
-        s.update(up=self._hilo(tconv_matrix(p["up.conv.weight"])), up_b=f32(p["up.conv.bias"]), up_res=res("up"), head=self._hilo(p["head.weight"]),
+                qkv=self._weight(b("attn.qkv.weight")), qkv_b=f32(torch.cat([b("attn.q_bias").float(), zero, b("attn.v_bias").float()])),
+                scale=f32(b("attn.logit_scale").reshape(-1)), cpb=f32(cpb), proj=self._weight(b("attn.proj.weight")), proj_b=f32(b("attn.proj.bias")),
+                n1_g=f32(b("norm1.weight")), n1_b=f32(b("norm1.bias")), fc1=self._weight(b("mlp.fc1.weight")), fc1_b=f32(b("mlp.fc1.bias")),
+                fc2=self._weight(b("mlp.fc2.weight")), fc2_b=f32(b("mlp.fc2.bias")), n2_g=f32(b("norm2.weight")), n2_b=f32(b("norm2.bias"))))
+        s.update(up=self._weight(tconv_matrix(p["up.conv.weight"])), up_b=f32(p["up.conv.bias"]), up_res=res("up"), head=self._weight(p["head.weight"]),
                  head_b=f32(p["head.bias"]))
         return s
 
@@ -141,15 +130,9 @@ class FuxiEngine:
             if name not in params:
                 raise ValueError(f"parameter {name} missing (expected shape {shape})")
         with torch.cuda.device(dev):
-            std = torch.as_tensor(params["norm.std"]).double()
-            if tuple(std.shape) != (c.channels,) or not bool((std != 0).all()):
-                raise ValueError(f"norm.std must hold {c.channels} non-zero values")
-            self.mean = torch.as_tensor(params["norm.mean"]).float().contiguous().to(dev)
-            self.std, self.inv_std = std.float().to(dev), (1.0 / std).float().to(dev)
-            self.stages = {}
-            for st in STAGES:
-                view = _StageView(params, st, dict(param_spec(c)))
-                self.stages[st] = self._prepare_stage(view)
+            self.upload_affine(params["norm.mean"], params["norm.std"], c.channels)
+            shapes = dict(param_spec(c))
+            self.stages = {st: self._prepare_stage(CheckedParams(params, shapes, prefix=f"{st}.")) for st in STAGES}
             C, (h0, w0), (h1, w1) = c.embed, c.grid0, c.grid1
             t0, t1 = h0 * w0, h1 * w1
             z = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)         # noqa: E731
@@ -243,13 +226,11 @@ class FuxiEngine:
 
     def call(self, x0: torch.Tensor, x1: torch.Tensor, time: datetime.datetime, stage: str = "short"):
         """One network call of ``stage``: states at time - 6 h (x0) and time (x1) -> a new tensor, the state at time + 6 h."""
-        if not self.prepared:
-            raise RuntimeError("FuxiEngine.call before load_params: not prepared")
+        self.require_prepared("call")
         if stage not in STAGES:
             raise ValueError(f"stage {stage!r} not one of {STAGES}")
-        for t, w in ((x0, "x0"), (x1, "x1")):
-            if t.device != self.device or t.dtype != torch.float32 or tuple(t.shape) != self.state_shape or not t.is_contiguous():
-                raise ValueError(f"{w}: expected a contiguous float32 tensor of shape {self.state_shape} on {self.device}")
+        self.check_state(x0, "x0")
+        self.check_state(x1, "x1")
         c, S, b = self.cfg, self.stages[stage], self.buf
         g0, g1 = c.grid0, c.grid1
         t0 = g0[0] * g0[1]
@@ -267,16 +248,3 @@ class FuxiEngine:
             self.linear(b["u"], S["head"], S["head_b"], b["head"], t0, head=True)
             self.resample(b["head"], y)
         return y
-
-
-class _StageView:
-    """``params`` seen through one stage's prefix, shape-checked on read."""
-
-    def __init__(self, params, stage: str, shapes: dict):
-        self.params, self.stage, self.shapes = params, stage, shapes
-
-    def __getitem__(self, name):
-        t = torch.as_tensor(self.params[f"{self.stage}.{name}"])
-        if tuple(t.shape) != tuple(self.shapes[name]):
-            raise ValueError(f"parameter {self.stage}.{name}: expected shape {self.shapes[name]}, got {tuple(t.shape)}")
-        return t

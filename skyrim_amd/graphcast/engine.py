@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from .. import native, ops
+from ..engine import Engine
 from ..sfno import engine as _sf
 from . import fused as _fz
 from .mesh import renumber_mesh, spatial_order, GraphStructure, build_graph, grouped_rows_by3, latitude_band, shard_graph
@@ -80,7 +81,9 @@ def load_library() -> ctypes.CDLL:
     return _lib
 
 
-class GraphcastEngine:
+class GraphcastEngine(Engine):
+    keep = ("rank", "world", "reduce_fn", "gather_fn", "sf")
+
     def __init__(self, cfg: GraphcastConfig | None = None, device: str | torch.device = "cuda:0", graph: GraphStructure | None = None,
                  shard: tuple[int, int] = (0, 1), reduce_fn=None, gather_fn=None):
         """``shard = (rank, world)``: one forecast over ``world`` GPUs (BASELINE configs[3]).  GRID side: this engine owns a latitude
@@ -106,17 +109,15 @@ class GraphcastEngine:
             raise RuntimeError("GraphcastEngine needs an MI355X: the GraphCast path has no CPU fallback")
         if self.cfg.latent % 8 != 0:
             raise ValueError("latent must be a multiple of 8")
-        self.lib = load_library()
         self.sf = _sf.load_library()
-        self.device = torch.device(device)
+        self.lat0, self.lat1 = latitude_band(self.cfg.n_lat, self.rank, self.world)
+        self._bind(load_library(), device, (self.cfg.n_vars, self.lat1 - self.lat0, self.cfg.n_lon))
         full = graph or build_graph(self.cfg.n_lat, self.cfg.n_lon, self.cfg.splits)
         # The multi-mesh numbers its nodes level by level; the engine works on a spatially coherent numbering (Morton order of the node
         # positions) so that the sender rows gathered for neighbouring receivers -- neighbouring tiles of the receiver-sorted edge list -- are
         # neighbours in memory too.  Mesh nodes never leave the engine: invisible outside.
         full = renumber_mesh(full, spatial_order(full.mesh_pos))
-        self.lat0, self.lat1 = latitude_band(self.cfg.n_lat, self.rank, self.world)
         self.graph = full if self.world == 1 else shard_graph(full, self.cfg.n_lat, self.cfg.n_lon, self.rank, self.world)
-        self.prepared = False
         self.profiling = False
         self._events = []
         self.fused_ln = self.cfg.latent == 512
@@ -130,16 +131,11 @@ class GraphcastEngine:
         # planes of the processor edge MLPs' first Linear (edge part): 1 = W_e as one fp16 plane (one MFMA term: +1.4e-4 of the predicted
         # increment at production width and depth, tools/graphcast_numerics.py); the edge kernel also takes 2 = hi/lo planes (two terms)
         self.w1_planes = 1
-        self.state_shape = (self.cfg.n_vars, self.lat1 - self.lat0, self.cfg.n_lon)
 
     def release(self):
-        """Drop the packed graph, every prepared weight and all latent / work buffers (~47 GB at 721x1440; GlobalModel.release_model).  The C ABI
-        holds no state of its own: all device memory is torch tensors owned here.  The engine is unusable afterwards."""
-        keep = ("cfg", "rank", "world", "reduce_fn", "gather_fn", "lib", "sf", "device", "state_shape")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
-        self.prepared = False
+        """Drop the packed graph, every prepared weight and all latent / work buffers (~47 GB at 721x1440; GlobalModel.release_model).
+        The engine is unusable afterwards."""
+        super().release()
         self._events = []
 
     def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
@@ -504,8 +500,7 @@ class GraphcastEngine:
     # ---- step ----------------------------------------------------------------------------------------- #
     def step(self, x_prev: torch.Tensor, x_cur: torch.Tensor, forcing: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """(83, n_lat, n_lon) states at t-6h and t, (15, n_lat, n_lon) forcings -> state at t+6h (fp32, engine device)."""
-        if not self.prepared:
-            raise RuntimeError("GraphcastEngine.step before load_params: not prepared")
+        self.require_prepared("step")
         c, L = self.cfg, self.cfg.latent
         fshape = (N_FORCING,) + self.state_shape[1:]
         for t, shape in ((x_prev, self.state_shape), (x_cur, self.state_shape), (forcing, fshape)):

@@ -78,7 +78,7 @@ def tensor_ptr(t, what: str, dtype, dev=None) -> int:
 class HiLoWeight:
     """A constant matrix [batch][N][K] (2-D: batch 1) as fp16 hi/lo planes on ``device``: ``buf`` holds the hi planes of every batch
     entry ([batch][N][ldw], ldw = K rounded up to 8), then the lo planes ``plane`` elements further; ``w_sb`` is the batch stride.
-    ``prepare``: the library's split entry point (sksfno_prepare_weight / skfcn_prepare_weight, one signature)."""
+    ``prepare``: the library's split entry point (``sk*_prepare_weight``, one signature; ``engine.Engine._weight`` names it per engine)."""
 
     def __init__(self, device: torch.device, prepare, w: torch.Tensor):
         w = w.float().contiguous()

@@ -275,6 +275,59 @@ def auto_map_slots(model: Model, slots: list, window: int = 16) -> tuple[dict, l
     return mapping, [s for (s, _), tk in zip(slots, taken) if not tk]
 
 
+def map_slots(model: Model, slots: list, explicit: dict | None = None) -> tuple[dict, list]:
+    """{slot: [onnx_name, transform]} and the list of unresolved slots: the ``explicit`` mapping ({slot: onnx_name | [onnx_name,
+    transform]}) where one is given, ``auto_map_slots`` otherwise."""
+    if explicit is not None:
+        mapping = {k: (v if isinstance(v, list) else [v, "id"]) for k, v in explicit.items()}
+        return mapping, [s for s, _ in slots if s not in mapping]
+    return auto_map_slots(model, slots)
+
+
+def load_graph_slots(graph: str, slots: list, map_file: str, source=None) -> dict:
+    """One ONNX graph of a model directory (FuXi's stages, FengWu) -> {slot: float32 tensor} for every (slot, shape) of ``slots``.
+    External data is opted in with the graph's directory as base; ``map_file`` (read if it exists) gives the mapping explicitly.  Nothing
+    partial comes back: unresolved slots, a mapped name that is no slot, a missing initializer and a failed transform are refused by name.
+    ``source(slot)`` says where a slot's shape comes from, for the last of these."""
+    import os
+
+    import torch
+    model = read_model(graph, base_dir=os.path.dirname(graph))
+    explicit, map_name = None, os.path.basename(map_file)
+    if os.path.exists(map_file):
+        with open(map_file) as fh:
+            explicit = json.load(fh)
+    mapping, unresolved = map_slots(model, slots, explicit)
+    if unresolved:
+        raise ValueError(f"{graph}: {len(unresolved)} parameter slots unresolved: {unresolved}; write {map_name} "
+                         "({slot: onnx_name | [onnx_name, transform]}) next to it")
+    shapes, out = dict(slots), {}
+    for slot, (name, how) in mapping.items():
+        if slot not in shapes:
+            raise KeyError(f"{map_name}: {slot!r} is not a parameter slot of this config")
+        if name not in model.initializers:
+            raise KeyError(f"{slot}: initializer {name!r} not in {graph}")
+        try:
+            out[slot] = torch.from_numpy(_apply(model.initializers[name].array().astype(np.float32), how, shapes[slot]))
+        except ValueError as e:
+            origin = f" (shape from {source(slot)})" if source else ""
+            raise ValueError(f"{graph}: slot {slot}{origin}: initializer {name!r}: {e}") from None
+    return out
+
+
+def read_norm_json(directory: str):
+    """``norm.json`` ({"mean": [...], "std": [...]}: the input affine of a model directory) -> (mean, std) float32 tensors; None without the file."""
+    import os
+
+    import torch
+    path = os.path.join(directory, "norm.json")
+    if not os.path.exists(path):
+        return None
+    with open(path) as f:
+        n = json.load(f)
+    return torch.tensor(n["mean"], dtype=torch.float32), torch.tensor(n["std"], dtype=torch.float32)
+
+
 def validate(arrays: dict) -> list[str]:
     """Plausibility of a converted parameter set, slot class by slot class -- what a WRONG slot assignment (several slots of a block
     share a shape: proj.bias, norm1.weight, norm1.bias, fc2.bias, norm2.* are all (C,)) or a wrong layout would break:

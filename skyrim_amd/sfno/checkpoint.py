@@ -11,11 +11,13 @@ reports every key it could not place, so that a naming difference surfaces as an
 """
 from __future__ import annotations
 
+import os
 import re
 
 import numpy as np
 import torch
 
+from .. import weights
 from .spec import SfnoConfig, param_spec
 
 # checkpoint key (after stripping "module." / "model.") -> slot; {i} = block index
@@ -80,7 +82,17 @@ def convert(state_dict: dict, cfg: SfnoConfig, means, stds) -> dict:
     return out
 
 
-def load(path, cfg: SfnoConfig, means_path, stds_path) -> dict:
+def load_files(path, cfg: SfnoConfig, means_path, stds_path) -> dict:
     ck = torch.load(path, map_location="cpu")
     sd = ck.get("model_state", ck) if isinstance(ck, dict) else ck
     return convert(sd, cfg, np.load(means_path), np.load(stds_path))
+
+
+def load_package(path: str, cfg: SfnoConfig) -> dict:
+    """The reference's own package: a directory holding ``weights.tar``, ``global_means.npy`` and ``global_stds.npy`` (earth2mip's
+    fcnv2_sm layout), mapped by ``convert``."""
+    return load_files(os.path.join(path, "weights.tar"), cfg, os.path.join(path, "global_means.npy"), os.path.join(path, "global_stds.npy"))
+
+
+def load(path: str, cfg: SfnoConfig) -> dict:
+    return weights.load_slots(path, lambda d: load_package(d, cfg))

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .. import native, ops
+from ..engine import Engine
 from .sht import ShtMatrices
 from .spec import SfnoConfig, param_spec
 
@@ -110,7 +111,10 @@ def _pad1(v: torch.Tensor, n: int) -> torch.Tensor:
     return out
 
 
-class SfnoEngine:
+class SfnoEngine(Engine):
+    keep = ("terms", "fused", "_label", "profiling")
+    prepare_symbol = "sksfno_prepare_weight"
+
     def __init__(self, cfg: SfnoConfig | None = None, device: str | torch.device = "cuda:0", terms: int = 3, fused: bool | None = None):
         """``terms``: MFMA terms per GEMM -- 3: activations and constants as fp16 hi/lo pairs (fp32-class, ~1e-6 vs the oracle);
         2: activations rounded to one fp16 plane (faster; error measured in tests/test_sfno_gpu.py).
@@ -125,29 +129,17 @@ class SfnoEngine:
         self.chain = None                 # shape class of the fused chains, set by load_params
         if not torch.cuda.is_available():
             raise RuntimeError("SfnoEngine needs an MI355X: the SFNO path has no CPU fallback")
-        self.lib = load_library()
-        self.device = torch.device(device)
-        self.prepared = False
+        c = self.cfg
+        self._bind(load_library(), device, (c.in_chans, c.n_lat, c.n_lon))
         self.profiling = False            # per-launch timing with events on the launch stream (bench.py / tools)
         self._events = []
-        c = self.cfg
         if c.num_layers < 2:
             raise ValueError("num_layers >= 2 (the first block goes to the internal grid, the last one back)")
-        self.state_shape = (c.in_chans, c.n_lat, c.n_lon)
         self._label = "gemm"
 
-    def _weight(self, w: torch.Tensor) -> native.HiLoWeight:
-        return native.HiLoWeight(self.device, self.lib.sksfno_prepare_weight, w)
-
     def release(self):
-        """Drop every prepared matrix, table and work buffer (GlobalModel.release_model).  The C ABI holds no state of its own -- all device
-        memory is torch tensors owned here -- so this IS the teardown; the engine is unusable until ``load_params`` runs again."""
-        keep = ("cfg", "terms", "fused", "lib", "device", "state_shape", "_label", "profiling")
-        kept = {k: v for k, v in vars(self).items() if k in keep}
-        self.__dict__.clear()
-        self.__dict__.update(kept)
+        super().release()
         self.chain = None
-        self.prepared = False
         self._events = []
 
     # ---- prepare ---------------------------------------------------------------------------------- #
@@ -344,11 +336,9 @@ class SfnoEngine:
 
     def step(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """One 6-h step: fp32 (in_chans, n_lat, n_lon) on the engine device -> (out_chans, n_lat, n_lon)."""
-        if not self.prepared:
-            raise RuntimeError("SfnoEngine.step before load_params: not prepared")
+        self.require_prepared("step")
         c = self.cfg
-        if x.device != self.device or x.dtype != torch.float32 or tuple(x.shape) != self.state_shape or not x.is_contiguous():
-            raise ValueError(f"expected a contiguous float32 tensor of shape {self.state_shape} on {self.device}")
+        self.check_state(x)
         e, hid = c.embed_dim, c.embed_dim * c.mlp_ratio
         hw_o = c.n_lat * c.n_lon
         with torch.cuda.device(self.device):

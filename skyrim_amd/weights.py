@@ -24,6 +24,15 @@ def resolve(env_var: str, load: Callable[[str], dict], synthetic: Callable[[], d
                        "SKYRIM_SYNTHETIC_WEIGHTS=1 to run on seeded random-init parameters (benchmarks / tests)")
 
 
+def load_slots(path: str, read_package: Callable[[str], dict]) -> dict:
+    """What every ``*/checkpoint.load(path, cfg)`` does with a weight path: a directory is the model's package (``read_package``), anything
+    else a torch file of the slot dict, read as it is."""
+    if os.path.isdir(path):
+        return read_package(path)
+    import torch
+    return torch.load(path, map_location="cpu")
+
+
 class FiniteGuard:
     """Deferred non-finite check of the yielded states: the flag of step k is computed on the stream and read when step k + 1
     is about to be yielded, so it never stalls the rollout.  fp16-plane modes overflow above 65504."""

@@ -294,6 +294,29 @@ def test_onnx_unresolved_slots_are_reported(tmp_path):
         checkpoint.load(str(tmp_path), cfg)
 
 
+def test_the_graph_is_one_graph_of_the_shared_reader(tmp_path):
+    from skyrim_amd.fengwu import checkpoint
+    from skyrim_amd.fengwu.spec import init_synthetic, param_spec
+    from skyrim_amd.pangu.onnx_weights import load_graph_slots, read_model
+    cfg = _toy()
+    params = {k: v.float() for k, v in init_synthetic(cfg, 2).items()}
+    _onnx_dir(tmp_path, cfg, params)
+    graph = load_graph_slots(str(tmp_path / "fengwu.onnx"), param_spec(cfg), str(tmp_path / checkpoint.MAP_FILE))
+    assert list(graph) == [s for s, _ in param_spec(cfg)] and all(torch.equal(t, params[s]) for s, t in graph.items())
+    # norm.json stands in for the two .npy files, with the same size check
+    (tmp_path / "global_means.npy").unlink()
+    with pytest.raises(ValueError, match=r"the input affine is missing \(global_means\.npy \+ global_stds\.npy, or norm\.json\)"):
+        checkpoint.load(str(tmp_path), cfg)
+    (tmp_path / "norm.json").write_text(json.dumps({"mean": params["norm.mean"].tolist(), "std": params["norm.std"].tolist()}))
+    got = checkpoint.load(str(tmp_path), cfg)
+    assert torch.equal(got["norm.mean"], params["norm.mean"]) and torch.equal(got["norm.std"], params["norm.std"])
+    # a mapped name that is no slot of this config
+    mapping, _ = checkpoint.graph_mapping(read_model(tmp_path / "fengwu.onnx", base_dir=tmp_path), cfg)
+    (tmp_path / checkpoint.MAP_FILE).write_text(json.dumps(dict(mapping, **{"enc.w.embed.bias": mapping["enc.z.embed.bias"]})))
+    with pytest.raises(KeyError, match=r"fengwu\.map\.json: 'enc\.w\.embed\.bias' is not a parameter slot of this config"):
+        checkpoint.load(str(tmp_path), cfg)
+
+
 def test_shape_mismatch_names_the_slot_and_the_field(tmp_path):
     from skyrim_amd.fengwu import checkpoint
     from skyrim_amd.fengwu.engine import FengwuEngine

@@ -238,6 +238,45 @@ def test_onnx_unresolved_slots_are_reported(tmp_path):
         checkpoint.load(str(tmp_path), cfg)
 
 
+def test_a_stage_is_one_graph_of_the_shared_reader(tmp_path):
+    from skyrim_amd.fuxi import checkpoint
+    from skyrim_amd.fuxi.spec import init_synthetic, param_spec
+    from skyrim_amd.pangu.onnx_weights import load_graph_slots, read_norm_json
+    cfg = _toy(depth=1, embed=256, heads=4, groups=8)
+    params = dict(init_synthetic(cfg, 2))
+    _onnx_dir(tmp_path, cfg, params)
+    stage = load_graph_slots(str(tmp_path / "long.onnx"), param_spec(cfg), str(tmp_path / "long.map.json"))
+    got = checkpoint.load(str(tmp_path), cfg)
+    assert list(stage) == [s for s, _ in param_spec(cfg)]
+    for slot, t in stage.items():
+        assert t.dtype == torch.float32 and torch.equal(t, got[f"long.{slot}"]) and torch.equal(t, params[f"long.{slot}"].float()), slot
+    mean, std = read_norm_json(str(tmp_path))
+    assert torch.equal(mean, got["norm.mean"]) and torch.equal(std, got["norm.std"]) and read_norm_json(str(tmp_path / "nowhere")) is None
+    (tmp_path / "norm.json").unlink()
+    with pytest.raises(ValueError, match=r'norm\.json missing -- the input affine \(\{"mean": \[6\], "std": \[6\]\}\) of the graphs'):
+        checkpoint.load(str(tmp_path), cfg)
+
+
+def test_onnx_map_with_an_unknown_slot_or_a_failed_transform_is_refused_by_name(tmp_path):
+    """The refusals of the directory reader FuXi shares with FengWu (pangu/onnx_weights.load_graph_slots): a mapped name that is no slot
+    of the config, and a transform that does not give the slot's shape -- reported with the graph, the slot and the initializer."""
+    from skyrim_amd.fuxi import checkpoint
+    from skyrim_amd.fuxi.spec import init_synthetic
+    from skyrim_amd.pangu.onnx_weights import read_model
+    cfg = _toy(depth=1, embed=256, heads=4, groups=8)
+    _onnx_dir(tmp_path, cfg, dict(init_synthetic(cfg, 2)))
+    mapping, _ = checkpoint.stage_mapping(read_model(tmp_path / "medium.onnx", base_dir=tmp_path), cfg)
+    (tmp_path / "medium.map.json").write_text(json.dumps(dict(mapping, **{"blocks.9.norm1.weight": mapping["embed.bias"]})))
+    with pytest.raises(KeyError, match=r"medium\.map\.json: 'blocks\.9\.norm1\.weight' is not a parameter slot of this config"):
+        checkpoint.load(str(tmp_path), cfg)
+    (tmp_path / "medium.map.json").write_text(json.dumps(dict(mapping, **{"embed.bias": mapping["head.weight"]})))
+    with pytest.raises(ValueError, match=r"medium\.onnx: slot embed\.bias: initializer 'onnx::MatMul_\d+': shape \(\d+, 256\) after 'T', slot wants \(256,\)"):
+        checkpoint.load(str(tmp_path), cfg)
+    (tmp_path / "medium.map.json").write_text(json.dumps(dict(mapping, **{"embed.bias": "no_such_tensor"})))
+    with pytest.raises(KeyError, match=r"embed\.bias: initializer 'no_such_tensor' not in .*medium\.onnx"):
+        checkpoint.load(str(tmp_path), cfg)
+
+
 def test_external_data_without_the_opt_in_is_refused_as_before(tmp_path):
     from skyrim_amd.fuxi.spec import init_synthetic
     from skyrim_amd.pangu.onnx_weights import read_model
